@@ -3,6 +3,11 @@
 node-expansions/s at 800 sims on 8x8).
 
     python bench.py --gpus N --steps K --warmup W          (N=1: plain python; N>1: torchrun)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py --gpus 1 --steps K --warmup W --full                 (+ every extra leg and figure below)
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds the
+roofline pass, the extra legs and the CPU baseline described below.
 
 A "step" = one lockstep MOVE of all G concurrent games = 1 root evaluation + `sims` simulations,
 each simulation being one fused HIP tree kernel + one batched CNN forward over the leaves that need
@@ -13,8 +18,9 @@ batch is in the steady state of continuous self-play.  value = positions/s over 
 
 The headline leg runs the evaluator at the REFERENCE's precision: `--nn f16x3` = the split-f16 tower
 (csrc/yy_tower_g.hip + yy_fc_heads.hip: float32-accurate, identical visit counts to the reference's CPU float32 search on
-every golden root at 6x6, 8x8, 12x12 and three non-default shapes -- tests/test_gpu_mcts.py::test_live_gpu_evaluator_search_vs_reference_pi).  At N=1 one more
-leg is timed in the same run and reported as an extra key of the same JSON line: `secondary` = the bf16
+every golden root at 6x6, 8x8, 12x12 and three non-default shapes -- tests/test_gpu_mcts.py::test_live_gpu_evaluator_search_vs_reference_pi).  With --full,
+the main leg is followed by a roofline pass (`roofline`, `roofline_tree_kernel`, `nn_forward_ms`, ...), the CPU baseline
+(`cpu_baseline`, N=1 only) and, at N=1, more legs timed in the same run and reported as extra keys of the same JSON line: `secondary` = the bf16
 tower (reduced precision: NOT the headline); `--oversubscribe G2` adds a leg with G2 concurrent games (`oversubscribed`);
 `with_evaluation_reuse` is the same workload with the engine's evaluation reuse on (off in the headline).
 """
@@ -54,11 +60,17 @@ def parse():
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--nn", default="f16x3", choices=NN_MODES,
                     help="evaluator of the headline leg; f16x3 = float32-accurate (the reference evaluates in float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline pass, CPU baseline and the extra legs (--secondary-nn, --reuse-steps, "
+                         "--oversubscribe); off by default, so that a plain run times the headline and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main leg's last timed step computed as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB in all; see write_outputs)")
     ap.add_argument("--secondary-nn", default="bf16", choices=NN_MODES + ["none"],
-                    help="N=1 only: a second, shorter leg with this evaluator, reported under `secondary`")
+                    help="--full, N=1 only: a second, shorter leg with this evaluator, reported under `secondary`")
     ap.add_argument("--secondary-steps", type=int, default=3)
     ap.add_argument("--oversubscribe", type=int, default=0,
-                    help="N=1 only: a third leg with this many concurrent games (compacted leaf batch ~ whole workgroup "
+                    help="--full, N=1 only: a third leg with this many concurrent games (compacted leaf batch ~ whole workgroup "
                          "rounds); 0 (default) = skip: measured neutral, the launch time is proportional to the live rows")
     ap.add_argument("--oversubscribe-steps", type=int, default=3)
     ap.add_argument("--reuse-evaluations", type=int, default=0,
@@ -67,7 +79,7 @@ def parse():
     ap.add_argument("--book-stones", type=int, default=8,
                     help="legs with evaluation reuse also get a shared opening book: every position reachable with at most this "
                          "many stones, evaluated once before the timed region (0 = none; boards of at most 64 cells)")
-    ap.add_argument("--reuse-steps", type=int, default=10, help="steps of the extra leg with evaluation reuse on (0 = skip)")
+    ap.add_argument("--reuse-steps", type=int, default=10, help="--full: steps of the extra leg with evaluation reuse on (0 = skip)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): --games concurrent games PER GPU; strong: --games in total, split over the ranks "
                          "(SURVEY 8d config 3: 8 x 512)")
@@ -82,7 +94,7 @@ def parse():
     ap.add_argument("--semantics", default="copied", choices=["copied", "aliased"])
     ap.add_argument("--quirks", action="store_true", help="reference_quirks (Q4/Q5)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline sample: half per board semantics")
     ap.add_argument("--cpu-workers", type=int, default=0, help="CPU baseline processes (0 = one per host core, at most 16)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="run only the CPU baseline leg (no GPU needed) and print it")
@@ -362,12 +374,12 @@ def cpu_baseline(args):
 
 
 # ------------------------------------------------------------------------------------------- one timed leg
-def timed_region(eng, steps, warmup, rank, world, dist, cdev, sims, capacity=None):
+def timed_region(eng, steps, warmup, rank, world, dist, cdev, sims, capacity=None, keep_examples=False):
     """The contract's timed region for one engine: W untimed warm-up steps, then EXACTLY K steps bracketed by a barrier +
     torch.cuda.synchronize() on both sides, the MAX of the elapsed time over ranks, the SUM of positions / evaluator rows
     over ranks, and the path's single exchange (all-gather of the examples produced in the region) after it.  `eng` needs
     play_move() -> positions, collect() -> example dict, ctx.status() / ctx.reset_counters(), G (tests drive this with a
-    stand-in engine under gloo, world 2)."""
+    stand-in engine under gloo, world 2).  keep_examples: the gathered examples are returned under `examples_out`."""
     from yinyang_game_alphazero_amd.self_play import gather_examples
     on_gpu = torch.cuda.is_available()
 
@@ -407,13 +419,72 @@ def timed_region(eng, steps, warmup, rank, world, dist, cdev, sims, capacity=Non
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         dt = float(mx[2])
-    return dict(games=eng.G, steps=steps, dt=dt, positions=float(tot[0]), evals=float(tot[1]), served=float(tot[3]), gather_s=gather_s,
-                examples=int(ex_all["states"].shape[0]), sims_total=steps * sims * eng.G * world, warmup=warmup,
-                step_ms=[round((b - a) * 1e3, 1) for a, b in zip(marks[:-1], marks[1:])],
-                eval_fraction=counters["evals"] / max(steps * sims * eng.G, 1))
+    leg = dict(games=eng.G, steps=steps, dt=dt, positions=float(tot[0]), evals=float(tot[1]), served=float(tot[3]), gather_s=gather_s,
+               examples=int(ex_all["states"].shape[0]), sims_total=steps * sims * eng.G * world, warmup=warmup,
+               step_ms=[round((b - a) * 1e3, 1) for a, b in zip(marks[:-1], marks[1:])],
+               eval_fraction=counters["evals"] / max(steps * sims * eng.G, 1))
+    if keep_examples:
+        leg["examples_out"] = ex_all
+    return leg
 
 
-def run_leg(args, nn, games, steps, warmup, rank, world, dist, cdev, with_roofline, reuse=None):
+# ------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 60 << 20          # payload of all .npy files together (the limit is 64 MB: headers and rounding stay well inside)
+DUMP_GAME_BYTES = 24 << 20     # of which the per-game arrays at most; the examples take the rest
+
+
+def last_step_outputs(eng, examples):
+    """What the timed path computed in its last step, as host arrays: per game slot (lanes in order), the root policy of that
+    move's search (visit counts / visits, the reference's pi), the root's visit count and mean value, and the game's global
+    index, board, player to move and ply after the move; and the training examples the timed steps produced (gathered over
+    the ranks), the arrays a caller of the self-play path receives.  Slots that did not search in the last step hold zeros
+    in the search arrays."""
+    lanes = getattr(eng, "lanes", [eng])
+    torch.cuda.synchronize()
+    per = {k: [] for k in ("pi", "root_visits", "root_value", "game_id", "boards", "players", "ply")}
+    for ln in lanes:
+        with ln._on_stream():
+            pi = ln.ctx.root_policy()
+            visits, wsum = ln.ctx.root_stats()
+        torch.cuda.synchronize()
+        active = pi.sum(1) > 0                                     # k_root_policy writes a zero row for a game that did not search
+        visits = torch.where(active, visits, torch.zeros_like(visits))
+        per["pi"].append(pi)
+        per["root_visits"].append(visits.to(torch.float32))
+        per["root_value"].append(torch.where(visits > 0, wsum / visits.clamp_min(1).to(torch.float64), torch.zeros_like(wsum)))
+        per["game_id"].append(ln.game_id.to(torch.float64))
+        per["boards"].append(ln.boards.to(torch.float32))
+        per["players"].append(ln.players.to(torch.float32))
+        per["ply"].append(ln.ply.to(torch.float32))
+    games = {k: torch.cat(v).cpu().numpy() for k, v in per.items()}
+    ex = {"examples_" + k: v.cpu().numpy().astype(np.float64 if k == "game_id" else np.float32) for k, v in examples.items()}
+    return games, ex
+
+
+def sample_rows(arrays, max_bytes, seed):
+    """`arrays` share their first axis; if together they exceed max_bytes, keep a fixed, seeded subset of the rows (in row
+    order) that fits, and say which under `<first name>_rows` -- np.random.default_rng(seed).choice without replacement."""
+    n = len(next(iter(arrays.values())))
+    per_row = sum(a.nbytes // max(len(a), 1) for a in arrays.values())
+    if n == 0 or n * per_row <= max_bytes:
+        return arrays
+    keep = np.sort(np.random.default_rng(seed).choice(n, max(1, max_bytes // (per_row + 8)), replace=False))
+    out = {k: a[keep] for k, a in arrays.items()}
+    out[next(iter(arrays)) + "_rows"] = keep.astype(np.float64)
+    return out
+
+
+def write_outputs(path, games, examples):
+    """DIR/<name>.npy for every array of last_step_outputs, float32 or float64, DUMP_BYTES at most in all."""
+    os.makedirs(path, exist_ok=True)
+    games = sample_rows(games, DUMP_GAME_BYTES, seed=1)
+    examples = sample_rows(examples, DUMP_BYTES - sum(a.nbytes for a in games.values()), seed=2)
+    for name, a in {**games, **examples}.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def run_leg(args, nn, games, steps, warmup, rank, world, dist, cdev, with_roofline, reuse=None, dump=False):
     import yinyang_game_alphazero_amd as pkg
     from yinyang_game_alphazero_amd.self_play import SelfPlayLanes, example_capacity
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -438,7 +509,9 @@ def run_leg(args, nn, games, steps, warmup, rank, world, dist, cdev, with_roofli
                          keep_evaluations=bool(args.reuse_evaluations if reuse is None else reuse))
     stagger_start(eng, 4242 + rank)
     leg = timed_region(eng, steps, warmup, rank, world, dist, cdev, args.sims,
-                       capacity=example_capacity(games * world, world, eng.T))
+                       capacity=example_capacity(games * world, world, eng.T), keep_examples=dump)
+    if dump:
+        leg["outputs"] = last_step_outputs(eng, leg.pop("examples_out"))
     leg["nn"], leg["reuse"] = nn, eng.reuse_pass_value or eng.reuse_transpositions
     if book is not None:
         leg["book"] = dict(max_stones=book.max_stones, positions=book.n, stored=book.stored, bytes=book.bytes, build_s=book_s,
@@ -583,10 +656,10 @@ def main():
     if args.scaling == "strong":
         assert args.games % world == 0, "--scaling strong: --games must divide by the number of ranks"
     per_rank = args.games if args.scaling == "weak" else args.games // world
-    main_leg = run_leg(args, args.nn, per_rank, args.steps, args.warmup, rank, world, dist, cdev, with_roofline=True)
+    main_leg = run_leg(args, args.nn, per_rank, args.steps, args.warmup, rank, world, dist, cdev, with_roofline=args.full,
+                       dump=bool(args.dump_outputs) and rank == 0)
     extra = {}
-    default_workload = (args.games, args.rows, args.cols, args.sims, args.channels, args.blocks) == (4096, 8, 8, 800, 128, 10)
-    if world == 1:
+    if world == 1 and args.full:
         if args.secondary_nn not in ("none", args.nn):
             leg = run_leg(args, args.secondary_nn, args.games, args.secondary_steps, 1, rank, world, dist, cdev, False)
             extra["secondary"] = leg_summary(leg, "same workload, %s evaluator%s" % (
@@ -628,11 +701,13 @@ def main():
                                                        "launch carries ~3950-4050 live rows = just under 8 whole rounds of 2-board workgroups "
                                                        "on 256 CUs")
     cpub = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only
         cpub = cpu_baseline(args)
     if dist is not None:
         dist.barrier()
     if rank == 0:
+        if "outputs" in main_leg:
+            write_outputs(args.dump_outputs, *main_leg.pop("outputs"))
         print(json.dumps(result_line(args, main_leg, world, extra, cpub)))
     if dist is not None:
         dist.destroy_process_group()

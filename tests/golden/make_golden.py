@@ -665,7 +665,7 @@ def gen_select_action():
 
 # --------------------------------------------------------------------------- trainer
 def gen_trainer():
-    """trainer.npz: the reference's AlphaZeroTrainer.train (trainer.py:67-161) for 2 epochs on a 16-channel / 1-block net,
+    """trainer.part*.npz: the reference's AlphaZeroTrainer.train (trainer.py:67-161) for 2 epochs on a 16-channel / 1-block net,
     batch 8, no augmentation, fixed seeds: the examples, the batch order its DataLoader used, the policy / value loss of
     every step and every parameter / buffer after the last step."""
     import tempfile
@@ -733,8 +733,10 @@ def gen_trainer():
         out["init/" + k] = v
     for k, v in final.items():
         out["final/" + k] = v
-    path = os.path.join(OUT, "trainer.npz")
-    np.savez_compressed(path, **out)
+    sys.path.insert(0, os.path.dirname(OUT))
+    from npz_parts import save_parts
+    path = os.path.join(OUT, "trainer")
+    save_parts(path, out)                  # trainer.part*.npz: the fixture is larger than one committed file may be
     print("wrote", path, "steps", len(log["p"]), "losses", metrics["total_loss"], flush=True)
 
 

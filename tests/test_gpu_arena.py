@@ -257,13 +257,13 @@ def test_cli_self_play_two_ranks_equals_one_rank(tmp_path):
 
 
 def test_bench_json_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's contract keys, the roofline and cpu_baseline objects."""
+    """bench.py --full prints ONE JSON line with the driver's contract keys, the roofline and cpu_baseline objects."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                        "--games", "256", "--sims", "40", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900)
+                        "--games", "256", "--sims", "40", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -295,6 +295,43 @@ def test_bench_json_contract(tmp_path):
     assert ru["nn"] == "f16x3" and ru["value"] > 0 and ru["evaluator_rows_per_s"] > 0 and ru["eval_fraction"] <= tree["eval_fraction"] + 0.02
     assert ru["node_expansions_per_s"] >= ru["evaluator_rows_per_s"]
     assert ru["opening_book"]["positions"] == ru["opening_book"]["stored"] == 769880 and ru["opening_book"]["build_s"] > 0
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain bench.py run times the headline leg and nothing else (no roofline pass, extra legs or CPU baseline), and
+    --dump-outputs writes what its last timed step computed: two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--games", "256", "--sims", "40", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        ls = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+        dumps.append({p.stem: np.load(p) for p in sorted(out.glob("*.npy"))})
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f16x3" and d["unit"] == "positions/s" and d["value"] > 0
+    assert abs(d["ms_per_step"] * 2 / 1e3 * d["value"] - 256 * 2) <= 256 * 2 * 0.5      # ~256 positions per step
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not any(k in d for k in ("roofline_tree_kernel", "secondary", "with_evaluation_reuse", "oversubscribed"))
+    a, b = dumps
+    assert set(a) == set(b) and {"pi", "root_visits", "root_value", "boards", "players", "ply", "game_id",
+                                 "examples_states", "examples_policies", "examples_values"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["pi"].shape == (256, 64) and a["boards"].shape == (256, 8, 8)
+    searched = a["root_visits"] > 0
+    assert searched.mean() > 0.5 and (a["root_visits"][searched] == 40).all()
+    assert np.allclose(a["pi"][searched].sum(1), 1.0) and (a["pi"][~searched] == 0).all()
 
 
 @pytest.mark.parametrize("nproc,backend,scaling", [(2, "gloo", "weak"), (2, "gloo", "strong"), (1, "nccl", "weak")],

@@ -355,6 +355,31 @@ def test_bench_multi_rank_control_flow_gloo_world2(tmp_path):
     assert "10 sims" in line["metric"] and "4x4" in line["metric"] and line["vs_baseline"] is None
 
 
+def test_bench_write_outputs_caps_the_size_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32/float64 .npy files only; outputs over the size cap are cut to a seeded sample of their
+    rows (the same rows every time, listed in <name>_rows), outputs under it are written whole."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    monkeypatch.setattr(bench, "DUMP_GAME_BYTES", 16 << 10)
+    rng = np.random.default_rng(0)
+    games = {"pi": rng.random((64, 16)), "boards": rng.random((64, 4, 4)).astype(np.float32)}       # 12 KB: whole
+    ex = {"examples_states": rng.random((4000, 4, 4)).astype(np.float32),
+          "examples_values": rng.random(4000).astype(np.float32)}                                   # 272 KB: sampled
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), games, ex)
+    got = {p.stem: np.load(p) for p in sorted((tmp_path / "a").glob("*.npy"))}
+    assert set(got) == {"pi", "boards", "examples_states", "examples_values", "examples_states_rows"}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 10
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["pi"], games["pi"]) and np.array_equal(got["boards"], games["boards"])
+    rows = got["examples_states_rows"].astype(np.int64)
+    assert 0 < len(rows) == len(got["examples_values"]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["examples_states"], ex["examples_states"][rows])
+    assert np.array_equal(got["examples_values"], ex["examples_values"][rows])
+    for p in (tmp_path / "a").glob("*.npy"):
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name)), p.name
+
+
 def test_publish_examples_file_name_is_unique_and_leaves_no_partial(tmp_path):
     """Two publications within one second get two files (no overwrite); the temporary name does not match the loaders' glob."""
     import glob
