@@ -1465,6 +1465,10 @@ __global__ void __launch_bounds__(64) k_head_finish(const unsigned short *__rest
 // float32 head finish (evaluator modes "f16x3" / float32 towers): logits f32 [Gd, A] and value_fc1 outputs f32 [Gd, H]
 // (bias added, no ReLU yet) of DENSE row i -> policy[g] = softmax(logits[i]), value[g] = tanh(relu(hidden[i]) . w2 + b2)
 // with g = rows ? rows[i] : i; blocks i >= *n_rows exit (the rows a compacted launch did not evaluate).
+// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
+// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
+
 __global__ void __launch_bounds__(64) k_head_finish_f32(const float *__restrict__ logits, const float *__restrict__ hidden,
                                                         int A, int H, const float *__restrict__ w2,
                                                         const float *__restrict__ b2, const int32_t *__restrict__ rows,
@@ -1485,7 +1489,7 @@ __global__ void __launch_bounds__(64) k_head_finish_f32(const float *__restrict_
     for (int a = lane; a < A; a += 64) policy[(size_t)g * A + a] = expf(row[a] - mx) / sum;
     const float *hr = hidden + (size_t)i * H;
     float acc = 0.0f;
-    for (int j = lane; j < H; j += 64) acc += fmaxf(hr[j], 0.0f) * w2[j];
+    for (int j = lane; j < H; j += 64) acc += relu_keep_nan(hr[j]) * w2[j];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if (lane == 0) value[g] = tanhf(acc + b2[0]);

@@ -44,6 +44,10 @@ extern "C" int yy_tower_set_err(int code, const char *msg);
 
 namespace tg {
 
+// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
+// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
+
 template <int NW_, int NB_, int D_> struct Geo {
     static constexpr int NW = NW_, NB = NB_, D = D_, CH = 32 * NW_, NCOL = 16 * NB_;
     static constexpr int RS = (NW_ >= 3) ? 288 : 160;              // row stride: data 2*CH bytes, stride/16 = 2 (mod 8)
@@ -279,7 +283,7 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
                 for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[nb][mb][i] + acc2[nb][mb][i], acc_scale, bq[mb][i]);
                 if (CONV2) v += *(const f32x4 *)(res_lds + (mb * NB + nb) * 1024);
 #pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = fmaxf(v[i], 0.0f);
+                for (int i = 0; i < 4; i++) v[i] = relu_keep_nan(v[i]);
                 if (KEEP) *(f32x4 *)(res_lds + (mb * NB + nb) * 1024) = v;
                 uint32_t h01, l01, h23, l23;
                 split_pair((f32x2){v[0], v[1]}, h01, l01);
@@ -351,7 +355,7 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
                 if (col < ncol && gb < n_live) {
                     float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
 #pragma unroll
-                    for (int i = 0; i < 4; i++) o[i * cells] = fmaxf(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]), 0.0f);
+                    for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
                 }
             }
         }

@@ -47,6 +47,10 @@ extern "C" int yy_tower_set_err(int code, const char *msg);
 
 namespace thr {
 
+// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
+// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
+
 template <int R_, int TB_, int D_, int NV_> struct Geo {
     static constexpr int R = R_, TB = TB_, D = D_, NV = NV_, CELLS = R_ * R_, NCOL = TB_ * R_ * R_, CT = (NCOL + 31) / 32;
     static constexpr int PART_BYTES = (NCOL + 1) * HR_ROW_BYTES;    // one part (hi or lo) of every column + its zero row
@@ -285,7 +289,7 @@ k_tower_h3r(const float *__restrict__ planes, const unsigned char *__restrict__ 
                 for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[tt][4 * q + i] + acc2[tt][4 * q + i], acc_scale, b[i]);
                 if (CONV2) v += GEO::RES_LDS ? rl[GEO::RES_LDS && CONV2 ? tt : 0][q] : res[tt][q];
 #pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = fmaxf(v[i], 0.0f);
+                for (int i = 0; i < 4; i++) v[i] = relu_keep_nan(v[i]);
                 if (KEEP) {
                     if (GEO::RES_LDS) *(f32x4 *)(res_lds + (q * CT + tt) * 1024) = v;
                     else res[tt][q] = v;
@@ -354,7 +358,7 @@ k_tower_h3r(const float *__restrict__ planes, const unsigned char *__restrict__ 
                         float *o = out_heads + (((size_t)gb * 2 + head) * 32 + 8 * q + 4 * h) * CELLS + cell;
 #pragma unroll
                         for (int i = 0; i < 4; i++)
-                            o[i * CELLS] = fmaxf(__builtin_fmaf(h1[t][4 * q + i] + h2[t][4 * q + i], head_scale, b[i]), 0.0f);
+                            o[i * CELLS] = relu_keep_nan(__builtin_fmaf(h1[t][4 * q + i] + h2[t][4 * q + i], head_scale, b[i]));
                     }
                 }
             }

@@ -386,11 +386,17 @@ def reference_precision_mode(net):
 def f16x3_covers(net):
     """True where the split-f16 kernels (csrc/yy_tower_g.hip + yy_fc_heads.hip) cover the network: any board of at most 144 cells,
     32 / 64 / 96 / 128 channels, at most 10 residual blocks, 32-channel head convolutions.
-    Range: activations live times 2^ACT_EXP in float16 pairs, so an activation (or head feature) above 65504 / 2^ACT_EXP = 8188
-    becomes inf, then NaN; the tree kernel turns a NaN prior / value into the game's sticky error flag and the engine raises at
-    the end of that MOVE (SelfPlayEngine.finish_move reads the context's status once per move).  Networks of this architecture
-    (BatchNorm after every convolution) stay orders of magnitude below it: the largest activation over the round's soaks was
-    ~10; a network that does not should be evaluated with mode "fp32"."""
+    Range: activations live times 2^ACT_EXP in float16 pairs.  An activation (or head feature) of 8190 or more (scaled 65520,
+    which rounds to float16 infinity) splits to hi = inf, lo = -inf, and the next layer's sums are NaN.  Every ReLU on this path
+    keeps NaN, so exactly the rows it touches come out NaN: the tree kernel turns a NaN prior / value into the game's sticky error
+    flag and the engine raises YYError at the end of that MOVE (SelfPlayEngine.finish_move reads the context's status once per
+    move; MCTS.search at the end of the search).  Below the limit (8189 is still exact) the result stays float32-grade:
+    measured on 128 x 10 networks with tower activations from ~1e-2 up to ~5 000, the policy is within 2e-6 of float64 and the
+    value within 5e-6 (the float32 module itself: up to 7e-6).  Toward the bottom the float16 lo parts go subnormal: with
+    tower activations around 1e-2 and below, single channels lose bits (2.5e-3 relative per channel at 1e-3 of the usual
+    scale; policy and value stayed within 1e-6).  Networks of this architecture (BatchNorm after every convolution) stay far
+    from the top: the largest activation over the round's soaks was ~10; a network that does not should be evaluated with
+    mode "fp32".  (tests/test_gpu_evaluator_range.py)"""
     R, C = net.board_size
     return (R * C <= G_MAX_CELLS and net.conv1.out_channels in G_CHANNELS and len(net.res_blocks) <= 10
             and net.policy_conv.out_channels == HEAD_CHANNELS and net.value_conv.out_channels == HEAD_CHANNELS)
