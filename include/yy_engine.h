@@ -279,11 +279,14 @@ int yy_nn_tower_f16x3_regs(const float *planes, const void *weights, const void 
  * [4][channels/32][2][512] times 2^head_exp and head_bias float32 [64], network.pack_heads_g) is non-NULL; rows / n_rows as
  * above.  The launch only computes when gate_lo < live rows <= gate_hi (-1, INT_MAX: always), so that two forms can be
  * enqueued and the one fitting the device-side row count runs.  A row's results do not depend on nb, boards or its position
- * in the batch (same accumulation order per output element in every form).  Replaces ai/neural_network.py:94-119. */
+ * in the batch (same accumulation order per output element in every form).  layout 0: where boards * C == 16 and nb == R
+ * (8x8 with two boards per workgroup) the kernel lays a block out as one row of every board and skips the MFMAs of the taps
+ * that only see the zero border; layout 1 forces the plain column layout (same bits; the A/B partner for timing).
+ * Replaces ai/neural_network.py:94-119. */
 int yy_nn_tower_g(const float *planes, const void *weights, const void *head_w, const float *bias, const float *head_bias,
                   float *out, float *out_heads, const int32_t *rows, const int32_t *n_rows, int G, int R, int C,
                   int channels, int n_layers, int weight_exp, int head_exp, int act_exp, int nb, int boards, int gate_lo,
-                  int gate_hi, yy_stream_t stream);
+                  int gate_hi, int layout, yy_stream_t stream);
 /* the nb values yy_nn_tower_g is built for at this channel count: writes up to 8 ints, returns how many (0: unsupported) */
 int yy_nn_tower_g_forms(int channels, int *nb_out);
 

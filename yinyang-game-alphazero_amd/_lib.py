@@ -92,7 +92,7 @@ _SIGS = {
                                C.c_int, _vp],
     "yy_nn_tower_g_forms": [C.c_int, C.POINTER(C.c_int)],
     "yy_nn_tower_g": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_nn_fc_heads_f16x3": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_selfplay_root_noise": [C.c_uint64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp],
     "yy_selfplay_sample_actions": [C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],

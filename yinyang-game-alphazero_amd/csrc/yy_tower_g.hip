@@ -23,6 +23,11 @@
 //   * activation fragments are refreshed IN PLACE, block by block, right after their last use (the next chunk's fragment of
 //     column block nb is read while the MFMAs of block nb + 1 run): 8*NB registers instead of 16*NB.
 //   * bias rows come from scalar loads (no LDS table): NB = 9 with the f32 residual parked in LDS needs 154 of the 160 KB.
+//   * ROW-ALIGNED form (RB, boards * C == 16 and NB == R, e.g. 8x8 with two boards): column nb*16 + n is row nb of board n / C,
+//     x = n % C, so a row shift is a whole block.  Block 0 then reads only the zero rows at the three dy = -1 taps and block
+//     NB - 1 at the three dy = +1 taps: those 6 of the 9 * NB (tap, block) pairs of every channel group are dropped at compile
+//     time, MFMAs and fragment reads both (1/12 of the tower's MFMAs at NB = 8).  A dropped pair only added exact zeros (finite
+//     weights times zero rows, to an accumulator that starts at +0), so every output bit is the one the column form computes.
 // Accumulation order per output element is the same for every (NB, boards-per-workgroup) form: identical bits whichever form
 // evaluates a board (tests/test_gpu_network.py).
 #include <hip/hip_runtime.h>
@@ -48,8 +53,9 @@ namespace tg {
 // -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
 __device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
 
-template <int NW_, int NB_, int D_> struct Geo {
+template <int NW_, int NB_, int D_, bool RB_> struct Geo {
     static constexpr int NW = NW_, NB = NB_, D = D_, CH = 32 * NW_, NCOL = 16 * NB_;
+    static constexpr bool RB = RB_;                                 // row-aligned column blocks (see the head of this file)
     static constexpr int RS = (NW_ >= 3) ? 288 : 160;              // row stride: data 2*CH bytes, stride/16 = 2 (mod 8)
     static constexpr int ZERO_OFF = NCOL * RS;                     // two zero rows' worth (512 B) behind the columns of a part
     static constexpr int PART_BYTES = ZERO_OFF + 512;
@@ -92,17 +98,31 @@ __device__ __forceinline__ void load_w(WChunk &w, const unsigned char *wbase, ui
     w.l[1] = __builtin_bit_cast(f16x8, p[192]);
 }
 
-// per-lane geometry: column nb*16 + n (n = lane & 15), board = column / cells, cell = column % cells; the lane's k group
-// (lane >> 4: input channels [8*kg, 8*kg+8) of a 32-channel chunk) is folded into the row base
+// (board in the workgroup, cell) of column col = nb*16 + n: column form board = col / cells, cell = col % cells; row-aligned
+// form board = n / C, cell = nb * C + n % C.  The LDS row of a column is the column index in both.
+template <class GEO> __device__ __forceinline__ void col_board_cell(int col, int C, int cells, int &board, int &cell) {
+    if constexpr (GEO::RB) {
+        const int n = col & 15;
+        board = n / C;
+        cell = (col >> 4) * C + (n - board * C);
+    } else {
+        board = col / cells;
+        cell = col - board * cells;
+    }
+}
+
+// per-lane geometry of column nb*16 + n (n = lane & 15); the lane's k group (lane >> 4: input channels [8*kg, 8*kg+8) of a
+// 32-channel chunk) is folded into the row base.  Columns of boards >= TB are padding: they read zero rows only.
 template <class GEO> struct LaneGeo {
     uint32_t rowbase[GEO::NB], okmask[GEO::NB];
 };
-template <class GEO> __device__ __forceinline__ void make_lane_geo(LaneGeo<GEO> &g, int lane, int R, int C, int n_valid_cols) {
+template <class GEO> __device__ __forceinline__ void make_lane_geo(LaneGeo<GEO> &g, int lane, int R, int C, int TB) {
     const int n = lane & 15, kg = lane >> 4, cells = R * C;
 #pragma unroll
     for (int nb = 0; nb < GEO::NB; nb++) {
         const int col = nb * 16 + n;
-        const int cell = col % cells;
+        int board, cell;
+        col_board_cell<GEO>(col, C, cells, board, cell);
         const int y = cell / C, x = cell - y * C;
         g.rowbase[nb] = (uint32_t)(col * GEO::RS + kg * 16);
         uint32_t m = 0;
@@ -111,16 +131,21 @@ template <class GEO> __device__ __forceinline__ void make_lane_geo(LaneGeo<GEO> 
             const int sy = y + tap / 3 - 1, sx = x + tap % 3 - 1;
             if (((unsigned)sy < (unsigned)R) && ((unsigned)sx < (unsigned)C)) m |= 1u << tap;
         }
-        g.okmask[nb] = (col < n_valid_cols) ? m : 0u;
+        g.okmask[nb] = (board < TB) ? m : 0u;
     }
 }
 // LDS byte address (hi part, channel-group offset excluded) column block nb reads for TAP: its shifted row, or -- off the
 // board -- the zero rows at (that address mod 256): same bank, no conflict with the lanes that read real rows
 template <class GEO, int TAP>
 __device__ __forceinline__ uint32_t tap_addr(int nb, int crs, const LaneGeo<GEO> &g) {
-    const int shift = (TAP / 3 - 1) * crs + (TAP % 3 - 1) * GEO::RS;   // wave-uniform; crs = C * RS
+    const int shift = (TAP / 3 - 1) * crs + (TAP % 3 - 1) * GEO::RS;   // wave-uniform; crs = C * RS (row-aligned: 16 * RS)
     const uint32_t a = g.rowbase[nb] + (uint32_t)shift;
     return (g.okmask[nb] & (1u << TAP)) ? a : ((a & 255u) | (uint32_t)GEO::ZERO_OFF);
+}
+
+// Row-aligned form: (tap, column block) pairs that read nothing but zero rows -- block 0 at dy = -1, block NB - 1 at dy = +1
+template <class GEO> constexpr bool off_board(int tap, int nb) {
+    return GEO::RB && ((nb == 0 && tap < 3) || (nb == GEO::NB - 1 && tap >= 6));
 }
 
 // Activation fragments of one chunk ({hi, lo} x 4 registers per column block), refreshed IN PLACE: right after the MFMAs of block
@@ -155,13 +180,16 @@ template <class GEO, int J, bool ZERO>
 __device__ __forceinline__ void run_chunk(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc2)[GEO::NB][2], const WChunk &w, XWin<GEO::NB> &X,
                                           const unsigned char *lds_cur, const unsigned char *lds_next, int crs, const LaneGeo<GEO> &geo) {
     constexpr int NB = GEO::NB, P = XWin<NB>::P;
+    static_assert(!GEO::RB || P == NB, "the row-aligned skips assume the full window");
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) {
-        mma6<ZERO>(acc1[nb], acc2[nb], w, X.h[nb % P], X.l[nb % P]);
+        // off-board pairs (row-aligned form): neither the MFMAs nor the fragment read that would feed them
+        const bool mma = !off_board<GEO>(J, nb), ld = nb + P < NB || !off_board<GEO>((J + 1) % 9, nb + P - NB);
+        if (mma) mma6<ZERO>(acc1[nb], acc2[nb], w, X.h[nb % P], X.l[nb % P]);
         if (nb + P < NB) load_x1<GEO>(X, nb % P, lds_cur, tap_addr<GEO, J>(nb + P, crs, geo));
-        else load_x1<GEO>(X, nb % P, lds_next, tap_addr<GEO, (J + 1) % 9>(nb + P - NB, crs, geo));
-        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        else if (ld) load_x1<GEO>(X, nb % P, lds_next, tap_addr<GEO, (J + 1) % 9>(nb + P - NB, crs, geo));
+        if (mma) __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+        if (ld) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
     }
 }
 
@@ -175,7 +203,12 @@ __device__ __forceinline__ void run_layer(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc
     constexpr int KQ = STEM ? 1 : GEO::NW, NB = GEO::NB, D = GEO::D, P = XWin<NB>::P;
     XWin<NB> X;
 #pragma unroll
-    for (int nb = 0; nb < P; nb++) load_x1<GEO>(X, nb, lds, tap_addr<GEO, 0>(nb, crs, geo));
+    for (int nb = 0; nb < P; nb++)
+        if (!off_board<GEO>(0, nb)) load_x1<GEO>(X, nb, lds, tap_addr<GEO, 0>(nb, crs, geo));
+    if constexpr (GEO::RB) {   // block 0 skips the layer's first chunk (tap 0): its sums start from +0, as that chunk's would
+#pragma unroll
+        for (int mb = 0; mb < 2; mb++) acc1[0][mb] = acc2[0][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     auto step = [&](auto jt, auto zt, const unsigned char *lds_cur, const unsigned char *lds_next) {
         constexpr int J = decltype(jt)::value, S = J % D;
         run_chunk<GEO, J, decltype(zt)::value>(acc1, acc2, W[S], X, lds_cur, lds_next, crs, geo);
@@ -203,13 +236,13 @@ __device__ __forceinline__ void run_layer(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc
     for (int kq = 1; kq < KQ; kq++) taps(std::false_type{}, lds + kq * 64, lds + (kq + 1) * 64);
 }
 
-template <int NW_, int NB_, int D_>
+template <int NW_, int NB_, int D_, bool RB_>
 __global__ void __launch_bounds__(64 * NW_, 1)
 k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ weights, const unsigned char *__restrict__ head_w,
           const float *__restrict__ bias, const float *__restrict__ head_bias, float *__restrict__ out, float *__restrict__ out_heads,
           const int *__restrict__ rows, const int *__restrict__ n_rows, int G, int R, int C, int TB, int n_layers, float in_scale,
           float acc_scale, float head_scale, float out_scale, int gate_lo, int gate_hi) {
-    using GEO = Geo<NW_, NB_, D_>;
+    using GEO = Geo<NW_, NB_, D_, RB_>;
     constexpr int NW = GEO::NW, NB = GEO::NB, D = GEO::D, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW_;
     __shared__ __attribute__((aligned(256))) unsigned char lds[GEO::LDS_BYTES];
     const int n_live = n_rows ? min(*n_rows, G) : G;
@@ -218,8 +251,8 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
     if (g0 >= n_live) return;                              // whole workgroup, before any barrier
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cells = R * C, ncol = TB * cells;            // ncol <= 16 * NB (checked on the host)
-    const int n_tower = 9 + 9 * NW * (n_layers - 1), crs = C * RS;
+    const int cells = R * C, ncol = TB * cells;            // ncol <= 16 * NB (checked on the host; row-aligned: == 16 * NB)
+    const int n_tower = 9 + 9 * NW * (n_layers - 1), crs = (GEO::RB ? 16 : C) * RS;
 
     // the weight stream starts first: D chunks in flight before anything else is touched
     const uint32_t voff = (uint32_t)(wave * 4096 + lane * 16);
@@ -230,8 +263,10 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
     for (int t = threadIdx.x; t < 128; t += NT)   // the zero rows of both parts (512 B each)
         ((u32x2 *)(lds + GEO::ZERO_OFF + (t >> 6) * GEO::PART_BYTES))[t & 63] = (u32x2){0u, 0u};
     for (int col = threadIdx.x; col < GEO::NCOL; col += NT) {   // 5 planes -> channels 0..4 of a 32-channel zero-padded input
-        const int gb = g0 + col / cells, cell = col % cells;
-        const bool live = col < ncol && gb < n_live;
+        int b, cell;
+        col_board_cell<GEO>(col, C, cells, b, cell);
+        const int gb = g0 + b;
+        const bool live = b < TB && gb < n_live;
         const int src = live ? (rows ? rows[gb] : gb) : 0;
         float p[6];
 #pragma unroll
@@ -251,7 +286,7 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
     }
 
     LaneGeo<GEO> geo;
-    make_lane_geo<GEO>(geo, lane, R, C, ncol);
+    make_lane_geo<GEO>(geo, lane, R, C, TB);
     const int n16 = lane & 15, kg = lane >> 4;
     unsigned char *res_lds = lds + GEO::RES_OFF + (wave * 2 * NB) * 1024 + lane * 16;   // slot (mb * NB + nb) * 1 KB, lane-private
     int chunk = 0;
@@ -350,9 +385,10 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
                     h2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xl, a, 0, 0, 0);
                 }
                 // features f32 [row][head][channel 32][cell] (the reference's NCHW flatten order)
-                const int col = nb * 16 + n16;
-                const int gb = g0 + col / cells, cell = col % cells;
-                if (col < ncol && gb < n_live) {
+                int bd, cell;
+                col_board_cell<GEO>(nb * 16 + n16, C, cells, bd, cell);
+                const int gb = g0 + bd;
+                if (bd < TB && gb < n_live) {
                     float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
 #pragma unroll
                     for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
@@ -363,11 +399,13 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
     }
     for (int p = threadIdx.x; p < ncol * (CH / 4); p += NT) {   // activations [column][CH] f32 = (hi + lo) * 2^-ka
         const int col = p / (CH / 4), ch4 = p % (CH / 4);
-        if (g0 + col / cells < n_live) {
+        int b, cell;
+        col_board_cell<GEO>(col, C, cells, b, cell);
+        if (b < TB && g0 + b < n_live) {
             const u32x2 ph = *(const u32x2 *)(lds + col * RS + ch4 * 8);
             const u32x2 pl = *(const u32x2 *)(lds + GEO::PART_BYTES + col * RS + ch4 * 8);
             const f32x2 v01 = join_pair(ph.x, pl.x), v23 = join_pair(ph.y, pl.y);
-            *(f32x4 *)(out + ((size_t)g0 * cells + col) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
+            *(f32x4 *)(out + ((size_t)(g0 + b) * cells + cell) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
         }
     }
 }
@@ -388,17 +426,22 @@ struct TgArgs {
     hipStream_t s;
 };
 
-template <int NW, int NB, int D> int launch_tg(const TgArgs &a) {
-    tg::k_tower_g<NW, NB, D><<<dim3((a.G + a.TB - 1) / a.TB), dim3(64 * NW), 0, a.s>>>(
+template <int NW, int NB, int D, bool RB = false> int launch_tg(const TgArgs &a) {
+    tg::k_tower_g<NW, NB, D, RB><<<dim3((a.G + a.TB - 1) / a.TB), dim3(64 * NW), 0, a.s>>>(
         a.planes, (const unsigned char *)a.weights, (const unsigned char *)a.head_w, a.bias, a.head_bias, a.out, a.out_heads, a.rows,
         a.n_rows, a.G, a.R, a.C, a.TB, a.n_layers, a.sc[0], a.sc[1], a.sc[2], a.sc[3], a.gate_lo, a.gate_hi);
     if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_nn_tower_g: launch failed");
     return YY_OK;
 }
 
-// instantiated forms: 128 channels with 4..9 column blocks; narrower networks with 9 (and 4 for small batches)
-int dispatch_tg(int nw, int nb, const TgArgs &a) {
+// instantiated forms: 128 channels with 4..9 column blocks; narrower networks with 9 (and 4 for small batches).  The
+// row-aligned layout is taken whenever the form admits it (boards * C == 16, nb == R) and it is instantiated: 128 channels at
+// nb = 8 (8x8, two boards: the large form of the 8x8 evaluator) and nb = 4 (4x4, four boards).  columns: force the column layout.
+int dispatch_tg(int nw, int nb, bool columns, const TgArgs &a) {
+    const bool rb = !columns && a.TB * a.C == 16 && nb == a.R;
     if (nw == 4) {
+        if (rb && nb == 8) return launch_tg<4, 8, 9, true>(a);
+        if (rb && nb == 4) return launch_tg<4, 4, 9, true>(a);
         switch (nb) {
         case 4: return launch_tg<4, 4, 9>(a);
         case 5: return launch_tg<4, 5, 9>(a);
@@ -436,21 +479,22 @@ extern "C" int yy_nn_tower_g_forms(int channels, int *nb_out) {
 // bias f32 [n_layers, channels] times 2^act_exp; planes f32 [G,5,R,C]; out f32 [G,R,C,channels] or out_heads f32 [G,2,32,R*C].
 // nb = column blocks per workgroup (a form listed by yy_nn_tower_g_forms), boards = boards per workgroup (boards*R*C <= 16*nb).
 // rows / n_rows (device, or both NULL): evaluate planes[rows[i]] for i < *n_rows into dense row i; the launch only runs when
-// gate_lo < live rows <= gate_hi (pass -1, INT_MAX for "always").
+// gate_lo < live rows <= gate_hi (pass -1, INT_MAX for "always").  layout: 0 = the row-aligned column blocks where the form
+// admits them, 1 = always the column layout (same bits; for timing the two against each other).
 extern "C" int yy_nn_tower_g(const float *planes, const void *weights, const void *head_w, const float *bias, const float *head_bias,
                              float *out, float *out_heads, const int32_t *rows, const int32_t *n_rows, int G, int R, int C,
                              int channels, int n_layers, int weight_exp, int head_exp, int act_exp, int nb, int boards, int gate_lo,
-                             int gate_hi, yy_stream_t s) {
+                             int gate_hi, int layout, yy_stream_t s) {
     if (G == 0) return YY_OK;
     if (!planes || !weights || !bias || (!out && !out_heads) || (out_heads && (!head_w || !head_bias)) || G < 0 || (rows && !n_rows))
         return yy_tower_set_err(YY_E_INVALID, "yy_nn_tower_g: bad argument");
     if (R < 1 || C < 1 || R * C > 144 || channels < 32 || channels > 128 || (channels & 31) || n_layers < 1 || n_layers > 21 ||
-        (n_layers & 1) == 0)
+        (n_layers & 1) == 0 || layout < 0 || layout > 1)
         return yy_tower_set_err(YY_E_UNSUPPORTED,
                                 "yy_nn_tower_g: needs boards of at most 144 cells, 32/64/96/128 channels, at most 10 residual blocks");
     if (boards < 1 || nb < 1 || boards * R * C > 16 * nb) return yy_tower_set_err(YY_E_INVALID, "yy_nn_tower_g: boards * cells > 16 * nb");
     TgArgs a = {planes, weights, head_w, bias, head_bias, out, out_heads, rows, n_rows, G, R, C, boards, n_layers,
                 {ldexpf(1.0f, act_exp), ldexpf(1.0f, -weight_exp), ldexpf(1.0f, -(head_exp + act_exp)), ldexpf(1.0f, -act_exp)},
                 gate_lo, gate_hi, (hipStream_t)s};
-    return dispatch_tg(channels / 32, nb, a);
+    return dispatch_tg(channels / 32, nb, layout == 1, a);
 }
