@@ -9,7 +9,9 @@
 // through Philox4x32-10, so game g's transcript is the same whatever slot, batch or rank plays it (SURVEY 8(d) config 2:
 // per-game seeds 1000 + g; 8(e): results independent of W).
 //   purpose 0 = Dirichlet noise: Gamma(alpha) per legal cell (Marsaglia-Tsang, with the U^(1/alpha) boost for alpha < 1),
-//               normalised over the game's legal cells in float64;
+//               normalised over the game's legal cells in float64; a row whose linear total is below 2^-900 (exactly 0
+//               included: alpha ~ 1e-3 underflows U^(1/alpha)) is redone in log space, so no drawing row with a legal cell
+//               comes out all zero (alpha >= 0.06 keeps every boosted cell above 2^-883, so such rows never take that path);
 //   purpose 1 = move choice: ONE uniform u in [0, 1) per (game, ply); temperature 1: first action whose running sum of
 //               pi[a] * mask[a] (ascending a, float64) exceeds u * total (uniform over the legal moves if the total is 0);
 //               temperature 0: the floor(u * n)-th of the n actions tied at max(pi).
@@ -53,13 +55,14 @@ __device__ __forceinline__ U4 draw(uint64_t seed, int64_t game, int ply, int pur
     return philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
-// Gamma(alpha, 1): Marsaglia-Tsang on alpha' = alpha (+1 when alpha < 1), attempt t uses element = cell * 64 + t
-__device__ double gamma_draw(uint64_t seed, int64_t game, int ply, int cell, double alpha) {
+// Gamma(alpha, 1): Marsaglia-Tsang on alpha' = alpha (+1 when alpha < 1), attempt t uses element = cell * 64 + t.
+// Returns g ~ Gamma(alpha'); the cell's value is g * ub^(1/alpha) when alpha < 1 (the boost), else g.
+__device__ double gamma_draw(uint64_t seed, int64_t game, int ply, int cell, double alpha, double &ub) {
     const bool boost = alpha < 1.0;
     const double a = boost ? alpha + 1.0 : alpha;
     const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
     double g = d;     // value if 64 attempts were all rejected (probability < 1e-80)
-    double ub = 0.5;
+    ub = 0.5;
     for (int t = 0; t < 64; t++) {
         const U4 r = draw(seed, game, ply, 0, (uint32_t)(cell * 64 + t));
         const U4 q = draw(seed, game, ply, 2, (uint32_t)(cell * 64 + t));
@@ -75,12 +78,18 @@ __device__ double gamma_draw(uint64_t seed, int64_t game, int ply, int cell, dou
             break;
         }
     }
-    return boost ? g * pow(ub, 1.0 / alpha) : g;
+    return g;
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -91,8 +100,9 @@ __global__ void __launch_bounds__(64) k_root_noise(uint64_t seed, const int64_t 
                                                    const uint8_t *__restrict__ mask, int A, double alpha,
                                                    double *__restrict__ noise) {
     const int g = blockIdx.x, lane = threadIdx.x;
-    const bool on = drawf[g] != 0;
-    double x[3] = {0.0, 0.0, 0.0}, part = 0.0;
+    const bool on = drawf[g] != 0, boost = alpha < 1.0;
+    double x[3] = {0.0, 0.0, 0.0}, gm[3] = {0.0, 0.0, 0.0}, ub[3] = {1.0, 1.0, 1.0}, part = 0.0;
+    bool legal[3] = {false, false, false};
     if (on) {
         const int64_t gid = game_id[g];
         const int p = ply[g];
@@ -100,13 +110,31 @@ __global__ void __launch_bounds__(64) k_root_noise(uint64_t seed, const int64_t 
         for (int j = 0; j < 3; j++) {
             const int a = j * 64 + lane;
             if (a < A && mask[(size_t)g * A + a]) {
-                x[j] = gamma_draw(seed, gid, p, a, alpha);
+                legal[j] = true;
+                gm[j] = gamma_draw(seed, gid, p, a, alpha, ub[j]);
+                x[j] = boost ? gm[j] * pow(ub[j], 1.0 / alpha) : gm[j];
                 part += x[j];
             }
         }
     }
     // one fixed summation order: lanes' partial sums (cells a, a+64, a+128) combined by the xor butterfly
-    const double tot = wave_sum_f64(part);
+    double tot = wave_sum_f64(part);
+    if (on && tot < 0x1.0p-900) {       // wave-uniform: redo the row in log space, relative to the row's largest cell
+        double lx[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            lx[j] = !legal[j] ? -INFINITY : boost ? log(gm[j]) + log(ub[j]) / alpha : log(gm[j]);
+        const double m = wave_max_f64(fmax(fmax(lx[0], lx[1]), lx[2]));
+        part = 0.0;
+        if (m > -INFINITY) {            // at least one legal cell
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                x[j] = legal[j] ? exp(lx[j] - m) : 0.0;
+                part += x[j];
+            }
+        }
+        tot = wave_sum_f64(part);
+    }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         const int a = j * 64 + lane;
@@ -170,7 +198,7 @@ __global__ void __launch_bounds__(64) k_sample_actions(uint64_t seed, const int6
 extern "C" int yy_selfplay_root_noise(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *draw,
                                       const uint8_t *mask, int G, int A, double alpha, double *noise, yy_stream_t s) {
     if (G == 0) return YY_OK;
-    if (!game_id || !ply || !draw || !mask || !noise || G < 0 || A < 1 || A > 192 || !(alpha > 0.0))
+    if (!game_id || !ply || !draw || !mask || !noise || G < 0 || A < 1 || A > 192 || !(alpha > 0.0 && alpha < INFINITY))
         return yy_tower_set_err(YY_E_INVALID, "yy_selfplay_root_noise: bad argument");
     sp::k_root_noise<<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(seed, game_id, ply, draw, mask, A, alpha, noise);
     if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_selfplay_root_noise: launch failed");

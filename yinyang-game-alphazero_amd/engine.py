@@ -328,7 +328,9 @@ def head_finish(h, A, w2, b2):
 
 # ------------------------------------------------------------------ episode-loop random draws (csrc/yy_selfplay.hip)
 def root_noise(seed, game_id, ply, draw, mask, alpha):
-    """Dirichlet(alpha) noise over the legal cells of the games with draw != 0, keyed by (seed, game_id, ply): float64 [G,A]."""
+    """Dirichlet(alpha) noise over the legal cells of the games with draw != 0, keyed by (seed, game_id, ply): float64 [G,A].
+    alpha must be positive and finite.  A row whose linear total falls below 2^-900 (small alpha: about 28 % of the rows at
+    alpha = 1e-3, k = 2; never at alpha >= 0.06) is normalised in log space, so every drawing row with a legal cell sums to 1."""
     G, A = mask.shape
     _need(game_id, torch.int64, (G,), "game_id")
     _need(ply, torch.int32, (G,), "ply")
