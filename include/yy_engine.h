@@ -281,14 +281,19 @@ int yy_nn_tower_f16x3_regs(const float *planes, const void *weights, const void 
  * enqueued and the one fitting the device-side row count runs.  A row's results do not depend on nb, boards or its position
  * in the batch (same accumulation order per output element in every form).  layout 0: where boards * C == 16 and nb == R
  * (8x8 with two boards per workgroup) the kernel lays a block out as one row of every board and skips the MFMAs of the taps
- * that only see the zero border; layout 1 forces the plain column layout (same bits; the A/B partner for timing).
- * Replaces ai/neural_network.py:94-119. */
+ * that only see the zero border; at 128 channels and nb = 8 that form runs on a 2x2 grid of waves (each 64 channels x half
+ * the blocks).  layout 1 forces the plain column layout, layout 2 the row-aligned blocks on the one-wave-per-32-channels grid
+ * (same bits in every layout; the A/B partners for timing).  Replaces ai/neural_network.py:94-119. */
 int yy_nn_tower_g(const float *planes, const void *weights, const void *head_w, const float *bias, const float *head_bias,
                   float *out, float *out_heads, const int32_t *rows, const int32_t *n_rows, int G, int R, int C,
                   int channels, int n_layers, int weight_exp, int head_exp, int act_exp, int nb, int boards, int gate_lo,
                   int gate_hi, int layout, yy_stream_t stream);
 /* the nb values yy_nn_tower_g is built for at this channel count: writes up to 8 ints, returns how many (0: unsupported) */
 int yy_nn_tower_g_forms(int channels, int *nb_out);
+/* Test hook for the ReLU of yy_nn_tower_g's 2x2-grid form: over the float32 bit patterns start .. start + count - 1 (wrapping
+ * at 2^32), counts into counts[0] (device uint32, accumulated) the inputs where it differs from the NaN-keeping ReLU of the other
+ * forms (bits differ for a non-NaN input, or a NaN input does not give a NaN) and lowers counts[1] to the smallest such pattern. */
+int yy_nn_tower_g_relu_check(uint32_t start, uint32_t count, uint32_t *counts, yy_stream_t stream);
 
 /* policy_fc and value_fc1 (neural_network.py:115, :120; float32 on the CPU in the reference) as one split-f16 GEMM kernel of
  * our own (csrc/yy_fc_heads.hip), on the dense feature rows a tower launch wrote: feats float32 [G,2,K] (K = 32*R*C) ->

@@ -91,6 +91,7 @@ _SIGS = {
     "yy_nn_tower_f16x3_regs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, _vp],
     "yy_nn_tower_g_forms": [C.c_int, C.POINTER(C.c_int)],
+    "yy_nn_tower_g_relu_check": [C.c_uint32, C.c_uint32, _vp, _vp],
     "yy_nn_tower_g": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_nn_fc_heads_f16x3": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],

@@ -410,6 +410,352 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 2x2 WAVE GRID form of the row-aligned 8-block tower (k_tower_g22): 128 channels, R = 8, boards * C == 16, 8 column blocks (the
+// large form of the 8x8 evaluator).  k_tower_g<4, 8, 9, true> gives wave w output channels 32w .. 32w+31 x all 8 blocks: every wave
+// reads every B fragment of a chunk and one 2 KB fragment (hi + lo) feeds 6 MFMAs.  Here wave (mh, nh) = (wave >> 1, wave & 1) owns
+// channels 64mh .. 64mh+63 (4 M blocks) x column blocks 4nh .. 4nh+3 (rows 4nh .. 4nh+3 of both boards): a fragment feeds 12 MFMAs,
+// the LDS bytes read per chunk halve (32 KB per CU instead of 64), the MFMAs per wave and chunk stay 48.
+//   * weights: the packing of k_tower_g.  A wave's A operand is the 8 KB of k_tower_g's waves 2mh and 2mh+1 ([M block 4][part 2]
+//     [lane 64][8 f16]); both nh waves load the same bytes (the second request is served by the vector L1).  Ring of D = 3 such
+//     chunks (96 registers) next to 128 accumulators and 32 fragment registers: no AGPR <-> VGPR copies, no spill.
+//   * skips: wave nh = 0 drops block 0 at the three dy = -1 taps, nh = 1 block 7 at the three dy = +1 taps (3 of its 36 (tap,
+//     block) pairs).  nh selects one of two compiled copies of the tower, so the skips stay compile-time.
+//   * layer edges: the tap addresses are computed once per kernel (the peeled channel group reads at them directly, the looped one
+//     adds its channel offset), the bias rows sit in an LDS table (one ds_read_b128 per M block, no per-lane selects), and the
+//     ReLU is one v_maximum3_f32.
+// Every output element keeps its MFMA chain -- [layer][channel group][tap], acc1 / acc2, the same row and column of the same-shaped
+// MFMA with the same operands -- so the bits are k_tower_g's.  The prologue and the head / output tail are k_tower_g's, kept as a
+// copy so that the k_tower_g instantiations compile exactly as before.
+template <int D_> struct Geo22 {
+    static constexpr int NW = 4, NB = 8, NBW = 4, MBW = 4, D = D_, CH = 128, NCOL = 128;
+    static constexpr bool RB = true;
+    static constexpr int RS = 288, ZERO_OFF = NCOL * RS, PART_BYTES = ZERO_OFF + 512;
+    static constexpr int RES_OFF = 2 * PART_BYTES;                       // f32 residual: [wave][M block 4][column block 4] x 1 KB
+    static constexpr int BIAS_OFF = RES_OFF + NW * MBW * NBW * 1024;     // f32 bias rows [layer <= 21][CH]
+    static constexpr int LDS_BYTES = BIAS_OFF + 21 * CH * 4;
+    static constexpr int CHUNK_BYTES = NW * 4096;
+    static_assert(9 % D_ == 0, "ring position = tap % D");
+    static_assert(ZERO_OFF % 256 == 0 && PART_BYTES % 256 == 0 && LDS_BYTES <= 163840, "LDS layout");
+};
+
+// NaN-keeping ReLU in one VALU, v_maximum3_f32 (IEEE 754-2019 maximum: a NaN operand gives a NaN, maximum(-0, +0) = +0): the bits
+// of relu_keep_nan for every input that is not a NaN; a NaN stays a NaN (tests/test_gpu_tower_grid.py runs all 2^32 inputs).
+__device__ __forceinline__ float relu_max(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
+// (tap, local column block) pairs of wave column half NH that read nothing but zero rows
+template <int NH> constexpr bool off22(int tap, int b) { return (NH == 0 && b == 0 && tap < 3) || (NH == 1 && b == 3 && tap >= 6); }
+
+// per-lane LDS byte address (hi part, channel group 0) of every (tap, local block) pair that is not dropped
+struct Taps22 {
+    uint32_t a[9][4];
+};
+template <class GEO, int NH> __device__ __forceinline__ void make_taps22(Taps22 &t, int lane, int R, int C, int TB) {
+    const int n = lane & 15, kg = lane >> 4, cells = R * C;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int col = (4 * NH + b) * 16 + n;
+        int board, cell;
+        col_board_cell<GEO>(col, C, cells, board, cell);
+        const int y = cell / C, x = cell - y * C;
+        const uint32_t base = (uint32_t)(col * GEO::RS + kg * 16);
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++) {
+            if (off22<NH>(tap, b)) continue;
+            const int sy = y + tap / 3 - 1, sx = x + tap % 3 - 1;
+            const uint32_t a = base + (uint32_t)((tap / 3 - 1) * 16 * GEO::RS + (tap % 3 - 1) * GEO::RS);
+            const bool ok = board < TB && (unsigned)sy < (unsigned)R && (unsigned)sx < (unsigned)C;
+            t.a[tap][b] = ok ? a : ((a & 255u) | (uint32_t)GEO::ZERO_OFF);
+        }
+    }
+}
+
+// this wave's A fragments of one weight chunk: [M block 4]{hi, lo}, 32 registers (k_tower_g's waves 2mh and 2mh + 1)
+struct WChunk22 {
+    f16x8 h[4], l[4];
+};
+// wbase: uniform chunk address; voff[2] = this lane's offsets of M blocks 0-1 and 2-3 (two registers, so that every load is
+// "uniform base + lane offset + immediate" with no per-chunk 64-bit address arithmetic)
+__device__ __forceinline__ void load_w22(WChunk22 &w, const unsigned char *wbase, const uint32_t (&voff)[2]) {
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        const u32x4 *p = (const u32x4 *)(wbase + voff[m >> 1]);
+        w.h[m] = __builtin_bit_cast(f16x8, p[128 * (m & 1)]);
+        w.l[m] = __builtin_bit_cast(f16x8, p[128 * (m & 1) + 64]);
+    }
+}
+struct XWin22 {
+    f16x8 h[4], l[4];
+};
+
+// acc1 += w_hi * x_hi ;  acc2 += w_lo * x_hi + w_hi * x_lo for the four M blocks of one column block (12 MFMAs, mma6's order)
+template <bool ZERO>
+__device__ __forceinline__ void mma12(f32x4 (&acc1)[4], f32x4 (&acc2)[4], const WChunk22 &w, const f16x8 xh, const f16x8 xl) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.l[m], xh, ZERO ? z : acc2[m], 0, 0, 0);
+        acc1[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[m], xh, ZERO ? z : acc1[m], 0, 0, 0);
+        acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[m], xl, a, 0, 0, 0);
+    }
+}
+
+// One chunk = tap J of an input-channel group: 48 MFMAs less the dropped pairs.  Right after the MFMAs of block b its fragment
+// slot takes the next chunk's fragment of block b (tap J + 1; the last tap reads the next channel group at koff_next).
+template <int NH, int J, bool ZERO>
+__device__ __forceinline__ void run_chunk22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], const WChunk22 &w, XWin22 &X,
+                                            const unsigned char *lds_cur, const unsigned char *lds_next, const Taps22 &t, int part_bytes) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const bool mma = !off22<NH>(J, b), ld = !off22<NH>((J + 1) % 9, b);
+        if (mma) mma12<ZERO>(acc1[b], acc2[b], w, X.h[b], X.l[b]);
+        if (ld) {
+            const unsigned char *p = (J == 8 ? lds_next : lds_cur) + t.a[(J + 1) % 9][b];
+            X.h[b] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
+            X.l[b] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + part_bytes));
+        }
+        if (mma) __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+        if (ld) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    }
+}
+
+// One layer (stem: one channel group), as run_layer: ring position = tap % D, weight stream order [layer][kq][tap].
+template <class GEO, int NH, bool STEM>
+__device__ __forceinline__ void run_layer22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], WChunk22 (&W)[GEO::D], const unsigned char *lds,
+                                            const unsigned char *weights, const uint32_t (&voff)[2], int &chunk, int n_tower,
+                                            const Taps22 &t) {
+    constexpr int KQ = STEM ? 1 : GEO::NW, D = GEO::D;
+    XWin22 X;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if (off22<NH>(0, b)) {   // this block skips the layer's first chunk (tap 0): its sums start from +0, as that chunk's would
+#pragma unroll
+            for (int m = 0; m < 4; m++) acc1[b][m] = acc2[b][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        } else {
+            X.h[b] = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + t.a[0][b]));
+            X.l[b] = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + t.a[0][b] + GEO::PART_BYTES));
+        }
+    }
+    auto step = [&](auto jt, auto zt, const unsigned char *lds_cur, const unsigned char *lds_next) {
+        constexpr int J = decltype(jt)::value, S = J % D;
+        run_chunk22<NH, J, decltype(zt)::value>(acc1, acc2, W[S], X, lds_cur, lds_next, t, GEO::PART_BYTES);
+        load_w22(W[S], weights + (size_t)min(chunk + D, n_tower - 1) * GEO::CHUNK_BYTES, voff);
+        __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);     // the eight fragment loads stay behind this chunk's MFMAs
+        __builtin_amdgcn_sched_barrier(0);                       // one scheduling region per chunk (see run_layer)
+        chunk++;
+    };
+    auto taps = [&](auto zt, const unsigned char *cur, const unsigned char *nxt) {
+        step(std::integral_constant<int, 0>{}, zt, cur, cur);
+        step(std::integral_constant<int, 1>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 2>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 3>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 4>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 5>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 6>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 7>{}, std::false_type{}, cur, cur);
+        step(std::integral_constant<int, 8>{}, std::false_type{}, cur, nxt);
+    };
+    taps(std::true_type{}, lds, lds + 64);                        // channel group 0, peeled: reads at the tap addresses themselves
+#pragma unroll 1
+    for (int kq = 1; kq < KQ; kq++) {
+        uint32_t cur = kq * 64, nxt = cur + 64;   // uniform channel-group offsets: one v_add per fragment address
+        asm volatile("" : "+s"(cur), "+s"(nxt));
+        taps(std::false_type{}, lds + cur, lds + nxt);
+    }
+}
+
+// Everything of wave column half NH up to the last layer's epilogue: the weight ring and the prologue (as k_tower_g's, plus the
+// bias table), then the stem and the CH -> CH layers, each followed by its epilogue: (acc1 + acc2) * 2^-kw + bias (+ residual),
+// ReLU, split again, back to LDS.  A lane holds output channels 64mh + 16m + 4kg + 0..3 of column (4NH + b)*16 + n16.
+template <class GEO, int NH>
+__device__ __forceinline__ void tower22(unsigned char *lds, const float *__restrict__ planes, const unsigned char *__restrict__ weights,
+                                        const float *__restrict__ bias, const int *__restrict__ rows, int g0, int n_live, int R, int C,
+                                        int TB, int n_layers, int lane, int wave, float in_scale, float acc_scale) {
+    constexpr int NW = GEO::NW, D = GEO::D, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW;
+    const int cells = R * C, n_tower = 9 + 9 * NW * (n_layers - 1);
+    uint32_t voff[2] = {(uint32_t)((wave >> 1) * 8192 + lane * 16), (uint32_t)((wave >> 1) * 8192 + 4096 + lane * 16)};
+    asm volatile("" : "+v"(voff[1]));
+    WChunk22 W[D];
+#pragma unroll
+    for (int j = 0; j < D; j++) load_w22(W[j], weights + (size_t)min(j, n_tower - 1) * GEO::CHUNK_BYTES, voff);
+
+    for (int t = threadIdx.x; t < 128; t += NT)   // the zero rows of both parts (512 B each)
+        ((u32x2 *)(lds + GEO::ZERO_OFF + (t >> 6) * GEO::PART_BYTES))[t & 63] = (u32x2){0u, 0u};
+    for (int i = threadIdx.x; i < n_layers * CH; i += NT) ((float *)(lds + GEO::BIAS_OFF))[i] = bias[i];
+    for (int col = threadIdx.x; col < GEO::NCOL; col += NT) {   // 5 planes -> channels 0..4 of a 32-channel zero-padded input
+        int b, cell;
+        col_board_cell<GEO>(col, C, cells, b, cell);
+        const int gb = g0 + b;
+        const bool live = b < TB && gb < n_live;
+        const int src = live ? (rows ? rows[gb] : gb) : 0;
+        float p[6];
+#pragma unroll
+        for (int k = 0; k < 5; k++) p[k] = live ? planes[((size_t)src * 5 + k) * cells + cell] * in_scale : 0.0f;
+        p[5] = 0.0f;
+        uint32_t hi[3], lo[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) split_pair((f32x2){p[2 * k], p[2 * k + 1]}, hi[k], lo[k]);
+        const u32x4 z = {0u, 0u, 0u, 0u};
+        *(u32x4 *)(lds + col * RS) = (u32x4){hi[0], hi[1], hi[2], 0u};
+        *(u32x4 *)(lds + GEO::PART_BYTES + col * RS) = (u32x4){lo[0], lo[1], lo[2], 0u};
+#pragma unroll
+        for (int q = 1; q < 4; q++) {
+            *(u32x4 *)(lds + col * RS + 16 * q) = z;
+            *(u32x4 *)(lds + GEO::PART_BYTES + col * RS + 16 * q) = z;
+        }
+    }
+
+    const int mh = wave >> 1, n16 = lane & 15, kg = lane >> 4;
+    Taps22 t;
+    make_taps22<GEO, NH>(t, lane, R, C, TB);
+    unsigned char *res_lds = lds + GEO::RES_OFF + wave * 16 * 1024 + lane * 16;      // slot (m * 4 + b) * 1 KB, lane-private
+    int chunk = 0;
+    auto epilogue = [&](const int L, f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], auto conv2_tag, auto keep_tag) {
+        constexpr bool CONV2 = decltype(conv2_tag)::value, KEEP = decltype(keep_tag)::value;
+        const unsigned char *bl = lds + GEO::BIAS_OFF + (L * CH + mh * 64 + kg * 4) * 4;
+        f32x4 bq[4];
+#pragma unroll
+        for (int m = 0; m < 4; m++) bq[m] = *(const f32x4 *)(bl + m * 64);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t rowoff = (uint32_t)(((4 * NH + b) * 16 + n16) * RS);
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                f32x4 v;
+#pragma unroll
+                for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[b][m][i] + acc2[b][m][i], acc_scale, bq[m][i]);
+                if (CONV2) v += *(const f32x4 *)(res_lds + (m * 4 + b) * 1024);
+#pragma unroll
+                for (int i = 0; i < 4; i++) v[i] = relu_max(v[i]);
+                if (KEEP) *(f32x4 *)(res_lds + (m * 4 + b) * 1024) = v;
+                uint32_t h01, l01, h23, l23;
+                split_pair((f32x2){v[0], v[1]}, h01, l01);
+                split_pair((f32x2){v[2], v[3]}, h23, l23);
+                const uint32_t co2 = (uint32_t)((mh * 64 + m * 16 + kg * 4) * 2);
+                *(u32x2 *)(lds + rowoff + co2) = (u32x2){h01, h23};
+                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = (u32x2){l01, l23};
+            }
+        }
+    };
+    {
+        f32x4 acc1[4][4], acc2[4][4];
+        __syncthreads();                                   // the prologue's LDS writes are visible
+        run_layer22<GEO, NH, true>(acc1, acc2, W, lds, weights, voff, chunk, n_tower, t);
+        __syncthreads();                                   // every wave has finished reading the input
+        epilogue(0, acc1, acc2, std::false_type{}, std::true_type{});
+    }
+    for (int L = 1; L < n_layers; L++) {
+        f32x4 acc1[4][4], acc2[4][4];
+        __syncthreads();
+        run_layer22<GEO, NH, false>(acc1, acc2, W, lds, weights, voff, chunk, n_tower, t);
+        __syncthreads();
+        if ((L & 1) == 0) epilogue(L, acc1, acc2, std::true_type{}, std::true_type{});      // second conv of a block: + skip, keep
+        else epilogue(L, acc1, acc2, std::false_type{}, std::false_type{});
+    }
+}
+
+template <int D_>
+__global__ void __launch_bounds__(256, 1)
+k_tower_g22(const float *__restrict__ planes, const unsigned char *__restrict__ weights, const unsigned char *__restrict__ head_w,
+            const float *__restrict__ bias, const float *__restrict__ head_bias, float *__restrict__ out, float *__restrict__ out_heads,
+            const int *__restrict__ rows, const int *__restrict__ n_rows, int G, int R, int C, int TB, int n_layers, float in_scale,
+            float acc_scale, float head_scale, float out_scale, int gate_lo, int gate_hi) {
+    using GEO = Geo22<D_>;
+    constexpr int NW = GEO::NW, NB = GEO::NB, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW;
+    __shared__ __attribute__((aligned(256))) unsigned char lds[GEO::LDS_BYTES];
+    const int n_live = n_rows ? min(*n_rows, G) : G;
+    if (n_live <= gate_lo || n_live > gate_hi) return;
+    const int g0 = blockIdx.x * TB;
+    if (g0 >= n_live) return;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cells = R * C, ncol = TB * cells;            // == 16 * NB (checked on the host)
+
+    // nh selects the compiled copy: everything up to the last layer's epilogue runs inside it, so no value crosses the branch
+    if (wave & 1) tower22<GEO, 1>(lds, planes, weights, bias, rows, g0, n_live, R, C, TB, n_layers, lane, wave, in_scale, acc_scale);
+    else tower22<GEO, 0>(lds, planes, weights, bias, rows, g0, n_live, R, C, TB, n_layers, lane, wave, in_scale, acc_scale);
+    __syncthreads();
+    if (out_heads) {
+        // 1x1 head convs (neural_network.py:113, 118): unit hm = head * 2 + M block (16 of a head's 32 channels), dealt to the
+        // waves round-robin; a wave runs its units over every column block.  head_w: [hm 4][kq NW][part 2][lane 64][8 f16].
+        // (the per-lane geometry is derived again from a laundered lane id: kept alive from the prologue it would sit in
+        // scratch across the whole tower)
+        int lane2 = lane;
+        asm volatile("" : "+v"(lane2) : : "memory");      // and not hoisted above the tower: its head weights would sit in scratch
+        const int n16 = lane2 & 15, kg = lane2 >> 4;
+        for (int hm = wave; hm < 4; hm += NW) {
+            const int head = hm >> 1, mb = hm & 1;
+            f16x8 wh[NW], wl[NW];
+#pragma unroll
+            for (int kq = 0; kq < NW; kq++) {
+                const unsigned char *p = head_w + ((size_t)(hm * NW + kq) * 2) * 1024 + lane2 * 16;
+                wh[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
+                wl[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + 1024));
+            }
+            const float *hb = head_bias + head * 32 + mb * 16;      // uniform: scalar loads
+            float sb[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                sb[k] = hb[k];
+                asm volatile("" : "+s"(sb[k]));
+            }
+            f32x4 b;
+#pragma unroll
+            for (int i = 0; i < 4; i++) b[i] = kg == 0 ? sb[i] : kg == 1 ? sb[4 + i] : kg == 2 ? sb[8 + i] : sb[12 + i];
+#pragma unroll
+            for (int nb = 0; nb < NB; nb++) {
+                const uint32_t xb = (uint32_t)((nb * 16 + n16) * RS + kg * 16);
+                f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kq = 0; kq < NW; kq++) {
+                    const f16x8 xh = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + kq * 64));
+                    const f16x8 xl = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + GEO::PART_BYTES + kq * 64));
+                    const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kq], xh, h2, 0, 0, 0);
+                    h1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xh, h1, 0, 0, 0);
+                    h2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xl, a, 0, 0, 0);
+                }
+                // features f32 [row][head][channel 32][cell] (the reference's NCHW flatten order)
+                int bd, cell;
+                col_board_cell<GEO>(nb * 16 + n16, C, cells, bd, cell);
+                const int gb = g0 + bd;
+                if (bd < TB && gb < n_live) {
+                    float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
+                }
+            }
+        }
+        return;
+    }
+    for (int p = threadIdx.x; p < ncol * (CH / 4); p += NT) {   // activations [column][CH] f32 = (hi + lo) * 2^-ka
+        const int col = p / (CH / 4), ch4 = p % (CH / 4);
+        int b, cell;
+        col_board_cell<GEO>(col, C, cells, b, cell);
+        if (b < TB && g0 + b < n_live) {
+            const u32x2 ph = *(const u32x2 *)(lds + col * RS + ch4 * 8);
+            const u32x2 pl = *(const u32x2 *)(lds + GEO::PART_BYTES + col * RS + ch4 * 8);
+            const f32x2 v01 = join_pair(ph.x, pl.x), v23 = join_pair(ph.y, pl.y);
+            *(f32x4 *)(out + ((size_t)(g0 + b) * cells + cell) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
+        }
+    }
+}
+
+// yy_nn_tower_g_relu_check: relu_max against relu_keep_nan, one bit pattern per thread and step
+__global__ void __launch_bounds__(256) k_relu_check(uint32_t start, uint32_t count, uint32_t *counts) {
+    for (uint64_t i = blockIdx.x * 256u + threadIdx.x; i < count; i += gridDim.x * 256u) {   // 64-bit: no wrap below count
+        const uint32_t x = start + (uint32_t)i;
+        float v = __builtin_bit_cast(float, x);
+        asm volatile("" : "+v"(v));
+        const float a = relu_keep_nan(v), b = relu_max(v);
+        const bool ok = __builtin_isnan(v) ? __builtin_isnan(b) : __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b);
+        if (!ok) {
+            atomicAdd(&counts[0], 1u);
+            atomicMin(&counts[1], x);
+        }
+    }
+}
+
 }   // namespace tg
 
 namespace {
@@ -426,6 +772,14 @@ struct TgArgs {
     hipStream_t s;
 };
 
+template <int D> int launch_tg22(const TgArgs &a) {
+    tg::k_tower_g22<D><<<dim3((a.G + a.TB - 1) / a.TB), dim3(256), 0, a.s>>>(
+        a.planes, (const unsigned char *)a.weights, (const unsigned char *)a.head_w, a.bias, a.head_bias, a.out, a.out_heads, a.rows,
+        a.n_rows, a.G, a.R, a.C, a.TB, a.n_layers, a.sc[0], a.sc[1], a.sc[2], a.sc[3], a.gate_lo, a.gate_hi);
+    if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_nn_tower_g: launch failed");
+    return YY_OK;
+}
+
 template <int NW, int NB, int D, bool RB = false> int launch_tg(const TgArgs &a) {
     tg::k_tower_g<NW, NB, D, RB><<<dim3((a.G + a.TB - 1) / a.TB), dim3(64 * NW), 0, a.s>>>(
         a.planes, (const unsigned char *)a.weights, (const unsigned char *)a.head_w, a.bias, a.head_bias, a.out, a.out_heads, a.rows,
@@ -436,11 +790,12 @@ template <int NW, int NB, int D, bool RB = false> int launch_tg(const TgArgs &a)
 
 // instantiated forms: 128 channels with 4..9 column blocks; narrower networks with 9 (and 4 for small batches).  The
 // row-aligned layout is taken whenever the form admits it (boards * C == 16, nb == R) and it is instantiated: 128 channels at
-// nb = 8 (8x8, two boards: the large form of the 8x8 evaluator) and nb = 4 (4x4, four boards).  columns: force the column layout.
-int dispatch_tg(int nw, int nb, bool columns, const TgArgs &a) {
-    const bool rb = !columns && a.TB * a.C == 16 && nb == a.R;
+// nb = 8 (8x8, two boards: the large form of the 8x8 evaluator; the 2x2 wave grid k_tower_g22) and nb = 4 (4x4, four boards).
+// layout 1: force the column layout; layout 2: the row-aligned nb = 8 form on k_tower_g's one-wave-per-channel-slice grid.
+int dispatch_tg(int nw, int nb, int layout, const TgArgs &a) {
+    const bool rb = layout != 1 && a.TB * a.C == 16 && nb == a.R;
     if (nw == 4) {
-        if (rb && nb == 8) return launch_tg<4, 8, 9, true>(a);
+        if (rb && nb == 8) return layout == 2 ? launch_tg<4, 8, 9, true>(a) : launch_tg22<3>(a);
         if (rb && nb == 4) return launch_tg<4, 4, 9, true>(a);
         switch (nb) {
         case 4: return launch_tg<4, 4, 9>(a);
@@ -480,7 +835,8 @@ extern "C" int yy_nn_tower_g_forms(int channels, int *nb_out) {
 // nb = column blocks per workgroup (a form listed by yy_nn_tower_g_forms), boards = boards per workgroup (boards*R*C <= 16*nb).
 // rows / n_rows (device, or both NULL): evaluate planes[rows[i]] for i < *n_rows into dense row i; the launch only runs when
 // gate_lo < live rows <= gate_hi (pass -1, INT_MAX for "always").  layout: 0 = the row-aligned column blocks where the form
-// admits them, 1 = always the column layout (same bits; for timing the two against each other).
+// admits them (8x8 two-board form: the 2x2 wave grid), 1 = always the column layout, 2 = the row-aligned blocks with one wave per
+// 32-channel slice (k_tower_g<4, 8, 9, true>) where the 2x2 grid would run.  Same bits in every layout; 1 and 2 are for timing.
 extern "C" int yy_nn_tower_g(const float *planes, const void *weights, const void *head_w, const float *bias, const float *head_bias,
                              float *out, float *out_heads, const int32_t *rows, const int32_t *n_rows, int G, int R, int C,
                              int channels, int n_layers, int weight_exp, int head_exp, int act_exp, int nb, int boards, int gate_lo,
@@ -489,12 +845,20 @@ extern "C" int yy_nn_tower_g(const float *planes, const void *weights, const voi
     if (!planes || !weights || !bias || (!out && !out_heads) || (out_heads && (!head_w || !head_bias)) || G < 0 || (rows && !n_rows))
         return yy_tower_set_err(YY_E_INVALID, "yy_nn_tower_g: bad argument");
     if (R < 1 || C < 1 || R * C > 144 || channels < 32 || channels > 128 || (channels & 31) || n_layers < 1 || n_layers > 21 ||
-        (n_layers & 1) == 0 || layout < 0 || layout > 1)
+        (n_layers & 1) == 0 || layout < 0 || layout > 2)
         return yy_tower_set_err(YY_E_UNSUPPORTED,
                                 "yy_nn_tower_g: needs boards of at most 144 cells, 32/64/96/128 channels, at most 10 residual blocks");
     if (boards < 1 || nb < 1 || boards * R * C > 16 * nb) return yy_tower_set_err(YY_E_INVALID, "yy_nn_tower_g: boards * cells > 16 * nb");
     TgArgs a = {planes, weights, head_w, bias, head_bias, out, out_heads, rows, n_rows, G, R, C, boards, n_layers,
                 {ldexpf(1.0f, act_exp), ldexpf(1.0f, -weight_exp), ldexpf(1.0f, -(head_exp + act_exp)), ldexpf(1.0f, -act_exp)},
                 gate_lo, gate_hi, (hipStream_t)s};
-    return dispatch_tg(channels / 32, nb, layout == 1, a);
+    return dispatch_tg(channels / 32, nb, layout, a);
+}
+
+extern "C" int yy_nn_tower_g_relu_check(uint32_t start, uint32_t count, uint32_t *counts, yy_stream_t s) {
+    if (!counts) return yy_tower_set_err(YY_E_INVALID, "yy_nn_tower_g_relu_check: bad argument");
+    if (count == 0) return YY_OK;
+    tg::k_relu_check<<<dim3(4096), dim3(256), 0, (hipStream_t)s>>>(start, count, counts);
+    if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_nn_tower_g_relu_check: launch failed");
+    return YY_OK;
 }

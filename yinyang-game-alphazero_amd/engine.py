@@ -205,14 +205,15 @@ def tower_g_available(channels):
 
 
 def tower_g(planes, weights, bias, n_layers, exps, nb, boards, head_w=None, head_bias=None, rows=None, n_rows=None, out=None,
-            gate=(-1, 0x7FFFFFFF), column_layout=False):
+            gate=(-1, 0x7FFFFFFF), column_layout=False, wave_grid=True):
     """General split-f16 tower (csrc/yy_tower_g.hip): planes f32 [G,5,R,C] (R*C <= 144) with the weights of network.pack_tower_g.
     With head_w / head_bias (pack_heads_g): -> f32 [G,2,32*R*C] = (policy features, value features) in the reference's flatten
     order; without: -> the tower activations f32 [G,CH,R,C] (channels-last memory).  nb column blocks of 16 and `boards` boards
     per workgroup (network.tower_g_forms).  rows int32 [G] / n_rows int32 [1] (device): evaluate planes[rows[i]] for i < n_rows
     into dense row i; gate = (lo, hi): the launch only runs when lo < live rows <= hi.  column_layout=True: never the row-aligned
     column blocks the kernel picks by itself where the form admits them (8x8 with two boards per workgroup; same bits), for A/B
-    timing."""
+    timing.  wave_grid=False: the row-aligned 8-block form at 128 channels on k_tower_g's one-wave-per-32-channels grid instead
+    of the 2x2 wave grid (k_tower_g22; same bits), for A/B timing."""
     G, _, R, Cc = planes.shape
     _need(planes, torch.float32, (G, 5, R, Cc), "planes")
     ch = bias.shape[1]
@@ -234,9 +235,20 @@ def tower_g(planes, weights, bias, n_layers, exps, nb, boards, head_w=None, head
     with torch.cuda.device(planes.device):
         check(lib().yy_nn_tower_g(_p(planes), _p(weights), _p(head_w), _p(bias), _p(head_bias), None if heads else _p(out),
                                   _p(out) if heads else None, _p(rows), _p(n_rows), G, R, Cc, ch, n_layers, int(exps[0]), int(exps[1]),
-                                  int(exps[2]), int(nb), int(boards), int(gate[0]), int(gate[1]), int(bool(column_layout)),
+                                  int(exps[2]), int(nb), int(boards), int(gate[0]), int(gate[1]),
+                                  1 if column_layout else 0 if wave_grid else 2,
                                   _stream()))
     return out if heads else out.permute(0, 3, 1, 2)
+
+
+def tower_g_relu_check(start, count, counts):
+    """Test hook (csrc/yy_tower_g.hip): over the float32 bit patterns start .. start + count - 1, add to counts[0] (uint32 as
+    int32 [2] on the device) the inputs where the 2x2-grid tower's ReLU differs from relu_keep_nan, and lower counts[1] (read as
+    uint32) to the smallest such pattern."""
+    _need(counts, torch.int32, (2,), "counts")
+    with torch.cuda.device(counts.device):
+        check(lib().yy_nn_tower_g_relu_check(int(start) & 0xFFFFFFFF, int(count), _p(counts), _stream()))
+    return counts
 
 
 def fc_heads(feats, wpk, bias, jobs, A, H, exps, n_rows=None, logits=None, hidden=None):
