@@ -129,15 +129,37 @@ typedef struct yy_mcts_config {
     uint32_t flags;            /* YY_FLAG_* */
     int64_t edges_per_game;    /* 0 = worst case (max_sims+2)*A */
     int64_t nodes_per_game;    /* 0 = max_sims+2 */
+    int32_t leaves_per_step;   /* K: descents per game per step (leaf parallelism with virtual visits); 0 and 1 = one,
+                                  the reference's search.  1 < K <= 64 needs copied boards and no YY_FLAG_REUSE_* /
+                                  YY_FLAG_KEEP_EVALUATIONS (create returns YY_E_UNSUPPORTED) and no book.  See below. */
 } yy_mcts_config;
+
+/* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after
+ * another, K_eff = min(K, simulations of this search not yet started) -- computed on the device from root.visits and the count
+ * set by yy_mcts_set_num_sims, so that one captured step serves every step of a search.  The tree and its statistics do not
+ * change during these descents.  Descent j sees on every edge a virtual count v = the number of descents 0 .. j-1 of this step
+ * that walked that edge, and scores a child with n = N + v, w = v > 0 ? f32(W - f32(v)) : W, in the float32 order of
+ * mcts.py:97-145: S = sum over the children of (N + v), sq = f32(sqrt(S)), u = f32(f32(f32(cpuct*P)*sq) / f32(1+n)),
+ * q = n > 0 ? f32(w / f32(n)) : 0, the largest q + u wins, the lowest action on ties.  With v = 0 this is the K = 1 formula.
+ * A descent that ends on the leaf of an earlier descent of the same step (the same unexpanded edge, the same childless node,
+ * the pass root) asks for no row: it shares that descent's evaluation and still counts as a simulation.  A terminal leaf asks
+ * for no row either.  Rows are game-major: select / step write planes [G*K,5,R,C] and needs_eval [G*K], row g*K + j for descent
+ * j of game g, needs_eval = 1 only for the first occurrence of a leaf that needs an evaluation (counters[0] counts those rows);
+ * expand_backup / step read policy [G*K,A] and value [G*K].  After the evaluator, for j = 0 .. K_eff-1 in order: the first
+ * occurrence of a leaf expands it as with K = 1, then every descent backs its value up along its own path as with K = 1.  So
+ * every step adds K_eff visits to the root, and root.visits == num_sims after ceil(num_sims / K) steps.  yy_mcts_begin writes
+ * the root planes to row g*K and yy_mcts_expand_root reads policy row g*K (the noise stays [G,A]). */
 
 typedef struct yy_mcts yy_mcts; /* opaque */
 
 /* sync. Allocates the arenas in HBM on the current device. */
 int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out);
 int yy_mcts_destroy(yy_mcts *ctx);
-/* bytes of HBM held by the context (host out) */
+/* bytes of HBM held by the context (host out); with K > 1 it includes the per-descent paths and leaf records */
 int yy_mcts_memory_bytes(const yy_mcts *ctx, uint64_t *out);
+/* Simulations of the searches begun after this call (0 = max_sims, the default); host only, read by yy_mcts_begin.  Used
+ * by leaf-parallel contexts (K > 1) to run the last step of a search with fewer descents; K = 1 ignores it. */
+int yy_mcts_set_num_sims(yy_mcts *ctx, int32_t num_sims);
 
 /* MCTS.search prologue (mcts.py:288-295): fresh root per game from boards int8 [G,R,C] and
  * root_players int8 [G]; active uint8 [G] (NULL = all active; inactive games are skipped by every

@@ -67,6 +67,10 @@ def parse_args(argv=None):
     p.add_argument("--arena-games", type=int, default=40)
     p.add_argument("--channels", type=int, default=128)
     p.add_argument("--blocks", type=int, default=10)
+    p.add_argument("--leaves-per-step", type=int, default=1,
+                   help="--mode evaluate: K descents per game per search step with virtual visits, evaluated in one batch (a "
+                        "search then takes ceil(simulations / K) evaluator calls; 1 = the reference's search; changes which "
+                        "moves are picked).  --mcts-threads stays inert")
     return p.parse_args(argv)
 
 
@@ -117,7 +121,8 @@ def main(argv=None):
         if not os.path.exists(model_path):
             sys.exit(f"Model file not found: {model_path}")
         res = pkg.evaluate_vs_random(game, model_path, num_games=10, num_simulations=args.simulations, nn_mode=args.nn,
-                                     num_channels=args.channels, num_res_blocks=args.blocks)
+                                     num_channels=args.channels, num_res_blocks=args.blocks,
+                                     leaves_per_step=args.leaves_per_step)
         print(json.dumps(res))
         return
     if not os.path.exists(model_path):           # same contract as the reference (train_alphazero.py:107-109)

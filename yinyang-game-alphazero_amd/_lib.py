@@ -30,7 +30,7 @@ class YYError(RuntimeError):
 class MctsConfig(C.Structure):
     _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_sims", C.c_int32),
                 ("cpuct", C.c_float), ("flags", C.c_uint32), ("edges_per_game", C.c_int64),
-                ("nodes_per_game", C.c_int64)]
+                ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32)]
 
 
 def build(force=False, verbose=False):
@@ -67,6 +67,7 @@ _SIGS = {
     "yy_mcts_create": [C.POINTER(MctsConfig), C.POINTER(_vp)],
     "yy_mcts_destroy": [_vp],
     "yy_mcts_memory_bytes": [_vp, C.POINTER(C.c_uint64)],
+    "yy_mcts_set_num_sims": [_vp, C.c_int32],
     "yy_mcts_begin": [_vp, _vp, _vp, _vp, _vp, _vp],
     "yy_mcts_expand_root": [_vp, _vp, _vp, C.c_double, _vp],
     "yy_mcts_select": [_vp, _vp, _vp, _vp],

@@ -33,19 +33,24 @@ class DualEvaluator:
     launch-bound, not compute-bound).  Routed (large matches): each network sees only its own rows (index_select /
     index_copy), eager launches."""
 
-    def __init__(self, ev_a, ev_b, G, A, device, dense=False):
+    def __init__(self, ev_a, ev_b, G, A, device, dense=False, leaves_per_step=1):
+        """leaves_per_step K: the leaf batch has K rows per game, row g*K + j belongs to game g."""
         self.ev_a, self.ev_b, self.dense = ev_a, ev_b, dense
+        self.K = max(1, int(leaves_per_step))
         self.idx_a = self.idx_b = None
         self.side = None
-        self.sel = torch.ones(G, dtype=torch.bool, device=device)
-        self.policy = torch.zeros((G, A), dtype=torch.float32, device=device)
-        self.value = torch.zeros(G, dtype=torch.float32, device=device)
+        self.sel = torch.ones(G * self.K, dtype=torch.bool, device=device)
+        self.policy = torch.zeros((G * self.K, A), dtype=torch.float32, device=device)
+        self.value = torch.zeros(G * self.K, dtype=torch.float32, device=device)
         # dense mode with two compacting evaluators: the step's needs_eval flags go to both, so a step in which no game needs an
         # evaluation (terminal revisits, reused evaluations) launches two towers that exit at once
         self.supports_compaction = dense and all(getattr(e, "supports_compaction", False) for e in (ev_a, ev_b))
         self.row_independent = all(getattr(e, "row_independent", False) for e in (ev_a, ev_b))
 
     def assign(self, a_rows):
+        """a_rows bool [G]: the games that A searches for."""
+        if self.K > 1:
+            a_rows = a_rows.repeat_interleave(self.K)
         self.sel.copy_(a_rows)
         if not self.dense:
             self.idx_a = a_rows.nonzero(as_tuple=True)[0]
@@ -98,7 +103,7 @@ class Arena:
     between two fixed networks is deterministic, as the reference's is."""
 
     def __init__(self, game, player_a, player_b, num_simulations=800, cpuct=1.0, device=None, seed=0,
-                 reference_scoring=False, literal=False, evaluation_reuse=True):
+                 reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1):
         """evaluation_reuse: inside one search a position is evaluated once (pass values, other move orders) when both players
         are row-independent compacting evaluators (the float32-accurate BatchedEvaluator); the moves are the same.
         reference_scoring=True reproduces the reference's attribution literally (alphazero.py:206-218): the value of
@@ -106,8 +111,13 @@ class Arena:
         literal=True reproduces the whole reference match loop (alphazero.py:171-220): the search runs on the game's own
         board object and mutates it (aliased boards), there is no pass handling -- a side without a move still
         searches, np.argmax of the uniform pi gives action 0, the illegal placement is ignored and the player flips (Q3) --
-        and the scoring is the reference's."""
+        and the scoring is the reference's.
+        leaves_per_step K > 1: leaf-parallel searches (MCTS leaves_per_step); copied boards only, so not with literal=True, and
+        without evaluation reuse."""
         self.game = game
+        self.K = max(1, int(leaves_per_step))
+        if self.K > 1 and literal:
+            raise ValueError("leaves_per_step > 1 needs copied boards: literal=True searches the aliased board")
         self.literal = bool(literal)
         self.evaluation_reuse = bool(evaluation_reuse)
         self.reference_scoring = bool(reference_scoring) or self.literal
@@ -132,12 +142,14 @@ class Arena:
         ev_a = _uniform_evaluator(self.A) if self.pa == "random" else self.pa
         ev_b = _uniform_evaluator(self.A) if self.pb == "random" else self.pb
         dense = G <= 1024
-        dual = DualEvaluator(ev_a, ev_b, G, self.A, dev, dense=dense)
+        dual = DualEvaluator(ev_a, ev_b, G, self.A, dev, dense=dense, leaves_per_step=self.K)
         # a search uses ONE network per game (assigned per move), so inside a search a position's evaluation can be reused
         # (pass values, other move orders); never across searches: the two networks alternate
-        reuse = self.evaluation_reuse and (not self.literal) and dense and dual.supports_compaction and dual.row_independent
+        reuse = (self.evaluation_reuse and (not self.literal) and dense and dual.supports_compaction and dual.row_independent
+                 and self.K == 1)
         ctx = engine.BatchedMCTS(G, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
-                                 aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse)
+                                 aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse,
+                                 leaves_per_step=self.K)
         try:
             search = LockstepSearch(ctx, dual, use_graph=dense)     # routed mode: the row sets change every move
             result = torch.zeros(G, dtype=torch.int8, device=dev)   # +1 black won, -1 white won, 2 draw
@@ -230,7 +242,7 @@ class RandomPlayer:
 class AlphaZeroPlayer:
     """alphazero.py:272-365: network + MCTS behind `play(board, player) -> action` (-1 = no move)."""
 
-    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None):
+    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1):
         self.game = game
         net = YinYangNeuralNetwork(game)
         if os.path.exists(model_path):
@@ -238,7 +250,7 @@ class AlphaZeroPlayer:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.neural_net = net.to(dev).eval()
         self.mcts = MCTS(game, self.neural_net, num_simulations=num_simulations, num_threads=num_threads,
-                         board_semantics="copied", device=dev)
+                         board_semantics="copied", device=dev, leaves_per_step=leaves_per_step)
         self.root = None
 
     def reset(self):
@@ -371,10 +383,11 @@ class AlphaZero:
 
 
 def evaluate_vs_random(game, model_path, num_games=10, num_simulations=800, nn_mode="auto", device=None,
-                       num_channels=128, num_res_blocks=10):
-    """`--mode evaluate` (train_alphazero.py:124-243): the model against RandomPlayer, alternating colours."""
+                       num_channels=128, num_res_blocks=10, leaves_per_step=1):
+    """`--mode evaluate` (train_alphazero.py:124-243): the model against RandomPlayer, alternating colours.  leaves_per_step:
+    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     ev = _load_evaluator(game, model_path, dev, nn_mode, num_channels, num_res_blocks)
-    res = Arena(game, ev, "random", num_simulations, device=dev).play(num_games)
+    res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step).play(num_games)
     return dict(alphazero_wins=res["a_wins"], random_wins=res["b_wins"], draws=res["draws"],
                 win_rate=res["a_wins"] / num_games)

@@ -17,8 +17,9 @@
 //   nodes  uint4 [G][node_cap]   {first_edge, k | flags<<16 | player<<24, terminal value f32, -}
 //   nboard u64   [G][node_cap][2*NW]   (copied mode only) black words then white words
 //   gboard u64   [G][2*NW]       root board (copied) / THE shared board (aliased)
-//   path   i32   [G][path_cap]   edge indices chosen by the last selection
+//   path   i32   [G][K][path_cap]   edge indices chosen by the last selection (K = leaves per step, 1 by default)
 //   state  GameState [G]         counters, root statistics, the pending leaf record
+//   leaves LeafRec [G][K]        (K > 1 only) the pending leaf record of every descent of the step
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -27,7 +28,7 @@
 #include "../../include/yy_engine.h"
 #include "yy_bitboard.h"
 
-#define YY_VERSION 100
+#define YY_VERSION 101
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -486,6 +487,24 @@ struct GameState {
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
 };
 
+// Leaf-parallel steps (leaves_per_step K > 1): the pending leaf of descent j of game g is leaves[g*K + j]
+struct LeafRec {
+    int32_t path_len, node;  // edges on the path; the leaf's node record (-1: unexpanded edge)
+    int32_t dup;             // >= 0: an earlier descent of this step that ended on the same leaf (its row is shared), else -1
+    float tv;                // terminal value of a freshly evaluated leaf
+    uint8_t kind, terminal;
+    int8_t player;
+    uint8_t pad[5];
+    uint64_t board[2 * YY_MAX_NW];
+    uint64_t mask[YY_MAX_NW];
+};
+
+struct MultiDev {  // by-value kernel argument of the K > 1 kernels
+    int32_t K;
+    LeafRec *leaves;         // [G*K]
+    int32_t *mst;            // [G][2] = {simulations of the current search, descents of the pending step}
+};
+
 struct yy_mcts {
     yy_mcts_config cfg;
     YYGeo geo;
@@ -507,6 +526,11 @@ struct yy_mcts {
     int bk_stones;
     GameState *state;
     float *sqrt_tab;
+    int32_t sqrt_len;       // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
+    int32_t K;              // leaves per step (1: one descent per game per step)
+    int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
+    LeafRec *leaves;
+    int32_t *mst;
     uint64_t *scratch;      // [8] counters + overflow count
     uint64_t bytes;
     int pending;            // 1 = a select is pending an expand_backup
@@ -567,8 +591,16 @@ static MctsDev make_dev(const yy_mcts *c) {
     d.bk_stones = c->bk_stones;
     d.state = c->state;
     d.sqrt_tab = c->sqrt_tab;
-    d.sqrt_n = c->cfg.max_sims + 2;
+    d.sqrt_n = c->sqrt_len;
     return d;
+}
+
+static MultiDev make_multi(const yy_mcts *c) {
+    MultiDev m;
+    m.K = c->K;
+    m.leaves = c->leaves;
+    m.mst = c->mst;
+    return m;
 }
 
 __device__ __forceinline__ uint32_t node_pack(int k, uint32_t flags, int player) {
@@ -591,10 +623,11 @@ __device__ __forceinline__ void leaf_rules(const YYGeo &geo, const GeoBB<NW> &gb
 }
 
 // ---- root prologue: mcts.py:288-295
-template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, const int8_t *boards,
+template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, const int8_t *boards,
                                                                 const int8_t *players, const uint8_t *active,
                                                                 float *planes) {
     const int g = blockIdx.x;
+    const int K = m.K;          // K > 1: the root row is row g*K, the pending root expansion is leaf record g*K
     GameState *st = d.state + g;
     const bool act = active ? (active[g] != 0) : true;
     BB<NW> black, white;
@@ -643,7 +676,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, const
         bool term;
         float tv;
         leaf_rules<NW>(d.geo, gb, black, white, rp, mask, term, tv);
-        if (lane_id() == 0) {
+        if (lane_id() == 0 && K == 1) {
 #pragma unroll
             for (int i = 0; i < NW; i++) {
                 st->leaf_board[i] = black.w[i];
@@ -654,7 +687,27 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, const
             st->leaf_terminal = term;
             st->leaf_tv = tv;
         }
-        write_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, black, white);
+        if (lane_id() == 0 && K > 1) {
+            LeafRec *rec = m.leaves + (size_t)g * K;
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                rec->board[i] = black.w[i];
+                rec->board[NW + i] = white.w[i];
+                rec->mask[i] = mask.w[i];
+            }
+            rec->player = (int8_t)rp;
+            rec->terminal = term;
+            rec->tv = tv;
+            rec->kind = K_ROOTINIT;
+            rec->node = 0;
+            rec->path_len = 0;
+            rec->dup = -1;
+        }
+        write_planes<NW>(planes + (size_t)g * K * 5 * d.geo.A, d.geo, black, white);
+    }
+    if (K > 1 && lane_id() == 0) {
+        m.mst[2 * g] = target;
+        m.mst[2 * g + 1] = act ? 1 : 0;
     }
 }
 
@@ -1028,6 +1081,305 @@ template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do
     if (do_sel) do_select<NW>(d, g, planes, needs_eval);
 }
 
+// =============================================================================== leaf-parallel steps (K > 1)
+// Every step runs K_eff = min(K, simulations of the search not yet started) descents per game, one after another, on the tree
+// as it stands at the start of the step.  Descent j sees on every edge a virtual count v = the number of descents 0 .. j-1 of
+// this step that walked it, and scores a child with n = N + v and w = v > 0 ? f32(W - f32(v)) : W, S = sum of the children's
+// n (include/yy_engine.h).  Only the paths are stored: the descents that reached the current node by the same path
+// are a bit mask `match` over the lanes, and lane i < j reads the edge descent i took out of it.  A descent ending on the leaf
+// of an earlier one (same unexpanded edge, same childless node, the pass root) takes no row and shares that evaluation.
+template <int NW>
+__device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev &m, const int g, float *planes,
+                                                uint8_t *needs_eval) {
+    GameState *st = d.state + g;
+    const int lane = lane_id();
+    const int K = m.K;
+    int32_t *ms = m.mst + 2 * g;
+    int keff = 0;
+    if (rfl((int)st->active) && !rfl((int)st->err)) keff = min(K, max(0, rfl(ms[0]) - rfl(st->root_N)));
+    const GeoBB<NW> gb = geo_bb<NW>(d.geo);
+    const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    uint64_t c_levels = 0, c_scan = 0, c_evals = 0, c_term = 0;
+    bool failed = false;
+    for (int j = 0; j < keff; j++) {
+        int32_t *path = d.path + ((size_t)g * K + j) * d.path_cap;
+        int node = 0, depth = 0, parent = -1, action = -1, kind;
+        uint64_t match = (1ull << j) - 1ull;                       // earlier descents on the same path (j < 64)
+        for (;;) {
+            const uint4 hdr = nodes[node];
+            const uint32_t hy = rfl(hdr.y);
+            const int k = node_k(hy), first = rfl((int)hdr.x);
+            if (node_flags(hy) & NF_TERMINAL) { kind = K_TERMINAL; break; }
+            if (k == 0) { kind = (node == 0) ? K_ROOTPASS : K_REEXPAND; break; }
+            if (depth >= (int)d.path_cap) { kind = K_NONE; break; }
+            // every descent in `match` reached this node, which has children: each went on through one of them
+            const int vi = ((match >> lane) & 1) ? d.path[((size_t)g * K + lane) * d.path_cap + depth] - first : -1;
+            int v[NW];
+#pragma unroll
+            for (int t = 0; t < NW; t++) v[t] = 0;
+            for (uint64_t mm = match; mm; mm &= mm - 1ull) {
+                const int c = __builtin_amdgcn_readlane(vi, (int)__ffsll((unsigned long long)mm) - 1);
+#pragma unroll
+                for (int t = 0; t < NW; t++) v[t] += (c == t * 64 + lane) ? 1 : 0;
+            }
+            uint4 e[NW];
+            uint32_t part = 0;
+#pragma unroll
+            for (int t = 0; t < NW; t++) {
+                const int jj = t * 64 + lane;
+                e[t] = (jj < k) ? edges[first + jj] : make_uint4(0u, 0u, 0u, 0u);
+                part += e[t].y + (uint32_t)v[t];
+            }
+            const int S = (int)wave_uadd(part);                    // sum of the children's N + v (mcts.py:112)
+            const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];
+            uint32_t bk = 0, bw = 0;
+            int bi = 0x7FFFFFFF;
+#pragma unroll
+            for (int t = 0; t < NW; t++) {
+                const int jj = t * 64 + lane;
+                if (jj < k) {
+                    const float P = __uint_as_float(e[t].x), W = __uint_as_float(e[t].z);
+                    const int n = (int)e[t].y + v[t];
+                    const float w = (v[t] > 0) ? __fsub_rn(W, (float)v[t]) : W;
+                    const float t1 = __fmul_rn(d.cpuct, P);
+                    const float t2 = __fmul_rn(t1, sq);
+                    const float u = __fdiv_rn(t2, (float)(1 + n));
+                    const float q = (n > 0) ? __fdiv_rn(w, (float)n) : 0.0f;
+                    const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);
+                    const uint32_t key = f32_key(ucb);
+                    if (key > bk) { bk = key; bi = jj; bw = e[t].w; }
+                }
+            }
+            const uint32_t mx = wave_umax(bk);
+            const bool tied = (bk == mx) && (bi != 0x7FFFFFFF);
+            int best;
+            if (k <= 64) {
+                const uint64_t tm = __ballot(tied);
+                best = tm ? (int)__ffsll((unsigned long long)tm) - 1 : 0x7FFFFFFF;
+            } else {
+                const uint32_t mi = wave_umin(tied ? (uint32_t)bi : 0xFFFFFFFFu);
+                best = (mi == 0xFFFFFFFFu) ? 0x7FFFFFFF : (int)mi;
+            }
+            if (mx == 0u) best = 0x7FFFFFFF;
+            if (best == 0x7FFFFFFF) { kind = K_NONE; break; }
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
+            if (lane == 0) path[depth] = first + best;
+            match = __ballot(vi == best);                          // vi == -1 outside `match`
+            depth++;
+            c_levels++;
+            c_scan += (uint64_t)k;
+            parent = node;
+            action = (int)(w >> 24);
+            const uint32_t child = w & CHILD_NONE;
+            if (child == CHILD_NONE) { kind = K_EXPAND; node = -1; break; }
+            node = (int)child;
+        }
+        if (kind == K_NONE) { failed = true; break; }
+        // the earlier descents left in `match` walked the same path and so ended on the same leaf
+        const int dup = match ? (int)__ffsll((unsigned long long)match) - 1 : -1;
+        const bool need = (kind == K_EXPAND || kind == K_REEXPAND || kind == K_ROOTPASS) && dup < 0;
+        LeafRec *rec = m.leaves + (size_t)g * K + j;
+        if (need) {
+            BB<NW> black, white;
+            int lplayer;
+            if (kind == K_ROOTPASS) {
+                const uint64_t *src = d.nboard + (size_t)g * d.node_cap * 2 * NW;
+                black = bb_uniform_load<NW>(src);
+                white = bb_uniform_load<NW>(src + NW);
+                lplayer = rfl((int)st->root_player);
+            } else {                                               // copied boards: the parent's legal move always places
+                const uint64_t *src = d.nboard + ((size_t)g * d.node_cap + parent) * 2 * NW;
+                black = bb_uniform_load<NW>(src);
+                white = bb_uniform_load<NW>(src + NW);
+                const int pplayer = node_player(rfl(nodes[parent].y));
+                if (pplayer == 1) black = black | bb_bit<NW>(action);
+                else white = white | bb_bit<NW>(action);
+                lplayer = -pplayer;
+            }
+            BB<NW> mask;
+            bool term;
+            float tv;
+            leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
+            write_planes<NW>(planes + ((size_t)g * K + j) * 5 * d.geo.A, d.geo, black, white);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < NW; i++) {
+                    rec->board[i] = black.w[i];
+                    rec->board[NW + i] = white.w[i];
+                    rec->mask[i] = mask.w[i];
+                }
+                rec->player = (int8_t)lplayer;
+                rec->terminal = term;
+                rec->tv = tv;
+            }
+        }
+        if (lane == 0) {
+            rec->kind = (uint8_t)kind;
+            rec->node = node;
+            rec->path_len = depth;
+            rec->dup = dup;
+            if (needs_eval) needs_eval[(size_t)g * K + j] = need;
+        }
+        c_evals += need ? 1 : 0;
+        c_term += (kind == K_TERMINAL) ? 1 : 0;
+        __syncthreads();   // this descent's path is read by the lanes of the next one
+    }
+    if (failed && lane == 0) st->err = st->err_ever = 1;           // path too deep / no selectable child: the game stops
+    if (needs_eval && lane < K && (failed || lane >= keff)) needs_eval[(size_t)g * K + lane] = 0;
+    if (lane == 0) {
+        ms[1] = failed ? 0 : keff;
+        st->ctr[1] += c_levels;
+        st->ctr[2] += c_scan;
+        if (!failed) st->ctr[0] += c_evals;
+        st->ctr[4] += c_term;
+    }
+}
+
+// expansion + backup of the K_eff descents of the last step, in descent order: the first occurrence of a leaf expands it
+// exactly like do_expand_backup, then every descent backs its value up along its own path
+template <int NW>
+__device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const MultiDev &m, const int g, const float *policy,
+                                                       const float *value, const double *noise) {
+    GameState *st = d.state + g;
+    const int lane = lane_id();
+    const int K = m.K;
+    int32_t *ms = m.mst + 2 * g;
+    const int nl = rfl(ms[1]);
+    if (nl == 0) return;
+    uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    const int A = d.geo.A;
+    for (int j = 0; j < nl; j++) {
+        const LeafRec *rec = m.leaves + (size_t)g * K + j;
+        const int kind = rfl((int)rec->kind);
+        const int depth = rfl(rec->path_len);
+        const int dup = rfl(rec->dup);
+        const int32_t *path = d.path + ((size_t)g * K + j) * d.path_cap;
+        const size_t row = (size_t)g * K + (dup >= 0 ? dup : j);
+        int node = rfl(rec->node);
+        float v;
+        bool v_is_py = false;
+        if (kind == K_TERMINAL) {
+            v = rflf(__uint_as_float(nodes[node].z));
+            v_is_py = true;
+        } else if (dup >= 0) {
+            v = rflf(value[row]);                                  // checked when the first occurrence was expanded
+        } else {
+            v = (kind == K_ROOTINIT) ? 0.0f : rflf(value[row]);
+            bool fail = (v != v);
+            int n_nodes = rfl(st->n_nodes), n_edges = rfl(st->n_edges);
+            if (!fail && kind == K_EXPAND) {
+                if (n_nodes >= (int)d.node_cap) fail = true;
+                else {
+                    node = n_nodes++;
+                    if (lane == 0) {
+                        uint4 *pe = edges + path[depth - 1];
+                        pe->w = (pe->w & 0xFF000000u) | (uint32_t)node;
+                        st->ctr[5] += 1;
+                    }
+                }
+            }
+            BB<NW> mask;
+#pragma unroll
+            for (int i = 0; i < NW; i++) mask.w[i] = rfl64(rec->mask[i]);
+            const int lplayer = rfl((int)rec->player);
+            if (!fail) {
+                uint64_t *nb = d.nboard + ((size_t)g * d.node_cap + node) * 2 * NW;
+                if (lane == 0) {
+#pragma unroll
+                    for (int i = 0; i < 2 * NW; i++) nb[i] = rec->board[i];
+                }
+            }
+            if (!fail && rfl((int)rec->terminal)) {
+                if (lane == 0) nodes[node] = make_uint4(0u, node_pack(0, NF_TERMINAL, lplayer), __float_as_uint(rec->tv), __float_as_uint(v));
+            } else if (!fail) {
+                const int k = bb_popc(mask);
+                if (n_edges + k > (int)d.edge_cap) fail = true;
+                else {
+                    const float keep = (float)(1.0 - d.eps);
+                    bool mix = false;
+                    if (noise) {
+                        uint64_t any = 0;
+#pragma unroll
+                        for (int t = 0; t < NW; t++) {
+                            const int cell = t * 64 + lane;
+                            const bool nz = ((mask.w[t] >> lane) & 1) && noise[(size_t)g * A + cell] != 0.0;
+                            any |= __ballot(nz);
+                        }
+                        mix = any != 0;
+                    }
+                    int base = n_edges;
+                    bool bad = false;
+#pragma unroll
+                    for (int t = 0; t < NW; t++) {
+                        const int cell = t * 64 + lane;
+                        if ((mask.w[t] >> lane) & 1) {
+                            float p = policy[row * A + cell];
+                            bad |= (p != p);
+                            if (mix) {
+                                const float kp = __fmul_rn(keep, p);
+                                p = (float)__dadd_rn((double)kp, __dmul_rn(d.eps, noise[(size_t)g * A + cell]));
+                            }
+                            edges[base + mbcnt(mask.w[t])] = make_uint4(__float_as_uint(p), 0u, 0u, CHILD_NONE | ((uint32_t)cell << 24));
+                        }
+                        base += yy_popc64(mask.w[t]);
+                    }
+                    if (__ballot(bad)) fail = true;
+                    else {
+                        if (lane == 0) {
+                            nodes[node] = make_uint4((uint32_t)n_edges, node_pack(k, 0u, lplayer), 0u, __float_as_uint(v));
+                            st->ctr[3] += (uint64_t)k;
+                        }
+                        n_edges += k;
+                    }
+                }
+            }
+            if (fail) {   // NaN from the evaluator or a full arena: the game stops, the error is sticky
+                if (lane == 0) { st->err = st->err_ever = 1; ms[1] = 0; }
+                return;
+            }
+            if (lane == 0) {
+                st->n_nodes = n_nodes;
+                st->n_edges = n_edges;
+            }
+        }
+        if (kind == K_ROOTINIT) break;                             // no backup
+        for (int i = lane; i < depth; i += 64) {                   // mcts.py:406-412, as in do_expand_backup
+            uint4 *e = edges + path[i];
+            const int dist = depth - (i + 1);
+            const float sv = (dist & 1) ? -v : v;
+            uint4 r = *e;
+            r.y = (uint32_t)((int)r.y + 1);
+            r.z = __float_as_uint(__fadd_rn(__uint_as_float(r.z), sv));
+            *e = r;
+        }
+        if (lane == 0) {
+            const float sv = (depth & 1) ? -v : v;
+            st->root_N += 1;
+            if (st->root_w_is_py && v_is_py && depth == 0) {
+                st->root_W_py += (double)((sv == 0.0001f) ? 0.0001 : (sv == -0.0001f ? -0.0001 : (double)sv));
+            } else {
+                const float base = st->root_w_is_py ? (float)st->root_W_py : st->root_W;
+                st->root_W = __fadd_rn(base, sv);
+                st->root_w_is_py = 0;
+            }
+        }
+        __syncthreads();   // the next descent's backup and expansion read what this one wrote
+    }
+    if (lane == 0) ms[1] = 0;
+}
+
+template <int NW> __global__ void __launch_bounds__(64) k_mcts_multi(MctsDev d, MultiDev m, int do_backup, int do_sel,
+                                                                     const float *policy, const float *value,
+                                                                     const double *noise, float *planes,
+                                                                     uint8_t *needs_eval) {
+    const int g = blockIdx.x;
+    if (do_backup) do_expand_backup_multi<NW>(d, m, g, policy, value, noise);
+    if (do_backup && do_sel) __syncthreads();
+    if (do_sel) do_select_multi<NW>(d, m, g, planes, needs_eval);
+}
+
 template <int NW> __global__ void __launch_bounds__(64) k_root_counts(MctsDev d, int32_t *counts, float *cw, float *cp) {
     const int g = blockIdx.x, A = d.geo.A;
     const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
@@ -1131,9 +1483,22 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     if (cfg->max_sims < 1) return set_err(YY_E_INVALID, "max_sims < 1%s%s");
     if ((cfg->flags & YY_FLAG_REUSE_PASS_VALUE) && (cfg->flags & YY_FLAG_ALIASED))
         return set_err(YY_E_INVALID, "YY_FLAG_REUSE_PASS_VALUE needs copied boards: with the aliased board a node's position changes between visits%s%s");
+    if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
+    if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
+    if (cfg->leaves_per_step > 1) {
+        if (cfg->flags & YY_FLAG_ALIASED)
+            return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 1 needs copied boards (YY_FLAG_ALIASED is not supported)%s%s");
+        if (cfg->flags & (YY_FLAG_REUSE_PASS_VALUE | YY_FLAG_REUSE_TRANSPOSITIONS | YY_FLAG_KEEP_EVALUATIONS))
+            return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 1 does not support evaluation reuse (YY_FLAG_REUSE_PASS_VALUE, "
+                                             "YY_FLAG_REUSE_TRANSPOSITIONS, YY_FLAG_KEEP_EVALUATIONS)%s%s");
+    }
     yy_mcts *c = new yy_mcts();
     memset(c, 0, sizeof *c);
     c->cfg = *cfg;
+    c->K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
+    c->target_sims = cfg->max_sims;
+    // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
+    c->sqrt_len = cfg->max_sims + 2 + (c->K > 1 ? c->K : 0);
     yy_make_geo(&c->geo, cfg->R, cfg->C, cfg->flags & YY_FLAG_ROWCOL);
     const int A = c->geo.A, NW = c->geo.NW;
     c->node_cap = cfg->nodes_per_game > 0 ? cfg->nodes_per_game : (int64_t)cfg->max_sims + 2;
@@ -1155,9 +1520,11 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         {(void **)&c->nodes, G * c->node_cap * sizeof(uint4)},
         {(void **)&c->nboard, copied ? G * c->node_cap * 2 * NW * sizeof(uint64_t) : 8},
         {(void **)&c->gboard, G * 2 * NW * sizeof(uint64_t)},
-        {(void **)&c->path, G * c->path_cap * sizeof(int32_t)},
+        {(void **)&c->path, G * c->K * c->path_cap * sizeof(int32_t)},
         {(void **)&c->state, G * sizeof(GameState)},
-        {(void **)&c->sqrt_tab, (size_t)(cfg->max_sims + 2) * sizeof(float)},
+        {(void **)&c->sqrt_tab, (size_t)c->sqrt_len * sizeof(float)},
+        {(void **)&c->leaves, c->K > 1 ? G * c->K * sizeof(LeafRec) : 0},
+        {(void **)&c->mst, c->K > 1 ? G * 2 * sizeof(int32_t) : 0},
         {(void **)&c->scratch, 9 * sizeof(uint64_t)},
         {(void **)&c->ec_meta, ec_on ? G * (size_t)c->ec_cap * sizeof(uint32_t) : 0},
         {(void **)&c->ec_key, ec_on ? G * (size_t)c->ec_cap * 2 * NW * sizeof(uint64_t) : 0},
@@ -1178,12 +1545,13 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         c->bytes += a.n;
     }
     // f32(math.sqrt(S)) table built with the host's correctly rounded double sqrt (mcts.py:130)
-    float *tab = new float[cfg->max_sims + 2];
-    for (int s = 0; s < cfg->max_sims + 2; s++) tab[s] = (float)sqrt((double)s);
+    float *tab = new float[c->sqrt_len];
+    for (int s = 0; s < c->sqrt_len; s++) tab[s] = (float)sqrt((double)s);
     hipError_t e = hipMemset(c->state, 0, G * sizeof(GameState));
     if (e == hipSuccess) e = hipMemset(c->nodes, 0, G * c->node_cap * sizeof(uint4));
     if (e == hipSuccess && c->ec_meta) e = hipMemset(c->ec_meta, 0, G * (size_t)c->ec_cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(c->sqrt_tab, tab, (size_t)(cfg->max_sims + 2) * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && c->mst) e = hipMemset(c->mst, 0, G * 2 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(c->sqrt_tab, tab, (size_t)c->sqrt_len * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     delete[] tab;
     if (e != hipSuccess) { yy_mcts_destroy(c); return set_err(YY_E_HIP, "arena initialisation: %s%s", hipGetErrorString(e)); }
@@ -1193,10 +1561,18 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
 
 extern "C" int yy_mcts_destroy(yy_mcts *c) {
     if (!c) return YY_OK;
-    void *ps[] = {c->edges, c->nodes, c->nboard, c->gboard, c->path, c->state, c->sqrt_tab, c->scratch, c->ec_meta, c->ec_key, c->ec_val, c->ec_pol};
+    void *ps[] = {c->edges, c->nodes, c->nboard, c->gboard, c->path, c->state, c->sqrt_tab, c->scratch, c->ec_meta, c->ec_key, c->ec_val, c->ec_pol,
+                  c->leaves, c->mst};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     delete c;
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_set_num_sims(yy_mcts *c, int32_t num_sims) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (num_sims < 0 || num_sims > c->cfg.max_sims) return set_err(YY_E_INVALID, "num_sims outside 0 .. max_sims%s%s");
+    c->target_sims = num_sims == 0 ? c->cfg.max_sims : num_sims;
     return YY_OK;
 }
 
@@ -1210,7 +1586,8 @@ extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *pla
                              float *planes, yy_stream_t s) {
     if (!c || !boards || !players || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
     MctsDev d = make_dev(c);
-    DISPATCH_NW(c->geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, boards,
+    MultiDev m = make_multi(c);
+    DISPATCH_NW(c->geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, m, c->target_sims, boards,
                                                players, active, planes));
     HIP_TRY(hipGetLastError());
     c->pending = 2;  // root expansion pending
@@ -1221,8 +1598,14 @@ static int launch_mcts(yy_mcts *c, int backup, int sel, const float *policy, con
                        double eps, float *planes, uint8_t *needs_eval, yy_stream_t s) {
     MctsDev d = make_dev(c);
     d.eps = eps;
-    DISPATCH_NW(c->geo.NW, k_mcts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, backup, sel,
-                                               policy, value, noise, planes, needs_eval));
+    if (c->K > 1) {
+        MultiDev m = make_multi(c);
+        DISPATCH_NW(c->geo.NW, k_mcts_multi<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, m, backup, sel,
+                                                   policy, value, noise, planes, needs_eval));
+    } else {
+        DISPATCH_NW(c->geo.NW, k_mcts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, backup, sel,
+                                                   policy, value, noise, planes, needs_eval));
+    }
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
@@ -1343,6 +1726,7 @@ extern "C" int yy_mcts_set_book(yy_mcts *c, const uint32_t *meta, const uint64_t
     if (!meta) { c->bk_meta = nullptr; c->bk_key = nullptr; c->bk_val = c->bk_pol = nullptr; c->bk_cap = 0; c->bk_stones = 0; return YY_OK; }
     if (!keys || !val || !pol || cap < 64 || (cap & (cap - 1)) || cap > (1ll << 31) || max_stones < 1)
         return set_err(YY_E_INVALID, "yy_mcts_set_book: bad argument (cap must be a power of two)%s%s");
+    if (c->K > 1) return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_book: leaves_per_step > 1 does not support evaluation reuse%s%s");
     c->bk_meta = meta; c->bk_key = keys; c->bk_val = val; c->bk_pol = pol; c->bk_cap = cap; c->bk_stones = max_stones;
     return YY_OK;
 }

@@ -448,14 +448,17 @@ class BatchedMCTS:
 
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
-                 keep_evaluations=False):
+                 keep_evaluations=False, leaves_per_step=1):
         """reuse_pass_value (copied boards only): a childless non-terminal node keeps the value of its first
         evaluation instead of being evaluated again on every visit (YY_FLAG_REUSE_PASS_VALUE, include/yy_engine.h);
         needs a deterministic evaluator whose row results do not depend on the rest of the batch.
         reuse_transpositions: a leaf whose position was already evaluated in this search takes the cached policy row and
         value instead of an evaluator row (YY_FLAG_REUSE_TRANSPOSITIONS); same requirement.
         keep_evaluations: the cache also serves the later searches of the context (YY_FLAG_KEEP_EVALUATIONS): every search
-        must then use the same evaluator -- call clear_evaluation_cache() when the network changes."""
+        must then use the same evaluator -- call clear_evaluation_cache() when the network changes.
+        leaves_per_step K > 1: every step runs K descents per game with virtual visits and sends up to G*K leaf rows to the
+        evaluator (row g*K + j = descent j of game g; include/yy_engine.h), so a search of num_sims simulations takes
+        ceil(num_sims / K) steps.  Copied boards only, no evaluation reuse.  K = 1 is the reference's search."""
         if not torch.cuda.is_available():
             raise _lib.YYError(-100, "BatchedMCTS needs a ROCm device: the hot path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -463,17 +466,20 @@ class BatchedMCTS:
         self.max_sims, self.cpuct, self.aliased, self.rowcol = int(max_sims), float(cpuct), bool(aliased), bool(rowcol)
         self.reuse_pass_value, self.reuse_transpositions = bool(reuse_pass_value), bool(reuse_transpositions)
         self.keep_evaluations = bool(keep_evaluations)
+        self.K = max(1, int(leaves_per_step))
+        self.rows = self.G * self.K            # evaluator rows of a step
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
                          | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0),
-                         int(edges_per_game), int(nodes_per_game))
+                         int(edges_per_game), int(nodes_per_game), int(leaves_per_step))
         h = ct.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_create(ct.byref(cfg), ct.byref(h)))
         self._h = h
-        self.planes = torch.zeros((self.G, 5, self.R, self.C), dtype=torch.float32, device=self.device)
-        self.needs_eval = torch.zeros(self.G, dtype=torch.uint8, device=self.device)
+        self.planes = torch.zeros((self.rows, 5, self.R, self.C), dtype=torch.float32, device=self.device)
+        self.needs_eval = torch.zeros(self.rows, dtype=torch.uint8, device=self.device)
+        self._num_sims = self.max_sims
 
     # -- lifetime
     def close(self):
@@ -493,6 +499,16 @@ class BatchedMCTS:
         check(lib().yy_mcts_memory_bytes(self._h, ct.byref(n)))
         return n.value
 
+    def steps(self, num_sims):
+        """Simulation steps (evaluator calls after the root call) of a search of num_sims simulations."""
+        return -(-int(num_sims) // self.K)
+
+    def set_num_sims(self, num_sims):
+        """Simulations of the searches begun from now on; K > 1 runs the last step of a search with fewer descents."""
+        if int(num_sims) != self._num_sims:
+            check(lib().yy_mcts_set_num_sims(self._h, int(num_sims)))
+            self._num_sims = int(num_sims)
+
     # -- the C ABI, one method per entry point
     def begin(self, boards, root_players, active=None):
         _need(boards, torch.int8, (self.G, self.R, self.C), "boards")
@@ -503,7 +519,7 @@ class BatchedMCTS:
             check(lib().yy_mcts_begin(self._h, _p(boards), _p(root_players), _p(active), _p(self.planes), _stream()))
 
     def expand_root(self, policy, noise=None, eps=0.25):
-        _need(policy, torch.float32, (self.G, self.A), "policy")
+        _need(policy, torch.float32, (self.rows, self.A), "policy")
         if noise is not None:
             _need(noise, torch.float64, (self.G, self.A), "noise")
         with torch.cuda.device(self.device):
@@ -514,14 +530,14 @@ class BatchedMCTS:
             check(lib().yy_mcts_select(self._h, _p(self.planes), _p(self.needs_eval), _stream()))
 
     def expand_backup(self, policy, value):
-        _need(policy, torch.float32, (self.G, self.A), "policy")
-        _need(value, torch.float32, (self.G,), "value")
+        _need(policy, torch.float32, (self.rows, self.A), "policy")
+        _need(value, torch.float32, (self.rows,), "value")
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_expand_backup(self._h, _p(policy), _p(value), _stream()))
 
     def step(self, policy, value):
-        _need(policy, torch.float32, (self.G, self.A), "policy")
-        _need(value, torch.float32, (self.G,), "value")
+        _need(policy, torch.float32, (self.rows, self.A), "policy")
+        _need(value, torch.float32, (self.rows,), "value")
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_step(self._h, _p(policy), _p(value), _p(self.planes), _p(self.needs_eval), _stream()))
 
@@ -597,21 +613,24 @@ class BatchedMCTS:
 
     # -- the whole of MCTS.search for G games (mcts.py:275-343)
     def search(self, boards, root_players, evaluator, num_sims, noise=None, eps=0.25, active=None, fused=True):
-        """evaluator(planes f32[G,5,R,C]) -> (policy f32[G,A] softmax, value f32[G]) on device.
+        """evaluator(planes f32[G*K,5,R,C]) -> (policy f32[G*K,A] softmax, value f32[G*K]) on device.
         Runs 1 + num_sims evaluator calls exactly like the reference (root call, then one per
-        simulation) and returns the root visit counts int32 [G,A]."""
+        simulation; with K leaves per step 1 + ceil(num_sims / K)) and returns the root visit counts int32 [G,A]."""
         if num_sims > self.max_sims:
             raise _lib.YYError(-1, f"num_sims {num_sims} > max_sims {self.max_sims} the context was sized for")
+        if self.K > 1:
+            self.set_num_sims(num_sims)
         self.begin(boards, root_players, active)
         policy, _ = evaluator(self.planes)
         self.expand_root(policy, noise, eps)
         self.select()
-        for s in range(num_sims):
+        n_steps = self.steps(num_sims)
+        for s in range(n_steps):
             policy, value = evaluator(self.planes)
-            if fused and s + 1 < num_sims:
+            if fused and s + 1 < n_steps:
                 self.step(policy, value)
             else:
                 self.expand_backup(policy, value)
-                if s + 1 < num_sims:
+                if s + 1 < n_steps:
                     self.select()
         return self.root_counts()

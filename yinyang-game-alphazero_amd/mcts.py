@@ -133,14 +133,18 @@ class _HostPredictEvaluator:
 class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
-                 board_semantics="aliased", device=None, evaluation_reuse=False):
+                 board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1):
         """board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
         evaluation_reuse (not in the reference; default off = its evaluator call sequence): a position is evaluated once per
         search (pass values with copied boards + the evaluation cache, include/yy_engine.h YY_FLAG_REUSE_*); same results, fewer
         evaluator rows; needs a deterministic network whose row results do not depend on the rest of the batch.
         num_threads is accepted for signature compatibility; simulations of one search are always
-        sequential (the reference's thread pool is an unsynchronised race)."""
+        sequential (the reference's thread pool is an unsynchronised race).
+        leaves_per_step K (not in the reference; default 1 = its search): leaf parallelism with virtual visits -- every step
+        runs K descents per game and evaluates their leaves in one batch, so a search takes ceil(num_simulations / K)
+        evaluator calls (include/yy_engine.h).  Needs board_semantics="copied" and no evaluation_reuse.  It changes which
+        moves a search picks."""
         assert board_semantics in ("aliased", "copied")
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
@@ -148,6 +152,7 @@ class MCTS:
         self.use_dirichlet, self.dirichlet_alpha, self.dirichlet_epsilon = dirichlet_noise, dirichlet_alpha, dirichlet_epsilon
         self.board_semantics = board_semantics
         self.evaluation_reuse = bool(evaluation_reuse)
+        self.leaves_per_step = max(1, int(leaves_per_step))
         self.R, self.C = game.getBoardSize()
         self.A = game.getActionSize()
         self.rowcol = bool(getattr(game, "rowcol_rule", False))
@@ -164,7 +169,7 @@ class MCTS:
                                      aliased=(self.board_semantics == "aliased"), rowcol=self.rowcol,
                                      device=self.device,
                                      reuse_pass_value=self.evaluation_reuse and self.board_semantics == "copied",
-                                     reuse_transpositions=self.evaluation_reuse)
+                                     reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step)
             self._ctx[G] = ctx
         return ctx
 

@@ -60,21 +60,23 @@ class LockstepSearch:
             self.graphs[self.ctx.G] = g
 
     def _evaluate(self, rows, compact=False):
-        """Evaluator on the first `rows` leaf rows (all searching games must sit there); returns full-height buffers.
+        """Evaluator on the leaf rows of the first `rows` games (all searching games must sit there); returns full-height buffers.
         compact: pass the step's needs_eval flags to an evaluator that can skip the rows whose leaf needs no evaluation
-        (terminal revisits, mcts.py:365-366; finished or idle slots)."""
+        (terminal revisits, mcts.py:365-366; finished or idle slots).  With K leaves per step a game has K rows."""
         ctx = self.ctx
+        full = getattr(ctx, "rows", ctx.G)         # G * K evaluator rows
+        rows = rows * (full // ctx.G)
         kw = {}
         if compact and getattr(self.evaluator, "supports_compaction", False):
-            kw["needs_eval"] = ctx.needs_eval if rows >= ctx.G else ctx.needs_eval[:rows]
+            kw["needs_eval"] = ctx.needs_eval if rows >= full else ctx.needs_eval[:rows]
         if getattr(self.evaluator, "supports_static", False):
             kw["static"] = id(self)                # private buffers: the results are consumed by the tree kernel before this search's next call
-        if rows >= ctx.G:
+        if rows >= full:
             return self.evaluator(ctx.planes, **kw)
         policy, value = self.evaluator(ctx.planes[:rows], **kw)
         if self._policy is None:
-            self._policy = torch.zeros((ctx.G, policy.shape[1]), dtype=torch.float32, device=ctx.device)
-            self._value = torch.zeros(ctx.G, dtype=torch.float32, device=ctx.device)
+            self._policy = torch.zeros((full, policy.shape[1]), dtype=torch.float32, device=ctx.device)
+            self._value = torch.zeros(full, dtype=torch.float32, device=ctx.device)
         self._policy[:rows].copy_(policy)
         self._value[:rows].copy_(value)
         return self._policy, self._value
@@ -98,12 +100,15 @@ class LockstepSearch:
             self._book_version = getattr(ctx, "book_version", 0)
             self._graph_evaluator = self.evaluator
         rows = ctx.G if rows is None else min(int(rows), ctx.G)
+        K = getattr(ctx, "K", 1)
+        if K > 1:
+            ctx.set_num_sims(num_sims)                         # the last step's descents follow from it on the device
         ctx.begin(boards, root_players, active)
         policy, _ = self._evaluate(rows)                       # mcts.py:295, value discarded
         ctx.expand_root(policy, noise, eps)
         ctx.select()
         done = 0
-        n_fused = num_sims - 1
+        n_fused = (num_sims if K == 1 else ctx.steps(num_sims)) - 1
         gkey = rows if not hasattr(self.evaluator, "form_key") else (rows, self.evaluator.form_key(id(self)))
         graph = self.graphs.get(gkey)
         if self.use_graph and graph is None and n_fused > self.eager_sims:
