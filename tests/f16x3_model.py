@@ -1,5 +1,5 @@
 """Float64 models of the split-f16 evaluator ("f16x3": csrc/yy_tower_g.hip, yy_fc_heads.hip, k_head_finish_f32 in
-yy_engine.hip) and the networks that stress its number format.  Test infrastructure, CPU or device, no GPU kernel.
+yy_nn_epilogue.hip) and the networks that stress its number format.  Test infrastructure, CPU or device, no GPU kernel.
 
 * `reference_f64`: the module in float64, stage by stage.
 * `emulate`: the kernels' arithmetic.  It reads the PACKED operands (network.pack_tower_g / pack_heads_g / pack_fc_heads),

@@ -1,0 +1,25 @@
+// yy_common.h -- what the .hip files of libyy_hip.so share: the error reporting behind yy_last_error() and a device
+// one-liner that more than one kernel file needs.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include "../../include/yy_engine.h"
+
+// Sets the calling thread's yy_last_error() text and returns `code` (defined in yy_engine.hip).
+extern "C" int yy_tower_set_err(int code, const char *msg);
+
+static inline int yy_hip_fail(const char *what, hipError_t e) {
+    char msg[512];
+    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
+    return yy_tower_set_err(YY_E_HIP, msg);
+}
+#define HIP_TRY(x)                                        \
+    do {                                                  \
+        hipError_t e_ = (x);                              \
+        if (e_ != hipSuccess) return yy_hip_fail(#x, e_); \
+    } while (0)
+
+// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
+// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }

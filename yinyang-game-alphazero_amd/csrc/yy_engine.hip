@@ -1,5 +1,7 @@
 // yy_engine.hip -- HIP kernels + C ABI (include/yy_engine.h) of the Yin-Yang self-play hot path
-// for MI355X (gfx950, wave64).  Written for CDNA4 only.
+// for MI355X (gfx950, wave64).  Written for CDNA4 only.  Two parts: the stateless rules kernels and the MCTS context
+// (tree kernels for K = 1 and K > 1 leaves per step on shared building blocks, read-out, book).  The evaluator's kernels are
+// in yy_tower*.hip, yy_fc_heads.hip and yy_nn_epilogue.hip, the episode loop's draws in yy_selfplay.hip.
 //
 // Execution model
 //   * tree kernels: ONE GAME PER WAVEFRONT (block = 64 threads, blockIdx.x = game).  Lane l owns
@@ -27,6 +29,7 @@
 
 #include "../../include/yy_engine.h"
 #include "yy_bitboard.h"
+#include "yy_common.h"
 
 #define YY_VERSION 101
 
@@ -36,14 +39,9 @@ static int set_err(int code, const char *fmt, const char *a = "", const char *b 
     snprintf(g_err, sizeof g_err, fmt, a, b);
     return code;
 }
-#define HIP_TRY(x)                                                                    \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) return set_err(YY_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" const char *yy_last_error(void) { return g_err; }
-extern "C" int yy_tower_set_err(int code, const char *msg) { return set_err(code, "%s%s", msg); }   // for yy_tower.hip
+extern "C" int yy_tower_set_err(int code, const char *msg) { return set_err(code, "%s%s", msg); }   // for the other .hip files (yy_common.h)
 extern "C" int yy_version(void) { return YY_VERSION; }
 
 static int check_geo(int G, int R, int C) {
@@ -464,39 +462,34 @@ template <int NW> __device__ __forceinline__ uint64_t bb_hash(const uint64_t *bl
     return h;
 }
 
-struct GameState {
-    int32_t n_nodes, n_edges;
-    int32_t root_N;
-    float root_W;
-    double root_W_py;       // root.value_sum while it is still a python float (terminal root only)
-    int32_t path_len;       // edges on the selected path == depth of the leaf
-    int32_t leaf_node;      // node record of the leaf when it already has one, else -1
-    float leaf_tv;          // terminal value of a freshly evaluated leaf (f32 of 1 / -1 / 1e-4)
-    int8_t root_player;
-    uint8_t active, err, root_w_is_py;
-    uint8_t leaf_kind;
-    int8_t leaf_player;
-    uint8_t leaf_terminal;
-    uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
-    int32_t leaf_src;       // >= 0: slot of the evaluation cache that holds this leaf's position (no evaluator row), else -1
-    int32_t leaf_ec_slot;   // leaf_src < 0: the cache slot this leaf's evaluation goes into
-    uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
-    int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
-    uint64_t leaf_board[2 * YY_MAX_NW];
-    uint64_t leaf_mask[YY_MAX_NW];
-    uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
-};
-
-// Leaf-parallel steps (leaves_per_step K > 1): the pending leaf of descent j of game g is leaves[g*K + j]
+// The pending leaf of one descent: what selection leaves for the expansion + backup that follows the evaluator.  K = 1 keeps
+// the one record of a game in its GameState; leaf-parallel steps (leaves_per_step K > 1) keep descent j of game g in
+// leaves[g*K + j].  board / mask / player / terminal / tv are set only for a leaf that is evaluated (leaf_store).
 struct LeafRec {
-    int32_t path_len, node;  // edges on the path; the leaf's node record (-1: unexpanded edge)
-    int32_t dup;             // >= 0: an earlier descent of this step that ended on the same leaf (its row is shared), else -1
-    float tv;                // terminal value of a freshly evaluated leaf
+    int32_t path_len, node;  // edges on the path == depth of the leaf; the leaf's node record when it already has one, else -1
+    int32_t dup;             // K > 1: >= 0: an earlier descent of this step that ended on the same leaf (its row is shared), else -1
+    float tv;                // terminal value of a freshly evaluated leaf (f32 of 1 / -1 / 1e-4)
     uint8_t kind, terminal;
     int8_t player;
     uint8_t pad[5];
     uint64_t board[2 * YY_MAX_NW];
     uint64_t mask[YY_MAX_NW];
+};
+
+struct GameState {
+    int32_t n_nodes, n_edges;
+    int32_t root_N;
+    float root_W;
+    double root_W_py;       // root.value_sum while it is still a python float (terminal root only)
+    int8_t root_player;
+    uint8_t active, err, root_w_is_py;
+    uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
+    int32_t leaf_src;       // >= 0: slot of the evaluation cache that holds this leaf's position (no evaluator row), else -1
+    int32_t leaf_ec_slot;   // leaf_src < 0: the cache slot this leaf's evaluation goes into
+    uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
+    int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
+    LeafRec leaf;           // K = 1: the pending leaf
+    uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels
@@ -622,6 +615,194 @@ __device__ __forceinline__ void leaf_rules(const YYGeo &geo, const GeoBB<NW> &gb
     tv = (res == 2) ? 0.0001f : ((player == 1) ? (float)res : (float)-res);
 }
 
+// ---- building blocks shared by the K = 1 and the K > 1 tree kernel: each float32 / float64 sequence of the parity contract
+// with the reference exists once, here.
+#define BEST_NONE 0x7FFFFFFF
+
+// Order-preserving key of one child's PUCT score (mcts.py:120-133), float32 order of SURVEY 8a/a12.  K = 1 passes the edge's
+// N and W, K > 1 the counts with this step's virtual visits (do_select_multi).
+__device__ __forceinline__ uint32_t child_key(float cpuct, float sq, float P, int n, float w) {
+    const float t1 = __fmul_rn(cpuct, P);
+    const float t2 = __fmul_rn(t1, sq);
+    const float u = __fdiv_rn(t2, (float)(1 + n));
+    const float q = (n > 0) ? __fdiv_rn(w, (float)n) : 0.0f;
+    const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);   // + 0.0f: -0.0 compares equal to +0.0 (mcts.py:133)
+    return f32_key(ucb);
+}
+
+// Wave arg-max over the k children of a node: every lane brings the best key `bk` of its own children and that child's index
+// `bi` (BEST_NONE: none).  Returns the child with the largest key, the lowest index among ties = the lowest action
+// (mcts.py:133), or BEST_NONE when no child is selectable (every key 0: NaN scores).
+__device__ __forceinline__ int best_child(uint32_t bk, int bi, int k) {
+    const uint32_t mx = wave_umax(bk);
+    const bool tied = (bk == mx) && (bi != BEST_NONE);
+    int best;
+    if (k <= 64) {   // lane == child index: the lowest tied lane
+        const uint64_t tm = __ballot(tied);
+        best = tm ? (int)__ffsll((unsigned long long)tm) - 1 : BEST_NONE;
+    } else {
+        const uint32_t mi = wave_umin(tied ? (uint32_t)bi : 0xFFFFFFFFu);
+        best = (mi == 0xFFFFFFFFu) ? BEST_NONE : (int)mi;
+    }
+    if (mx == 0u) best = BEST_NONE;
+    return best;
+}
+
+// The position a descent ended on, and its side to move (the return value).  A pass root is evaluated on its own board
+// (mcts.py:371-381); every other leaf on its parent's board after getNextState (mcts.py:385-391): place iff legal
+// (yin_yang_game.py:52-58).  With copied boards the action is one of the parent's legal moves on this very board, so it
+// always places and is placed here.  The aliased board has moved on since: do_select tests legality and places it.
+template <int NW>
+__device__ __forceinline__ int leaf_position(const MctsDev &d, const GameState *st, const int g, const uint4 *nodes,
+                                             const int kind, const int parent, const int action, const bool aliased,
+                                             BB<NW> &black, BB<NW> &white) {
+    const uint64_t *src = aliased ? d.gboard + (size_t)g * 2 * NW
+                                  : d.nboard + ((size_t)g * d.node_cap + (kind == K_ROOTPASS ? 0 : parent)) * 2 * NW;
+    black = bb_uniform_load<NW>(src);
+    white = bb_uniform_load<NW>(src + NW);
+    if (kind == K_ROOTPASS) return rfl((int)st->root_player);
+    const int pplayer = node_player(rfl(nodes[parent].y));
+    if (!aliased) {
+        if (pplayer == 1) black = black | bb_bit<NW>(action);
+        else white = white | bb_bit<NW>(action);
+    }
+    return -pplayer;
+}
+
+// the position half of a leaf record: what the expansion needs of a leaf that is evaluated
+template <int NW>
+__device__ __forceinline__ void leaf_store(LeafRec *rec, BB<NW> black, BB<NW> white, BB<NW> mask, int player, bool term,
+                                           float tv) {
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            rec->board[i] = black.w[i];
+            rec->board[NW + i] = white.w[i];
+            rec->mask[i] = mask.w[i];
+        }
+        rec->player = (int8_t)player;
+        rec->terminal = term;
+        rec->tv = tv;
+    }
+}
+
+// Node.expand (mcts.py:50-91) of the evaluated leaf `rec`: v is its value, prow its policy row (the evaluator's row, a cache
+// row or a book row), path the edges that led to it.  A K_EXPAND leaf gets its node here; every other kind has one.
+// `hold`: a node without children keeps v for YY_FLAG_REUSE_PASS_VALUE.  Returns false on a NaN value, a full node or edge
+// arena or a NaN prior: the caller marks the game failed, it stops searching, and what was written up to there is never read.
+template <int NW>
+__device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, const int g, const LeafRec *rec,
+                                            const int32_t *path, const float *prow, const float v, const bool hold,
+                                            const bool aliased, const double *noise) {
+    if (v != v) return false;   // a NaN from the evaluator must not enter the statistics
+    const int lane = lane_id();
+    const int A = d.geo.A;
+    uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    const int lplayer = rfl((int)rec->player);
+    const bool term = rfl((int)rec->terminal) != 0;
+    int node = rfl(rec->node);
+    int n_nodes = rfl(st->n_nodes), n_edges = rfl(st->n_edges);
+    if (rfl((int)rec->kind) == K_EXPAND) {
+        if (n_nodes >= (int)d.node_cap) return false;
+        node = n_nodes++;
+        if (lane == 0) {
+            uint4 *pe = edges + path[rfl(rec->path_len) - 1];
+            pe->w = (pe->w & 0xFF000000u) | (uint32_t)node;
+            st->ctr[5] += 1;
+        }
+    }
+    BB<NW> mask;
+#pragma unroll
+    for (int i = 0; i < NW; i++) mask.w[i] = rfl64(rec->mask[i]);
+    if (!aliased) {
+        uint64_t *nb = d.nboard + ((size_t)g * d.node_cap + node) * 2 * NW;
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 2 * NW; i++) nb[i] = rec->board[i];
+        }
+    }
+    if (term) {                                                                 // mcts.py:63-68
+        if (lane == 0)
+            nodes[node] = make_uint4(0u, node_pack(0, NF_TERMINAL, lplayer), __float_as_uint(rec->tv), __float_as_uint(v));
+    } else {                                                                    // mcts.py:71-89
+        const int k = bb_popc(mask);
+        if (n_edges + k > (int)d.edge_cap) return false;
+        const float keep = (float)(1.0 - d.eps);
+        // a game whose noise row is all zero over its legal moves drew no noise (a Dirichlet draw
+        // sums to 1): it keeps the raw priors, like add_exploration_noise=False (mcts.py:298)
+        bool mix = false;
+        if (noise) {
+            uint64_t any = 0;
+#pragma unroll
+            for (int j = 0; j < NW; j++) {
+                const int cell = j * 64 + lane;
+                const bool nz = ((mask.w[j] >> lane) & 1) && noise[(size_t)g * A + cell] != 0.0;
+                any |= __ballot(nz);
+            }
+            mix = any != 0;
+        }
+        int base = n_edges;
+        bool bad = false;   // a NaN prior (python: `score > best` is never true for it, select_child returns None and the game raises)
+#pragma unroll
+        for (int j = 0; j < NW; j++) {
+            const int cell = j * 64 + lane;
+            if ((mask.w[j] >> lane) & 1) {
+                float p = prow[cell];
+                bad |= (p != p);
+                if (mix) {                                                      // mcts.py:310-312
+                    const float kp = __fmul_rn(keep, p);
+                    p = (float)__dadd_rn((double)kp, __dmul_rn(d.eps, noise[(size_t)g * A + cell]));
+                }
+                edges[base + mbcnt(mask.w[j])] =
+                    make_uint4(__float_as_uint(p), 0u, 0u, CHILD_NONE | ((uint32_t)cell << 24));
+            }
+            base += yy_popc64(mask.w[j]);
+        }
+        if (__ballot(bad)) return false;
+        if (lane == 0) {
+            nodes[node] = make_uint4((uint32_t)n_edges, node_pack(k, (hold && k == 0) ? NF_HASVALUE : 0u, lplayer), 0u,
+                                     __float_as_uint(v));                       // .w = the evaluator's value of this position
+            st->ctr[3] += (uint64_t)k;
+        }
+        n_edges += k;
+    }
+    if (lane == 0) {
+        st->n_nodes = n_nodes;
+        st->n_edges = n_edges;
+    }
+    return true;
+}
+
+// Backup (mcts.py:147-156, 406-412) of v along the `depth` edges of `path`: edge i leads to the node at depth i+1 and the
+// leaf is at `depth`; players alternate every ply, so the sign is the parity of the distance to the leaf.  v_is_py: v is a
+// python number (a terminal value), not an np.float32.
+__device__ __forceinline__ void backup_path(uint4 *edges, const int32_t *path, const int depth, const float v,
+                                            const bool v_is_py, GameState *st) {
+    const int lane = lane_id();
+    for (int i = lane; i < depth; i += 64) {
+        uint4 *e = edges + path[i];
+        const int dist = depth - (i + 1);
+        const float sv = (dist & 1) ? -v : v;
+        uint4 r = *e;
+        r.y = (uint32_t)((int)r.y + 1);
+        r.z = __float_as_uint(__fadd_rn(__uint_as_float(r.z), sv));
+        *e = r;
+    }
+    if (lane == 0) {
+        const float sv = (depth & 1) ? -v : v;
+        st->root_N += 1;
+        if (st->root_w_is_py && v_is_py && depth == 0) {
+            // terminal root: python float + python number stays a python float (f64)
+            st->root_W_py += (double)((sv == 0.0001f) ? 0.0001 : (sv == -0.0001f ? -0.0001 : (double)sv));
+        } else {
+            const float base = st->root_w_is_py ? (float)st->root_W_py : st->root_W;
+            st->root_W = __fadd_rn(base, sv);
+            st->root_w_is_py = 0;
+        }
+    }
+}
+
 // ---- root prologue: mcts.py:288-295
 template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, const int8_t *boards,
                                                                 const int8_t *players, const uint8_t *active,
@@ -629,6 +810,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
     const int g = blockIdx.x;
     const int K = m.K;          // K > 1: the root row is row g*K, the pending root expansion is leaf record g*K
     GameState *st = d.state + g;
+    LeafRec *rec = K > 1 ? m.leaves + (size_t)g * K : &st->leaf;
     const bool act = active ? (active[g] != 0) : true;
     BB<NW> black, white;
     board_to_bb<NW>(boards + (size_t)g * d.geo.A, d.geo.A, black, white);
@@ -639,12 +821,13 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         st->root_W = 0.0f;
         st->root_W_py = 0.0;
         st->root_w_is_py = 1;
-        st->path_len = 0;
-        st->leaf_node = 0;
         st->root_player = players[g];
         st->active = act;
         st->err = 0;
-        st->leaf_kind = act ? K_ROOTINIT : K_NONE;
+        rec->kind = act ? K_ROOTINIT : K_NONE;
+        rec->node = 0;
+        rec->path_len = 0;
+        rec->dup = -1;
         d.nodes[(size_t)g * d.node_cap] = make_uint4(0u, node_pack(0, 0, players[g]), 0u, 0u);
     }
     if (d.ec_meta && lane_id() == 0) {
@@ -676,33 +859,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         bool term;
         float tv;
         leaf_rules<NW>(d.geo, gb, black, white, rp, mask, term, tv);
-        if (lane_id() == 0 && K == 1) {
-#pragma unroll
-            for (int i = 0; i < NW; i++) {
-                st->leaf_board[i] = black.w[i];
-                st->leaf_board[NW + i] = white.w[i];
-                st->leaf_mask[i] = mask.w[i];
-            }
-            st->leaf_player = (int8_t)rp;
-            st->leaf_terminal = term;
-            st->leaf_tv = tv;
-        }
-        if (lane_id() == 0 && K > 1) {
-            LeafRec *rec = m.leaves + (size_t)g * K;
-#pragma unroll
-            for (int i = 0; i < NW; i++) {
-                rec->board[i] = black.w[i];
-                rec->board[NW + i] = white.w[i];
-                rec->mask[i] = mask.w[i];
-            }
-            rec->player = (int8_t)rp;
-            rec->terminal = term;
-            rec->tv = tv;
-            rec->kind = K_ROOTINIT;
-            rec->node = 0;
-            rec->path_len = 0;
-            rec->dup = -1;
-        }
+        leaf_store<NW>(rec, black, white, mask, rp, term, tv);
         write_planes<NW>(planes + (size_t)g * K * 5 * d.geo.A, d.geo, black, white);
     }
     if (K > 1 && lane_id() == 0) {
@@ -718,7 +875,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     const int lane = lane_id();
     if (!rfl((int)st->active) || rfl((int)st->err)) {
         if (lane == 0) {
-            st->leaf_kind = K_NONE;
+            st->leaf.kind = K_NONE;
             if (needs_eval) needs_eval[g] = 0;
         }
         return;
@@ -744,7 +901,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             break;
         }
         if (depth >= (int)d.path_cap) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }
-        // ---- Node.select_child (mcts.py:97-145), float32 order of SURVEY 8a/a12
+        // ---- Node.select_child (mcts.py:97-145)
         // sum of child visits (mcts.py:112).  Copied boards: every visit of an expanded node after its
         // first descends into exactly one child, so the sum is N(node)-1 (root: completed simulations) and
         // is carried down the descent; aliased boards can give a pass node children later, so sum there.
@@ -758,31 +915,14 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         }
         const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
         uint32_t bk = 0, bw = 0, bn = 0;
-        int bi = 0x7FFFFFFF;
+        int bi = BEST_NONE;
         for (int j = lane; j < k; j += 64) {
             const uint4 e = edges[first + j];
-            const float P = __uint_as_float(e.x), W = __uint_as_float(e.z);
-            const int N = (int)e.y;
-            const float t1 = __fmul_rn(d.cpuct, P);
-            const float t2 = __fmul_rn(t1, sq);
-            const float u = __fdiv_rn(t2, (float)(1 + N));
-            const float q = (N > 0) ? __fdiv_rn(W, (float)N) : 0.0f;
-            const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);   // + 0.0f: -0.0 compares equal to +0.0 (mcts.py:133)
-            const uint32_t key = f32_key(ucb);
+            const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e.x), (int)e.y, __uint_as_float(e.z));
             if (key > bk) { bk = key; bi = j; bw = e.w; bn = e.y; }               // strict >: lowest j of a lane
         }
-        const uint32_t mx = wave_umax(bk);
-        const bool tied = (bk == mx) && (bi != 0x7FFFFFFF);
-        int best;
-        if (k <= 64) {   // lane == child index: lowest tied lane = lowest action (mcts.py:133)
-            const uint64_t tm = __ballot(tied);
-            best = tm ? (int)__ffsll((unsigned long long)tm) - 1 : 0x7FFFFFFF;
-        } else {
-            const uint32_t mi = wave_umin(tied ? (uint32_t)bi : 0xFFFFFFFFu);
-            best = (mx == 0u || mi == 0xFFFFFFFFu) ? 0x7FFFFFFF : (int)mi;
-        }
-        if (mx == 0u) best = 0x7FFFFFFF;
-        if (best == 0x7FFFFFFF) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }  // no selectable child
+        const int best = best_child(bk, bi, k);
+        if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }  // no selectable child
         const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
         s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
         if (lane == 0) path[depth] = first + best;
@@ -799,37 +939,18 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     bool need = false;
     if (kind == K_EXPAND || kind == K_REEXPAND || kind == K_ROOTPASS) {
         BB<NW> black, white;
-        int lplayer;
-        if (kind == K_ROOTPASS) {                                                   // mcts.py:371-381
-            const uint64_t *src = d.aliased ? d.gboard + (size_t)g * 2 * NW : d.nboard + (size_t)g * d.node_cap * 2 * NW;
-            black = bb_uniform_load<NW>(src);
-            white = bb_uniform_load<NW>(src + NW);
-            lplayer = rfl((int)st->root_player);
-        } else {                                                                    // mcts.py:385-391
-            const uint64_t *src = d.aliased ? d.gboard + (size_t)g * 2 * NW
-                                            : d.nboard + ((size_t)g * d.node_cap + parent) * 2 * NW;
-            black = bb_uniform_load<NW>(src);
-            white = bb_uniform_load<NW>(src + NW);
-            const int pplayer = node_player(rfl(nodes[parent].y));
-            // getNextState: place iff legal (yin_yang_game.py:52-58).  In copied mode the action is
-            // one of the parent's legal moves on this very board, so it always places; in aliased
-            // mode the shared board has moved on and the full legality test is required.
-            bool ok = true;
-            if (d.aliased) {
-                bool pre = bb_pre2x2(black, white, gb);
-                BB<NW> m = (pplayer == 1) ? bb_legal(black, white, pre, d.geo, gb) : bb_legal(white, black, pre, d.geo, gb);
-                ok = bb_test(m, action);
-            }
-            if (ok) {
+        const int lplayer = leaf_position<NW>(d, st, g, nodes, kind, parent, action, d.aliased != 0u, black, white);
+        if (d.aliased && kind != K_ROOTPASS) {   // the shared board: the full legality test, then the stone goes onto it
+            const int pplayer = -lplayer;
+            bool pre = bb_pre2x2(black, white, gb);
+            BB<NW> m = (pplayer == 1) ? bb_legal(black, white, pre, d.geo, gb) : bb_legal(white, black, pre, d.geo, gb);
+            if (bb_test(m, action)) {
                 if (pplayer == 1) black = black | bb_bit<NW>(action);
                 else white = white | bb_bit<NW>(action);
-                if (d.aliased) {
-                    uint64_t *dst = d.gboard + (size_t)g * 2 * NW;
-                    bb_store_lane0<NW>(dst, black);
-                    bb_store_lane0<NW>(dst + NW, white);
-                }
+                uint64_t *dst = d.gboard + (size_t)g * 2 * NW;
+                bb_store_lane0<NW>(dst, black);
+                bb_store_lane0<NW>(dst + NW, white);
             }
-            lplayer = -pplayer;
         }
         BB<NW> mask;
         bool term;
@@ -886,16 +1007,8 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             if (slot < 0) slot = (int)at0;                                     // every probed entry is live: replace the first
         }
         if (src == -1) write_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, black, white);
+        leaf_store<NW>(&st->leaf, black, white, mask, lplayer, term, tv);
         if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NW; i++) {
-                st->leaf_board[i] = black.w[i];
-                st->leaf_board[NW + i] = white.w[i];
-                st->leaf_mask[i] = mask.w[i];
-            }
-            st->leaf_player = (int8_t)lplayer;
-            st->leaf_terminal = term;
-            st->leaf_tv = tv;
             st->leaf_src = src;
             st->leaf_ec_slot = slot;
         }
@@ -903,9 +1016,9 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         if (!need && lane == 0) st->ctr[7] += 1;
     }
     if (lane == 0) {
-        st->leaf_kind = (uint8_t)kind;
-        st->leaf_node = node;
-        st->path_len = depth;
+        st->leaf.kind = (uint8_t)kind;
+        st->leaf.node = node;
+        st->leaf.path_len = depth;
         st->ctr[1] += c_levels;
         st->ctr[2] += c_scan;
         if (need) st->ctr[0] += 1;
@@ -915,19 +1028,19 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     }
 }
 
-// ---- expansion + backup: mcts.py:50-91 (expand), 147-156 + 406-412 (update along the path)
+// ---- expansion + backup: mcts.py:50-91 (expand_leaf), 147-156 + 406-412 (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, const float *policy,
                                                  const float *value, const double *noise) {
     GameState *st = d.state + g;
     const int lane = lane_id();
-    const int kind = rfl((int)st->leaf_kind);
+    const int kind = rfl((int)st->leaf.kind);
     if (kind == K_NONE) return;
-    uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
     uint4 *edges = d.edges + (size_t)g * d.edge_cap;
     const int32_t *path = d.path + (size_t)g * d.path_cap;
-    const int depth = rfl(st->path_len);
-    int node = rfl(st->leaf_node);
+    const int depth = rfl(st->leaf.path_len);
+    const int node = rfl(st->leaf.node);
     float v;
     bool v_is_py = false;   // value is a python number (terminal value), not np.float32
     if (kind == K_TERMINAL) {
@@ -936,93 +1049,20 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
     } else if (kind == K_REUSE) {
         v = rflf(__uint_as_float(nodes[node].w));                                   // the np.float32 the evaluator returned for this node
     } else {
+        const int A = d.geo.A;
         const int src = ((d.ec_meta || d.bk_meta) && kind != K_ROOTINIT) ? rfl(st->leaf_src) : -1;
         const bool copy = src != -1;             // evaluation taken from the game's cache (slot src >= 0) or the book (slot -2 - src)
-        const float *cpol = src >= 0 ? d.ec_pol + ((size_t)g * d.ec_cap + src) * d.geo.A
-                                     : copy ? d.bk_pol + (size_t)(-2 - src) * d.geo.A : nullptr;
+        const float *prow = src >= 0 ? d.ec_pol + ((size_t)g * d.ec_cap + src) * A
+                                     : copy ? d.bk_pol + (size_t)(-2 - src) * A : policy + (size_t)g * A;
         v = (kind == K_ROOTINIT) ? 0.0f
             : src >= 0 ? rflf(d.ec_val[(size_t)g * d.ec_cap + src]) : copy ? rflf(d.bk_val[-2 - src]) : rflf(value[g]);
-        if (v != v) {   // a NaN from the evaluator must not enter the statistics: the game stops searching, the error is sticky
-            if (lane == 0) { st->err = st->err_ever = 1; st->leaf_kind = K_NONE; }
+        // a pass node keeps its value (not from the root call of mcts.py:288: that value is discarded and
+        // yy_mcts_expand_root is not given it -- a pass root keeps the value of its first simulation)
+        const bool hold = d.reuse && kind != K_ROOTINIT;
+        if (!expand_leaf<NW>(d, st, g, &st->leaf, path, prow, v, hold, d.aliased != 0u, noise)) {
+            // NaN from the evaluator or a full arena: the game stops searching, the error is sticky
+            if (lane == 0) { st->err = st->err_ever = 1; st->leaf.kind = K_NONE; }
             return;
-        }
-        const int A = d.geo.A;
-        const int lplayer = rfl((int)st->leaf_player);
-        const bool term = rfl((int)st->leaf_terminal) != 0;
-        int n_nodes = rfl(st->n_nodes), n_edges = rfl(st->n_edges);
-        if (kind == K_EXPAND) {
-            if (n_nodes >= (int)d.node_cap) { if (lane == 0) { st->err = st->err_ever = 1; st->leaf_kind = K_NONE; } return; }
-            node = n_nodes++;
-            if (lane == 0) {
-                uint4 *pe = edges + path[depth - 1];
-                pe->w = (pe->w & 0xFF000000u) | (uint32_t)node;
-                st->ctr[5] += 1;
-            }
-        }
-        BB<NW> mask;
-#pragma unroll
-        for (int i = 0; i < NW; i++) mask.w[i] = rfl64(st->leaf_mask[i]);
-        if (!d.aliased) {
-            uint64_t *nb = d.nboard + ((size_t)g * d.node_cap + node) * 2 * NW;
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < 2 * NW; i++) nb[i] = st->leaf_board[i];
-            }
-        }
-        if (term) {                                                                 // mcts.py:63-68
-            if (lane == 0)
-                nodes[node] = make_uint4(0u, node_pack(0, NF_TERMINAL, lplayer), __float_as_uint(st->leaf_tv), __float_as_uint(v));
-        } else {                                                                    // mcts.py:71-89
-            const int k = bb_popc(mask);
-            if (n_edges + k > (int)d.edge_cap) { if (lane == 0) { st->err = st->err_ever = 1; st->leaf_kind = K_NONE; } return; }
-            const float keep = (float)(1.0 - d.eps);
-            // a game whose noise row is all zero over its legal moves drew no noise (a Dirichlet draw
-            // sums to 1): it keeps the raw priors, like add_exploration_noise=False (mcts.py:298)
-            bool mix = false;
-            if (noise) {
-                uint64_t any = 0;
-#pragma unroll
-                for (int j = 0; j < NW; j++) {
-                    const int cell = j * 64 + lane;
-                    const bool nz = ((mask.w[j] >> lane) & 1) && noise[(size_t)g * A + cell] != 0.0;
-                    any |= __ballot(nz);
-                }
-                mix = any != 0;
-            }
-            int base = n_edges;
-            bool bad = false;   // a NaN prior (python: `score > best` is never true for it, select_child returns None and the game raises)
-#pragma unroll
-            for (int j = 0; j < NW; j++) {
-                const int cell = j * 64 + lane;
-                if ((mask.w[j] >> lane) & 1) {
-                    float p = copy ? cpol[cell] : policy[(size_t)g * A + cell];
-                    bad |= (p != p);
-                    if (mix) {                                                      // mcts.py:310-312
-                        const float kp = __fmul_rn(keep, p);
-                        p = (float)__dadd_rn((double)kp, __dmul_rn(d.eps, noise[(size_t)g * A + cell]));
-                    }
-                    edges[base + mbcnt(mask.w[j])] =
-                        make_uint4(__float_as_uint(p), 0u, 0u, CHILD_NONE | ((uint32_t)cell << 24));
-                }
-                base += yy_popc64(mask.w[j]);
-            }
-            if (__ballot(bad)) {
-                if (lane == 0) { st->err = st->err_ever = 1; st->leaf_kind = K_NONE; }
-                return;
-            }
-            if (lane == 0) {
-                // a pass node keeps its value (not from the root call of mcts.py:288: that value is discarded and
-                // yy_mcts_expand_root is not given it -- a pass root keeps the value of its first simulation)
-                const bool hold = d.reuse && k == 0 && kind != K_ROOTINIT;
-                nodes[node] = make_uint4((uint32_t)n_edges, node_pack(k, hold ? NF_HASVALUE : 0u, lplayer), 0u,
-                                         __float_as_uint(v));                       // .w = the evaluator's value of this position
-                st->ctr[3] += (uint64_t)k;
-            }
-            n_edges += k;
-        }
-        if (lane == 0) {
-            st->n_nodes = n_nodes;
-            st->n_edges = n_edges;
         }
         if (d.ec_meta && !copy && kind != K_ROOTINIT) {                            // a fresh evaluation goes into the cache
             const int slot = rfl(st->leaf_ec_slot);
@@ -1036,39 +1076,17 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
                 int stones = 0;
 #pragma unroll
                 for (int i = 0; i < 2 * NW; i++) {
-                    d.ec_key[e * 2 * NW + i] = st->leaf_board[i];
-                    stones += yy_popc64(st->leaf_board[i]);
+                    d.ec_key[e * 2 * NW + i] = st->leaf.board[i];
+                    stones += yy_popc64(st->leaf.board[i]);
                 }
                 d.ec_val[e] = v;
                 d.ec_meta[e] = (st->ec_epoch << 8) | (uint32_t)(stones & 0xFF);
             }
         }
     }
-    if (lane == 0) st->leaf_kind = K_NONE;
+    if (lane == 0) st->leaf.kind = K_NONE;
     if (kind == K_ROOTINIT) return;                                                 // no backup
-    // ---- backup (mcts.py:406-412): edge i leads to the node at depth i+1; the leaf is at `depth`;
-    // players alternate every ply so the sign is the parity of the distance to the leaf.
-    for (int i = lane; i < depth; i += 64) {
-        uint4 *e = edges + path[i];
-        const int dist = depth - (i + 1);
-        const float sv = (dist & 1) ? -v : v;
-        uint4 r = *e;
-        r.y = (uint32_t)((int)r.y + 1);
-        r.z = __float_as_uint(__fadd_rn(__uint_as_float(r.z), sv));
-        *e = r;
-    }
-    if (lane == 0) {
-        const float sv = (depth & 1) ? -v : v;
-        st->root_N += 1;
-        if (st->root_w_is_py && v_is_py && depth == 0) {
-            // terminal root: python float + python number stays a python float (f64)
-            st->root_W_py += (double)((sv == 0.0001f) ? 0.0001 : (sv == -0.0001f ? -0.0001 : (double)sv));
-        } else {
-            const float base = st->root_w_is_py ? (float)st->root_W_py : st->root_W;
-            st->root_W = __fadd_rn(base, sv);
-            st->root_w_is_py = 0;
-        }
-    }
+    backup_path(edges, path, depth, v, v_is_py, st);
 }
 
 template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do_backup, int do_sel,
@@ -1134,35 +1152,19 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
             const int S = (int)wave_uadd(part);                    // sum of the children's N + v (mcts.py:112)
             const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];
             uint32_t bk = 0, bw = 0;
-            int bi = 0x7FFFFFFF;
+            int bi = BEST_NONE;
 #pragma unroll
             for (int t = 0; t < NW; t++) {
                 const int jj = t * 64 + lane;
                 if (jj < k) {
-                    const float P = __uint_as_float(e[t].x), W = __uint_as_float(e[t].z);
-                    const int n = (int)e[t].y + v[t];
+                    const float W = __uint_as_float(e[t].z);
                     const float w = (v[t] > 0) ? __fsub_rn(W, (float)v[t]) : W;
-                    const float t1 = __fmul_rn(d.cpuct, P);
-                    const float t2 = __fmul_rn(t1, sq);
-                    const float u = __fdiv_rn(t2, (float)(1 + n));
-                    const float q = (n > 0) ? __fdiv_rn(w, (float)n) : 0.0f;
-                    const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);
-                    const uint32_t key = f32_key(ucb);
+                    const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e[t].x), (int)e[t].y + v[t], w);
                     if (key > bk) { bk = key; bi = jj; bw = e[t].w; }
                 }
             }
-            const uint32_t mx = wave_umax(bk);
-            const bool tied = (bk == mx) && (bi != 0x7FFFFFFF);
-            int best;
-            if (k <= 64) {
-                const uint64_t tm = __ballot(tied);
-                best = tm ? (int)__ffsll((unsigned long long)tm) - 1 : 0x7FFFFFFF;
-            } else {
-                const uint32_t mi = wave_umin(tied ? (uint32_t)bi : 0xFFFFFFFFu);
-                best = (mi == 0xFFFFFFFFu) ? 0x7FFFFFFF : (int)mi;
-            }
-            if (mx == 0u) best = 0x7FFFFFFF;
-            if (best == 0x7FFFFFFF) { kind = K_NONE; break; }
+            const int best = best_child(bk, bi, k);
+            if (best == BEST_NONE) { kind = K_NONE; break; }
             const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
             if (lane == 0) path[depth] = first + best;
             match = __ballot(vi == best);                          // vi == -1 outside `match`
@@ -1182,37 +1184,13 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
         LeafRec *rec = m.leaves + (size_t)g * K + j;
         if (need) {
             BB<NW> black, white;
-            int lplayer;
-            if (kind == K_ROOTPASS) {
-                const uint64_t *src = d.nboard + (size_t)g * d.node_cap * 2 * NW;
-                black = bb_uniform_load<NW>(src);
-                white = bb_uniform_load<NW>(src + NW);
-                lplayer = rfl((int)st->root_player);
-            } else {                                               // copied boards: the parent's legal move always places
-                const uint64_t *src = d.nboard + ((size_t)g * d.node_cap + parent) * 2 * NW;
-                black = bb_uniform_load<NW>(src);
-                white = bb_uniform_load<NW>(src + NW);
-                const int pplayer = node_player(rfl(nodes[parent].y));
-                if (pplayer == 1) black = black | bb_bit<NW>(action);
-                else white = white | bb_bit<NW>(action);
-                lplayer = -pplayer;
-            }
+            const int lplayer = leaf_position<NW>(d, st, g, nodes, kind, parent, action, false, black, white);
             BB<NW> mask;
             bool term;
             float tv;
             leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
             write_planes<NW>(planes + ((size_t)g * K + j) * 5 * d.geo.A, d.geo, black, white);
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < NW; i++) {
-                    rec->board[i] = black.w[i];
-                    rec->board[NW + i] = white.w[i];
-                    rec->mask[i] = mask.w[i];
-                }
-                rec->player = (int8_t)lplayer;
-                rec->terminal = term;
-                rec->tv = tv;
-            }
+            leaf_store<NW>(rec, black, white, mask, lplayer, term, tv);
         }
         if (lane == 0) {
             rec->kind = (uint8_t)kind;
@@ -1237,7 +1215,7 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
 }
 
 // expansion + backup of the K_eff descents of the last step, in descent order: the first occurrence of a leaf expands it
-// exactly like do_expand_backup, then every descent backs its value up along its own path
+// (expand_leaf), then every descent backs its value up along its own path (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const MultiDev &m, const int g, const float *policy,
                                                        const float *value, const double *noise) {
@@ -1247,9 +1225,8 @@ __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const M
     int32_t *ms = m.mst + 2 * g;
     const int nl = rfl(ms[1]);
     if (nl == 0) return;
-    uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
     uint4 *edges = d.edges + (size_t)g * d.edge_cap;
-    const int A = d.geo.A;
     for (int j = 0; j < nl; j++) {
         const LeafRec *rec = m.leaves + (size_t)g * K + j;
         const int kind = rfl((int)rec->kind);
@@ -1257,114 +1234,23 @@ __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const M
         const int dup = rfl(rec->dup);
         const int32_t *path = d.path + ((size_t)g * K + j) * d.path_cap;
         const size_t row = (size_t)g * K + (dup >= 0 ? dup : j);
-        int node = rfl(rec->node);
         float v;
         bool v_is_py = false;
         if (kind == K_TERMINAL) {
-            v = rflf(__uint_as_float(nodes[node].z));
+            v = rflf(__uint_as_float(nodes[rfl(rec->node)].z));
             v_is_py = true;
         } else if (dup >= 0) {
             v = rflf(value[row]);                                  // checked when the first occurrence was expanded
         } else {
             v = (kind == K_ROOTINIT) ? 0.0f : rflf(value[row]);
-            bool fail = (v != v);
-            int n_nodes = rfl(st->n_nodes), n_edges = rfl(st->n_edges);
-            if (!fail && kind == K_EXPAND) {
-                if (n_nodes >= (int)d.node_cap) fail = true;
-                else {
-                    node = n_nodes++;
-                    if (lane == 0) {
-                        uint4 *pe = edges + path[depth - 1];
-                        pe->w = (pe->w & 0xFF000000u) | (uint32_t)node;
-                        st->ctr[5] += 1;
-                    }
-                }
-            }
-            BB<NW> mask;
-#pragma unroll
-            for (int i = 0; i < NW; i++) mask.w[i] = rfl64(rec->mask[i]);
-            const int lplayer = rfl((int)rec->player);
-            if (!fail) {
-                uint64_t *nb = d.nboard + ((size_t)g * d.node_cap + node) * 2 * NW;
-                if (lane == 0) {
-#pragma unroll
-                    for (int i = 0; i < 2 * NW; i++) nb[i] = rec->board[i];
-                }
-            }
-            if (!fail && rfl((int)rec->terminal)) {
-                if (lane == 0) nodes[node] = make_uint4(0u, node_pack(0, NF_TERMINAL, lplayer), __float_as_uint(rec->tv), __float_as_uint(v));
-            } else if (!fail) {
-                const int k = bb_popc(mask);
-                if (n_edges + k > (int)d.edge_cap) fail = true;
-                else {
-                    const float keep = (float)(1.0 - d.eps);
-                    bool mix = false;
-                    if (noise) {
-                        uint64_t any = 0;
-#pragma unroll
-                        for (int t = 0; t < NW; t++) {
-                            const int cell = t * 64 + lane;
-                            const bool nz = ((mask.w[t] >> lane) & 1) && noise[(size_t)g * A + cell] != 0.0;
-                            any |= __ballot(nz);
-                        }
-                        mix = any != 0;
-                    }
-                    int base = n_edges;
-                    bool bad = false;
-#pragma unroll
-                    for (int t = 0; t < NW; t++) {
-                        const int cell = t * 64 + lane;
-                        if ((mask.w[t] >> lane) & 1) {
-                            float p = policy[row * A + cell];
-                            bad |= (p != p);
-                            if (mix) {
-                                const float kp = __fmul_rn(keep, p);
-                                p = (float)__dadd_rn((double)kp, __dmul_rn(d.eps, noise[(size_t)g * A + cell]));
-                            }
-                            edges[base + mbcnt(mask.w[t])] = make_uint4(__float_as_uint(p), 0u, 0u, CHILD_NONE | ((uint32_t)cell << 24));
-                        }
-                        base += yy_popc64(mask.w[t]);
-                    }
-                    if (__ballot(bad)) fail = true;
-                    else {
-                        if (lane == 0) {
-                            nodes[node] = make_uint4((uint32_t)n_edges, node_pack(k, 0u, lplayer), 0u, __float_as_uint(v));
-                            st->ctr[3] += (uint64_t)k;
-                        }
-                        n_edges += k;
-                    }
-                }
-            }
-            if (fail) {   // NaN from the evaluator or a full arena: the game stops, the error is sticky
+            if (!expand_leaf<NW>(d, st, g, rec, path, policy + row * d.geo.A, v, false, false, noise)) {
+                // NaN from the evaluator or a full arena: the game stops, the error is sticky
                 if (lane == 0) { st->err = st->err_ever = 1; ms[1] = 0; }
                 return;
             }
-            if (lane == 0) {
-                st->n_nodes = n_nodes;
-                st->n_edges = n_edges;
-            }
         }
         if (kind == K_ROOTINIT) break;                             // no backup
-        for (int i = lane; i < depth; i += 64) {                   // mcts.py:406-412, as in do_expand_backup
-            uint4 *e = edges + path[i];
-            const int dist = depth - (i + 1);
-            const float sv = (dist & 1) ? -v : v;
-            uint4 r = *e;
-            r.y = (uint32_t)((int)r.y + 1);
-            r.z = __float_as_uint(__fadd_rn(__uint_as_float(r.z), sv));
-            *e = r;
-        }
-        if (lane == 0) {
-            const float sv = (depth & 1) ? -v : v;
-            st->root_N += 1;
-            if (st->root_w_is_py && v_is_py && depth == 0) {
-                st->root_W_py += (double)((sv == 0.0001f) ? 0.0001 : (sv == -0.0001f ? -0.0001 : (double)sv));
-            } else {
-                const float base = st->root_w_is_py ? (float)st->root_W_py : st->root_W;
-                st->root_W = __fadd_rn(base, sv);
-                st->root_w_is_py = 0;
-            }
-        }
+        backup_path(edges, path, depth, v, v_is_py, st);
         __syncthreads();   // the next descent's backup and expansion read what this one wrote
     }
     if (lane == 0) ms[1] = 0;
@@ -1741,191 +1627,6 @@ extern "C" int yy_mcts_reset_counters(yy_mcts *c, yy_stream_t s) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
     MctsDev d = make_dev(c);
     hipLaunchKernelGGL(k_reset_counters, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, d);
-    HIP_TRY(hipGetLastError());
-    return YY_OK;
-}
-
-// =============================================================================== evaluator epilogue
-// Fused bias + residual + ReLU over a channels-last bf16 activation tensor, in place:
-//     x[r, c] = relu( x[r, c] + bias[c] (+ residual[r, c]) )
-// This replaces the 3-4 separate elementwise passes PyTorch/MIOpen run after every convolution of
-// the policy/value tower (bias add, residual add, clamp) by ONE pass: 16-B loads/stores per lane,
-// f32 arithmetic, one bf16 rounding.  HBM-bound: (2 or 3) * rows * C * 2 bytes per launch.
-typedef __attribute__((ext_vector_type(8))) unsigned short us8;
-
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((uint32_t)h) << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) {   // round-to-nearest-even, NaN stays NaN
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x40u);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-template <bool HAS_RES, bool RELU, bool FIXED>
-__global__ void __launch_bounds__(256) k_bias_act(us8 *x, const float *bias, const us8 *res, size_t n_vec, int cvec) {
-    // cvec = C / 8 vectors per row.  FIXED: the grid stride is a multiple of cvec, so a lane keeps the
-    // same 8 channels for its whole grid-stride walk and the bias slice lives in registers.
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    float b[8];
-    if (FIXED) {
-        const float4 *bp = reinterpret_cast<const float4 *>(bias + (tid % (size_t)cvec) * 8);
-        const float4 b0 = bp[0], b1 = bp[1];
-        b[0] = b0.x; b[1] = b0.y; b[2] = b0.z; b[3] = b0.w;
-        b[4] = b1.x; b[5] = b1.y; b[6] = b1.z; b[7] = b1.w;
-    }
-    for (size_t i = tid; i < n_vec; i += stride) {
-        if (!FIXED) {
-            const int cb = (int)(i % (size_t)cvec) * 8;
-#pragma unroll
-            for (int j = 0; j < 8; j++) b[j] = bias[cb + j];
-        }
-        const us8 v = x[i];
-        us8 r;
-        if (HAS_RES) r = res[i];
-        us8 o;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            float f = bf2f(v[j]) + b[j];
-            if (HAS_RES) f += bf2f(r[j]);
-            if (RELU) f = fmaxf(f, 0.0f);
-            o[j] = f2bf(f);
-        }
-        x[i] = o;
-    }
-}
-
-template <bool FIXED>
-static void launch_bias_act(us8 *xv, const float *bias, const us8 *rv, size_t n_vec, int cvec, int relu, unsigned blocks,
-                            hipStream_t st) {
-    if (rv) {
-        if (relu) k_bias_act<true, true, FIXED><<<dim3(blocks), dim3(256), 0, st>>>(xv, bias, rv, n_vec, cvec);
-        else k_bias_act<true, false, FIXED><<<dim3(blocks), dim3(256), 0, st>>>(xv, bias, rv, n_vec, cvec);
-    } else {
-        if (relu) k_bias_act<false, true, FIXED><<<dim3(blocks), dim3(256), 0, st>>>(xv, bias, rv, n_vec, cvec);
-        else k_bias_act<false, false, FIXED><<<dim3(blocks), dim3(256), 0, st>>>(xv, bias, rv, n_vec, cvec);
-    }
-}
-
-extern "C" int yy_nn_bias_act_bf16(void *x, const float *bias, const void *residual, int64_t rows, int C, int relu,
-                                   yy_stream_t s) {
-    if (rows == 0) return YY_OK;
-    if (!x || !bias || rows < 0 || C <= 0) return set_err(YY_E_INVALID, "bad argument%s%s");
-    if (C % 8) return set_err(YY_E_UNSUPPORTED, "channels must be a multiple of 8%s%s");
-    const int cvec = C / 8;
-    const size_t n_vec = (size_t)rows * (size_t)cvec;
-    size_t blocks = (n_vec + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;          // ~8 blocks per CU, grid-stride the rest
-    const bool fixed = (256 % cvec) == 0;            // grid stride (blocks*256) is then a multiple of cvec
-    if (fixed) launch_bias_act<true>((us8 *)x, bias, (const us8 *)residual, n_vec, cvec, relu, (unsigned)blocks, (hipStream_t)s);
-    else launch_bias_act<false>((us8 *)x, bias, (const us8 *)residual, n_vec, cvec, relu, (unsigned)blocks, (hipStream_t)s);
-    HIP_TRY(hipGetLastError());
-    return YY_OK;
-}
-
-// Head finish (neural_network.py:115, 120-121 + predict's softmax :152): row g of h holds the A policy logits
-// followed by the H hidden activations of value_fc1 (bias already added by the GEMM, bf16).  One wave per
-// row: policy = softmax(logits) in f32; value = tanh(sum_j relu(hidden_j) * w2_j + b2).
-__global__ void __launch_bounds__(64) k_head_finish(const unsigned short *__restrict__ h, int A, int H,
-                                                    const float *__restrict__ w2, const float *__restrict__ b2,
-                                                    float *__restrict__ policy, float *__restrict__ value) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const unsigned short *row = h + (size_t)g * (A + H);
-    float mx = -INFINITY;
-    for (int a = lane; a < A; a += 64) mx = fmaxf(mx, bf2f(row[a]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float sum = 0.0f;
-    for (int a = lane; a < A; a += 64) sum += expf(bf2f(row[a]) - mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    for (int a = lane; a < A; a += 64) policy[(size_t)g * A + a] = expf(bf2f(row[a]) - mx) / sum;
-    float acc = 0.0f;
-    for (int j = lane; j < H; j += 64) acc += fmaxf(bf2f(row[A + j]), 0.0f) * w2[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) value[g] = tanhf(acc + b2[0]);
-}
-
-// float32 head finish (evaluator modes "f16x3" / float32 towers): logits f32 [Gd, A] and value_fc1 outputs f32 [Gd, H]
-// (bias added, no ReLU yet) of DENSE row i -> policy[g] = softmax(logits[i]), value[g] = tanh(relu(hidden[i]) . w2 + b2)
-// with g = rows ? rows[i] : i; blocks i >= *n_rows exit (the rows a compacted launch did not evaluate).
-// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
-// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
-__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
-
-__global__ void __launch_bounds__(64) k_head_finish_f32(const float *__restrict__ logits, const float *__restrict__ hidden,
-                                                        int A, int H, const float *__restrict__ w2,
-                                                        const float *__restrict__ b2, const int32_t *__restrict__ rows,
-                                                        const int32_t *__restrict__ n_rows, float *__restrict__ policy,
-                                                        float *__restrict__ value) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (n_rows && i >= *n_rows) return;
-    const int g = rows ? rows[i] : i;
-    const float *row = logits + (size_t)i * A;
-    float mx = -INFINITY;
-    for (int a = lane; a < A; a += 64) mx = fmaxf(mx, row[a]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float sum = 0.0f;
-    for (int a = lane; a < A; a += 64) sum += expf(row[a] - mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    for (int a = lane; a < A; a += 64) policy[(size_t)g * A + a] = expf(row[a] - mx) / sum;
-    const float *hr = hidden + (size_t)i * H;
-    float acc = 0.0f;
-    for (int j = lane; j < H; j += 64) acc += relu_keep_nan(hr[j]) * w2[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) value[g] = tanhf(acc + b2[0]);
-}
-
-extern "C" int yy_nn_head_finish_f32(const float *logits, const float *hidden, int G, int A, int H, const float *w2,
-                                     const float *b2, const int32_t *rows, const int32_t *n_rows, float *policy, float *value,
-                                     yy_stream_t s) {
-    if (G == 0) return YY_OK;
-    if (!logits || !hidden || !w2 || !b2 || !policy || !value || G < 0 || A <= 0 || H <= 0 || (rows && !n_rows))
-        return set_err(YY_E_INVALID, "bad argument%s%s");
-    k_head_finish_f32<<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(logits, hidden, A, H, w2, b2, rows, n_rows, policy, value);
-    HIP_TRY(hipGetLastError());
-    return YY_OK;
-}
-
-// Leaf-batch compaction: rows[0 .. *n) = the indices g with flags[g] != 0, ascending; one 1024-thread workgroup.
-__global__ void __launch_bounds__(1024) k_compact_rows(const uint8_t *__restrict__ flags, int G, int32_t *__restrict__ rows,
-                                                       int32_t *__restrict__ n) {
-    __shared__ int wsum[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int per = (G + 1023) / 1024, lo = min(t * per, G), hi = min(lo + per, G);
-    int cnt = 0;
-    for (int g = lo; g < hi; g++) cnt += flags[g] != 0;
-    int incl = cnt;                                             // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; w++) base += wsum[w];
-    int pos = base + incl - cnt;
-    for (int g = lo; g < hi; g++)
-        if (flags[g] != 0) rows[pos++] = g;
-    if (t == 1023) *n = base + incl;
-}
-
-extern "C" int yy_compact_rows(const uint8_t *flags, int G, int32_t *rows, int32_t *n, yy_stream_t s) {
-    if (!flags || !rows || !n || G < 0) return set_err(YY_E_INVALID, "bad argument%s%s");
-    k_compact_rows<<<dim3(1), dim3(1024), 0, (hipStream_t)s>>>(flags, G, rows, n);
-    HIP_TRY(hipGetLastError());
-    return YY_OK;
-}
-
-extern "C" int yy_nn_head_finish_bf16(const void *h, int G, int A, int H, const float *w2, const float *b2, float *policy,
-                                      float *value, yy_stream_t s) {
-    if (G == 0) return YY_OK;
-    if (!h || !w2 || !b2 || !policy || !value || G < 0 || A <= 0 || H <= 0) return set_err(YY_E_INVALID, "bad argument%s%s");
-    k_head_finish<<<dim3(G), dim3(64), 0, (hipStream_t)s>>>((const unsigned short *)h, A, H, w2, b2, policy, value);
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }

@@ -31,7 +31,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace fch {
 

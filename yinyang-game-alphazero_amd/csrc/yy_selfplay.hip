@@ -22,7 +22,7 @@
 
 #include "../../include/yy_engine.h"
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace sp {
 

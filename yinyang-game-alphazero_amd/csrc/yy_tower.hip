@@ -52,7 +52,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define YY_TOWER_TB1_MAX_G 256   // <= one 1-board workgroup per CU
 #define YY_TOWER_TB2_MAX_G 512   // <= one 2-board workgroup per CU
 
-extern "C" int yy_tower_set_err(int code, const char *msg);   // defined in yy_engine.hip
+#include "yy_common.h"
 
 __device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
     bf16x2 t;

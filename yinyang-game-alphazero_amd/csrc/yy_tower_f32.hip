@@ -32,7 +32,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #define F_ZERO_OFF (F_BIAS_OFF + F_MAX_LAYERS * F_CH * 4)
 #define F_LDS_BYTES (F_ZERO_OFF + 512)                        // 161792
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace tf32 {
 

@@ -45,13 +45,9 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace tg {
-
-// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
-// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
-__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
 
 template <int NW_, int NB_, int D_, bool RB_> struct Geo {
     static constexpr int NW = NW_, NB = NB_, D = D_, CH = 32 * NW_, NCOL = 16 * NB_;

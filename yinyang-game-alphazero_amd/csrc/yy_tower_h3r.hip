@@ -43,13 +43,9 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 #define HR_CHUNK_BYTES 16384
 #define HR_MAX_LAYERS 22
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace thr {
-
-// ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
-// -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
-__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
 
 template <int R_, int TB_, int D_, int NV_> struct Geo {
     static constexpr int R = R_, TB = TB_, D = D_, NV = NV_, CELLS = R_ * R_, NCOL = TB_ * R_ * R_, CT = (NCOL + 31) / 32;

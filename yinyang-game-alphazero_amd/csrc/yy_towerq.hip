@@ -38,7 +38,7 @@ typedef __attribute__((ext_vector_type(2))) short s16x2;
 #define TQ_NSLOT 4
 #define TQ_MAX_LAYERS 23
 
-extern "C" int yy_tower_set_err(int code, const char *msg);
+#include "yy_common.h"
 
 namespace tq {
 

@@ -1,7 +1,7 @@
 """Torch-tensor level binding of the HIP hot path (include/yy_engine.h).
 
 PyTorch is plumbing here: it owns the HBM tensors and the stream; every operation below is a
-hand-written gfx950 kernel in csrc/yy_engine.hip.  No CPU fallback exists: tensors must be on a
+hand-written gfx950 kernel in csrc/*.hip.  No CPU fallback exists: tensors must be on a
 ROCm device and the extension must be built, otherwise these functions raise.
 """
 import ctypes as ct
