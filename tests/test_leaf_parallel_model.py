@@ -7,20 +7,20 @@ import oracle_lib as O
 import leaf_parallel_model as M
 
 
-def random_root(R, C, plies, seed):
+def random_root(R, C, plies, seed, flags=0):
     """A position after `plies` random legal moves from the empty board (fewer when the game ends first), side to move."""
     rng = np.random.default_rng(seed)
     board, player = np.zeros((1, R, C), np.int8), np.ones(1, np.int8)
     for _ in range(plies):
-        m = O.valid_mask(board, player)[0]
-        if not m.any() or O.game_ended(board, player)[0] != 0:
+        m = O.valid_mask(board, player, flags)[0]
+        if not m.any() or O.game_ended(board, player, flags)[0] != 0:
             break
-        board, player, _ = O.next_state(board, player, np.array([rng.choice(np.flatnonzero(m))], np.int32))
+        board, player, _ = O.next_state(board, player, np.array([rng.choice(np.flatnonzero(m))], np.int32), flags)
     return board[0], int(player[0])
 
 
-def dirichlet_noise(board, player, seed, alpha=0.3):
-    legal = np.flatnonzero(O.valid_mask(board[None], [player])[0])
+def dirichlet_noise(board, player, seed, alpha=0.3, flags=0):
+    legal = np.flatnonzero(O.valid_mask(board[None], [player], flags)[0])
     nz = np.zeros(board.size)
     if len(legal):
         nz[legal] = np.random.default_rng(seed).dirichlet([alpha] * len(legal))
@@ -96,6 +96,15 @@ def one_move_root():
     raise AssertionError("no position with one legal move found")
 
 
+def terminal_root(R=4, C=4):
+    """A finished game: random play until the game has ended."""
+    for seed in range(400):
+        board, player = random_root(R, C, R * C + 2, seed)
+        if O.game_ended(board[None], [player])[0] != 0:
+            return board, player
+    raise AssertionError("no terminal root found")
+
+
 def test_one_legal_move_produces_duplicates():
     board, player = one_move_root()
     trace = []
@@ -116,3 +125,100 @@ def test_root_visits_equal_num_sims(K):
         if O.game_ended(board[None], [player])[0] == 0 and O.valid_mask(board[None], [player])[0].any():
             assert r.counts.sum() == sims
         assert r.evals <= sims
+
+
+# ---------------------------------------------------------------------------- trace boards, counters, and the GPU matrix
+@pytest.mark.parametrize("R,C,plies,sims", CASES)
+def test_k1_traced_boards_are_the_oracles_leaves(R, C, plies, sims):
+    """The boards of the flagged rows in call order are the boards the C oracle evaluated (it does not log the root call)."""
+    for seed in range(2):
+        board, player = random_root(R, C, plies, seed)
+        noise = dirichlet_noise(board, player, 100 + seed) if seed else None
+        want = O.search_hash(board, player, sims, 1, 10, 11, noise=noise, leaf_cap=sims)
+        trace = []
+        got = M.search(board, player, sims, 1, 10, 11, noise=noise, trace=trace)
+        leaves = [d.board for step in trace for d in step if d.needs_eval]
+        assert all(len(step) == 1 for step in trace)
+        assert len(leaves) == got.evals == want.n_evals == len(want.leaves) > 0
+        assert np.array_equal(np.stack(leaves), want.leaves)
+        for step in trace:
+            for d in step:
+                assert d.needs_eval == (d.kind != M.TERMINAL) and (d.board is None) == (not d.needs_eval)
+                assert d.player is None or d.player == (player if len(d.actions) % 2 == 0 else -player)
+
+
+def tree_recount(root):
+    """levels, children_created, nodes below the root -- from the final tree alone"""
+    levels = created = nodes = 0
+    stack = [root]
+    while stack:
+        n = stack.pop()
+        created += len(n.edges)
+        for e in n.edges:
+            levels += e.N
+            if e.child is not None:
+                nodes += 1
+                stack.append(e.child)
+    return levels, created, nodes
+
+
+@pytest.mark.parametrize("K", [1, 2, 8, 32])
+def test_counter_identities(K):
+    for (R, C, plies, sims) in [(3, 3, 2, 40), (4, 4, 9, 60), (4, 4, 12, 37), (8, 8, 6, 101), (12, 12, 0, 70)]:
+        for seed in range(3):
+            board, player = random_root(R, C, plies, seed)
+            trace = []
+            r = M.search(board, player, sims, K, trace=trace)
+            levels, created, nodes = tree_recount(r.root)
+            assert r.levels == levels == sum(len(d.actions) for step in trace for d in step)
+            assert r.children_created == created                      # every node with children, the root included
+            assert r.nodes == nodes                                   # the root is not counted
+            kinds = [d for step in trace for d in step]
+            assert r.terminal_revisits == sum(d.kind == M.TERMINAL for d in kinds)
+            assert r.duplicates == sum(d.dup >= 0 for d in kinds)
+            assert r.evals + r.terminal_revisits + r.duplicates == r.root_visits == sims
+            assert r.evals == sum(d.needs_eval for d in kinds)
+            assert r.children_scanned >= r.levels and (r.levels == 0) == (r.children_scanned == 0)
+
+
+@pytest.fixture(scope="module")
+def gpu_matrix():
+    import test_gpu_leaf_parallel_trace as T                          # the case list of the device tests, nothing of the GPU
+    return T
+
+
+@pytest.mark.parametrize("mutant", list(M.MUTANTS))
+def test_gpu_matrix_catches_every_mutant(gpu_matrix, mutant):
+    """Each deliberately broken rule differs from the true model, on at least one case of the GPU matrix, in something the
+    device test compares (row flags, boards of flagged rows, root arrays, counters)."""
+    T = gpu_matrix
+    for name in T.MATRIX:
+        if T.MATRIX[name]["K"] == 1:
+            continue
+        diff = T.differences(T.model_observables(name, mutant), T.model_observables(name))
+        if diff:
+            print(f"{mutant} ({M.MUTANTS[mutant]}): caught by {name}: {diff[0][:90]}")
+            return
+    raise AssertionError(f"no case of the GPU matrix tells the mutant {mutant} from the model: add a case")
+
+
+def test_gpu_matrix_holds_every_leaf_kind(gpu_matrix):
+    T = gpu_matrix
+    seen, deep_terminal_k32 = {}, 0
+    for name, c in T.MATRIX.items():
+        if c["K"] < 8:
+            continue
+        boards, players, noise = T.case_roots(name)
+        for _, trace in T.run_model(boards, players, noise, c["sims"], c["K"], c["cpuct"], int(c["rowcol"])):
+            for d in (d for step in trace for d in step):
+                kind = "terminal root" if d.kind == M.TERMINAL and not d.actions else d.kind
+                seen.setdefault(kind, name)
+                if d.dup >= 0:
+                    seen.setdefault("duplicate", name)
+                deep_terminal_k32 += c["K"] == 32 and d.kind == M.TERMINAL and len(d.actions) >= 1
+    print(seen, deep_terminal_k32)
+    assert set(seen) == {M.EXPAND, M.REEXPAND, M.ROOTPASS, M.TERMINAL, "terminal root", "duplicate"}
+    assert deep_terminal_k32 >= 1
+    nw = {-(-c["R"] * c["C"] // 64) for c in T.MATRIX.values()}
+    assert nw == {1, 2, 3}                                            # every instantiation of the tree kernels
+    assert {1, 64} <= {c["K"] for c in T.MATRIX.values()}
