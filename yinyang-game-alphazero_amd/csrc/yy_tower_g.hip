@@ -23,6 +23,8 @@
 //   * activation fragments are refreshed IN PLACE, block by block, right after their last use (the next chunk's fragment of
 //     column block nb is read while the MFMAs of block nb + 1 run): 8*NB registers instead of 16*NB.
 //   * bias rows come from scalar loads (no LDS table): NB = 9 with the f32 residual parked in LDS needs 154 of the 160 KB.
+//   * k_tower_g (one wave per 32-channel slice) and k_tower_g22 (2x2 wave grid of the 8x8 form, further down) compute the same bits
+//     from ONE copy of every shared sequence: stage_planes, mma_split, for_each_tap, epilogue_quad, heads_tail, store_activations.
 //   * ROW-ALIGNED form (RB, boards * C == 16 and NB == R, e.g. 8x8 with two boards): column nb*16 + n is row nb of board n / C,
 //     x = n % C, so a row shift is a whole block.  Block 0 then reads only the zero rows at the three dy = -1 taps and block
 //     NB - 1 at the three dy = +1 taps: those 6 of the 9 * NB (tap, block) pairs of every channel group are dropped at compile
@@ -77,16 +79,16 @@ __device__ __forceinline__ f32x2 join_pair(const uint32_t hi, const uint32_t lo)
     return h + l;
 }
 
-// this wave's fragments of one weight chunk: [M block 2]{hi, lo}, 16 registers
-struct WChunk {
-    f16x8 h[2], l[2];
+// this wave's fragments of one weight chunk: [M block MB]{hi, lo}, 8 * MB registers (k_tower_g: MB = 2, k_tower_g22: MB = 4)
+template <int MB> struct WChunk {
+    f16x8 h[MB], l[MB];
 };
 // The four 1 KB fragment loads of a chunk: wbase = weights + chunk * CHUNK_BYTES (uniform), voff = wave * 4096 + lane * 16.
 // Plain loads that the compiler counts itself: it waits for a ring entry with a counted vmcnt (the 4 * (D - 1) younger loads
 // stay in flight) and a sched_group_barrier keeps the refill right behind the chunk that freed the entry.  (yy_tower_h3r.hip
 // issues these loads from inline asm with a hand-counted vmcnt: under register pressure the compiler then copies or spills
 // the destination registers BEFORE the data has landed -- the failure this form cannot have.)
-__device__ __forceinline__ void load_w(WChunk &w, const unsigned char *wbase, uint32_t voff) {
+__device__ __forceinline__ void load_w(WChunk<2> &w, const unsigned char *wbase, uint32_t voff) {
     const u32x4 *p = (const u32x4 *)(wbase + voff);
     w.h[0] = __builtin_bit_cast(f16x8, p[0]);
     w.l[0] = __builtin_bit_cast(f16x8, p[64]);
@@ -148,40 +150,53 @@ template <class GEO> constexpr bool off_board(int tap, int nb) {
 // nb its slot takes the NEXT chunk's fragment of block nb, i.e. a fragment is requested a whole chunk (6 * NB MFMAs) before its use
 // and 8 * NB registers hold activations.  (A shorter rotating window of 3-4 blocks -- 24-32 registers -- was the first form of this
 // kernel; with one scheduling region per chunk the full window measures 1.8 % faster at NB = 8 and still fits at NB = 9.)
-template <int NB> struct XWin {
-    static constexpr int P = NB;
+template <int P> struct XWin {
     f16x8 h[P], l[P];
 };
 template <class GEO> __device__ __forceinline__ void load_x1(XWin<GEO::NB> &f, int slot, const unsigned char *lds, uint32_t cb) {
     f.h[slot] = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + cb));
     f.l[slot] = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + cb + GEO::PART_BYTES));
 }
-// acc1 += w_hi * x_hi ;  acc2 += w_lo * x_hi + w_hi * x_lo for the two M blocks of one column block (6 MFMAs).  Two
+// acc1 += w_hi * x_hi ;  acc2 += w_lo * x_hi + w_hi * x_lo for a wave's MB M blocks of one column block (3 * MB MFMAs).  Two
 // accumulators because every MFMA rounds its accumulator once: the large sum is rounded once per k-step (as in an f32 dot
-// product) and the 2^-11-times-smaller corrections round among themselves.
-template <bool ZERO>
-__device__ __forceinline__ void mma6(f32x4 (&acc1)[2], f32x4 (&acc2)[2], const WChunk &w, const f16x8 xh, const f16x8 xl) {
+// product) and the 2^-11-times-smaller corrections round among themselves.  The MFMA order inside an M block is the bit contract.
+template <int MB, bool ZERO>
+__device__ __forceinline__ void mma_split(f32x4 (&acc1)[MB], f32x4 (&acc2)[MB], const WChunk<MB> &w, const f16x8 xh, const f16x8 xl) {
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int mb = 0; mb < 2; mb++) {
+    for (int mb = 0; mb < MB; mb++) {
         const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.l[mb], xh, ZERO ? z : acc2[mb], 0, 0, 0);
         acc1[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[mb], xh, ZERO ? z : acc1[mb], 0, 0, 0);
         acc2[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[mb], xl, a, 0, 0, 0);
     }
 }
+// The nine taps of one input-channel group as compile-time constants: step(tap, starts the sums, LDS base of this chunk, of the
+// chunk after it).  zt: only the layer's first chunk starts the sums; the group's last tap prefetches from the next group (nxt).
+template <class STEP, class ZT>
+__device__ __forceinline__ void for_each_tap(STEP &step, ZT zt, const unsigned char *cur, const unsigned char *nxt) {
+    step(std::integral_constant<int, 0>{}, zt, cur, cur);
+    step(std::integral_constant<int, 1>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 2>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 3>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 4>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 5>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 6>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 7>{}, std::false_type{}, cur, cur);
+    step(std::integral_constant<int, 8>{}, std::false_type{}, cur, nxt);
+}
 
 // One chunk = tap J of input-channel group kq: 6 * NB MFMAs.  lds_cur / lds_next = LDS base + the channel-group offset of this
 // chunk / of the chunk after it (the layer's last chunk prefetches in-bounds bytes nobody uses).
 template <class GEO, int J, bool ZERO>
-__device__ __forceinline__ void run_chunk(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc2)[GEO::NB][2], const WChunk &w, XWin<GEO::NB> &X,
+__device__ __forceinline__ void run_chunk(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc2)[GEO::NB][2], const WChunk<2> &w, XWin<GEO::NB> &X,
                                           const unsigned char *lds_cur, const unsigned char *lds_next, int crs, const LaneGeo<GEO> &geo) {
-    constexpr int NB = GEO::NB, P = XWin<NB>::P;
+    constexpr int NB = GEO::NB, P = NB;   // P: window length
     static_assert(!GEO::RB || P == NB, "the row-aligned skips assume the full window");
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) {
         // off-board pairs (row-aligned form): neither the MFMAs nor the fragment read that would feed them
         const bool mma = !off_board<GEO>(J, nb), ld = nb + P < NB || !off_board<GEO>((J + 1) % 9, nb + P - NB);
-        if (mma) mma6<ZERO>(acc1[nb], acc2[nb], w, X.h[nb % P], X.l[nb % P]);
+        if (mma) mma_split<2, ZERO>(acc1[nb], acc2[nb], w, X.h[nb % P], X.l[nb % P]);
         if (nb + P < NB) load_x1<GEO>(X, nb % P, lds_cur, tap_addr<GEO, J>(nb + P, crs, geo));
         else if (ld) load_x1<GEO>(X, nb % P, lds_next, tap_addr<GEO, (J + 1) % 9>(nb + P - NB, crs, geo));
         if (mma) __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
@@ -193,10 +208,10 @@ __device__ __forceinline__ void run_chunk(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc
 // tap % D (compile-time).  After its last use a ring entry is refilled with the chunk D further down the stream (the next
 // group / the next layer).  Weight stream order: [layer][kq][tap].
 template <class GEO, bool STEM>
-__device__ __forceinline__ void run_layer(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc2)[GEO::NB][2], WChunk (&W)[GEO::D], const unsigned char *lds,
+__device__ __forceinline__ void run_layer(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc2)[GEO::NB][2], WChunk<2> (&W)[GEO::D], const unsigned char *lds,
                                           const unsigned char *weights, uint32_t voff, int &chunk, int n_tower, int crs,
                                           const LaneGeo<GEO> &geo) {
-    constexpr int KQ = STEM ? 1 : GEO::NW, NB = GEO::NB, D = GEO::D, P = XWin<NB>::P;
+    constexpr int KQ = STEM ? 1 : GEO::NW, NB = GEO::NB, D = GEO::D, P = NB;
     XWin<NB> X;
 #pragma unroll
     for (int nb = 0; nb < P; nb++)
@@ -216,49 +231,20 @@ __device__ __forceinline__ void run_layer(f32x4 (&acc1)[GEO::NB][2], f32x4 (&acc
         __builtin_amdgcn_sched_barrier(0);
         chunk++;
     };
-    auto taps = [&](auto zt, const unsigned char *cur, const unsigned char *nxt) {
-        step(std::integral_constant<int, 0>{}, zt, cur, cur);              // zt: the layer's first chunk starts the sums
-        step(std::integral_constant<int, 1>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 2>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 3>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 4>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 5>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 6>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 7>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 8>{}, std::false_type{}, cur, nxt);
-    };
-    taps(std::true_type{}, lds, lds + 64);                                 // channel group 0, peeled: no zero / non-zero branch
+    for_each_tap(step, std::true_type{}, lds, lds + 64);                   // channel group 0, peeled: no zero / non-zero branch
 #pragma unroll 1
-    for (int kq = 1; kq < KQ; kq++) taps(std::false_type{}, lds + kq * 64, lds + (kq + 1) * 64);
+    for (int kq = 1; kq < KQ; kq++) for_each_tap(step, std::false_type{}, lds + kq * 64, lds + (kq + 1) * 64);
 }
 
-template <int NW_, int NB_, int D_, bool RB_>
-__global__ void __launch_bounds__(64 * NW_, 1)
-k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ weights, const unsigned char *__restrict__ head_w,
-          const float *__restrict__ bias, const float *__restrict__ head_bias, float *__restrict__ out, float *__restrict__ out_heads,
-          const int *__restrict__ rows, const int *__restrict__ n_rows, int G, int R, int C, int TB, int n_layers, float in_scale,
-          float acc_scale, float head_scale, float out_scale, int gate_lo, int gate_hi) {
-    using GEO = Geo<NW_, NB_, D_, RB_>;
-    constexpr int NW = GEO::NW, NB = GEO::NB, D = GEO::D, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW_;
-    __shared__ __attribute__((aligned(256))) unsigned char lds[GEO::LDS_BYTES];
-    const int n_live = n_rows ? min(*n_rows, G) : G;
-    if (n_live <= gate_lo || n_live > gate_hi) return;     // the launch only runs for row counts in (gate_lo, gate_hi]
-    const int g0 = blockIdx.x * TB;                        // first dense row of the workgroup
-    if (g0 >= n_live) return;                              // whole workgroup, before any barrier
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cells = R * C, ncol = TB * cells;            // ncol <= 16 * NB (checked on the host; row-aligned: == 16 * NB)
-    const int n_tower = 9 + 9 * NW * (n_layers - 1), crs = (GEO::RB ? 16 : C) * RS;
-
-    // the weight stream starts first: D chunks in flight before anything else is touched
-    const uint32_t voff = (uint32_t)(wave * 4096 + lane * 16);
-    WChunk W[D];
-#pragma unroll
-    for (int j = 0; j < D; j++) load_w(W[j], weights + (size_t)min(j, n_tower - 1) * GEO::CHUNK_BYTES, voff);
-
-    for (int t = threadIdx.x; t < 128; t += NT)   // the zero rows of both parts (512 B each)
+// The prologue both kernels share: the zero rows of both parts (512 B each), then the 5 planes of every column (gathered through
+// rows, times 2^ka, split) into channels 0..4 of a 32-channel zero-padded input.
+template <class GEO>
+__device__ __forceinline__ void stage_planes(unsigned char *lds, const float *planes, const int *rows, int g0, int n_live, int C,
+                                             int cells, int TB, float in_scale) {
+    constexpr int RS = GEO::RS, NT = 64 * GEO::NW;
+    for (int t = threadIdx.x; t < 128; t += NT)
         ((u32x2 *)(lds + GEO::ZERO_OFF + (t >> 6) * GEO::PART_BYTES))[t & 63] = (u32x2){0u, 0u};
-    for (int col = threadIdx.x; col < GEO::NCOL; col += NT) {   // 5 planes -> channels 0..4 of a 32-channel zero-padded input
+    for (int col = threadIdx.x; col < GEO::NCOL; col += NT) {
         int b, cell;
         col_board_cell<GEO>(col, C, cells, b, cell);
         const int gb = g0 + b;
@@ -280,15 +266,135 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
             *(u32x4 *)(lds + GEO::PART_BYTES + col * RS + 16 * q) = z;
         }
     }
+}
 
+// One lane's four output channels of one (M block, column block) after a layer: (acc1 + acc2) * 2^-kw + bias (+ the f32 residual
+// at res) and RELU in f32, kept at res for the skip (KEEP: the output is a block input x), split again into the packed words of
+// the hi and the lo part.  Activations, bias rows and residual live in the 2^ka-scaled domain.  The callers keep their loops,
+// their bias source and the LDS offsets they store hi and lo at.
+template <bool CONV2, bool KEEP, float (*RELU)(float)>
+__device__ __forceinline__ void epilogue_quad(const f32x4 acc1, const f32x4 acc2, float acc_scale, const f32x4 bq, unsigned char *res,
+                                              u32x2 &hi, u32x2 &lo) {
+    f32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[i] + acc2[i], acc_scale, bq[i]);
+    if (CONV2) v += *(const f32x4 *)res;
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = RELU(v[i]);
+    if (KEEP) *(f32x4 *)res = v;
+    uint32_t h01, l01, h23, l23;
+    split_pair((f32x2){v[0], v[1]}, h01, l01);
+    split_pair((f32x2){v[2], v[3]}, h23, l23);
+    hi = (u32x2){h01, h23};
+    lo = (u32x2){l01, l23};
+}
+
+// After the last layer, with out_heads: the 1x1 head convs (neural_network.py:113, 118): unit hm = head * 2 + M block (16 of a
+// head's 32 channels), dealt to the waves round-robin; a wave runs its units over every column block.  head_w: [hm 4][kq NW]
+// [part 2][lane 64][8 f16].  The per-lane geometry is derived again from a laundered lane id: kept alive from the prologue it would
+// sit in scratch across the whole tower.  The asm statement has no "memory" clobber, the form k_tower_g had (k_tower_g22's copy
+// carried one): k_tower_g22 stays free of scratch and within its registers without it.
+template <class GEO>
+__device__ __forceinline__ void heads_tail(const unsigned char *lds, const unsigned char *head_w, const float *head_bias, float *out_heads,
+                                           int g0, int n_live, int C, int cells, int TB, int lane, int wave, float head_scale) {
+    constexpr int NW = GEO::NW, NB = GEO::NB, RS = GEO::RS;
+    int lane2 = lane;
+    asm volatile("" : "+v"(lane2));
+    const int n16 = lane2 & 15, kg = lane2 >> 4;
+    for (int hm = wave; hm < 4; hm += NW) {
+        const int head = hm >> 1, mb = hm & 1;
+        f16x8 wh[NW], wl[NW];
+#pragma unroll
+        for (int kq = 0; kq < NW; kq++) {
+            const unsigned char *p = head_w + ((size_t)(hm * NW + kq) * 2) * 1024 + lane2 * 16;
+            wh[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
+            wl[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + 1024));
+        }
+        const float *hb = head_bias + head * 32 + mb * 16;      // uniform: scalar loads
+        float sb[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            sb[k] = hb[k];
+            asm volatile("" : "+s"(sb[k]));
+        }
+        f32x4 b;
+#pragma unroll
+        for (int i = 0; i < 4; i++) b[i] = kg == 0 ? sb[i] : kg == 1 ? sb[4 + i] : kg == 2 ? sb[8 + i] : sb[12 + i];
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++) {
+            const uint32_t xb = (uint32_t)((nb * 16 + n16) * RS + kg * 16);
+            f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kq = 0; kq < NW; kq++) {   // mma_split's order, one M block, chained over the k-steps
+                const f16x8 xh = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + kq * 64));
+                const f16x8 xl = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + GEO::PART_BYTES + kq * 64));
+                const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kq], xh, h2, 0, 0, 0);
+                h1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xh, h1, 0, 0, 0);
+                h2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xl, a, 0, 0, 0);
+            }
+            // features f32 [row][head][channel 32][cell] (the reference's NCHW flatten order)
+            int bd, cell;
+            col_board_cell<GEO>(nb * 16 + n16, C, cells, bd, cell);
+            const int gb = g0 + bd;
+            if (bd < TB && gb < n_live) {
+                float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
+#pragma unroll
+                for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
+            }
+        }
+    }
+}
+
+// After the last layer, without out_heads: activations [column][CH] f32 = (hi + lo) * 2^-ka
+template <class GEO>
+__device__ __forceinline__ void store_activations(const unsigned char *lds, float *out, int g0, int n_live, int C, int cells, int TB,
+                                                  float out_scale) {
+    constexpr int CH = GEO::CH, RS = GEO::RS, NT = 64 * GEO::NW;
+    const int ncol = TB * cells;            // <= 16 * NB (checked on the host; row-aligned: == 16 * NB)
+    for (int p = threadIdx.x; p < ncol * (CH / 4); p += NT) {
+        const int col = p / (CH / 4), ch4 = p % (CH / 4);
+        int b, cell;
+        col_board_cell<GEO>(col, C, cells, b, cell);
+        if (b < TB && g0 + b < n_live) {
+            const u32x2 ph = *(const u32x2 *)(lds + col * RS + ch4 * 8);
+            const u32x2 pl = *(const u32x2 *)(lds + GEO::PART_BYTES + col * RS + ch4 * 8);
+            const f32x2 v01 = join_pair(ph.x, pl.x), v23 = join_pair(ph.y, pl.y);
+            *(f32x4 *)(out + ((size_t)(g0 + b) * cells + cell) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
+        }
+    }
+}
+
+template <int NW_, int NB_, int D_, bool RB_>
+__global__ void __launch_bounds__(64 * NW_, 1)
+k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ weights, const unsigned char *__restrict__ head_w,
+          const float *__restrict__ bias, const float *__restrict__ head_bias, float *__restrict__ out, float *__restrict__ out_heads,
+          const int *__restrict__ rows, const int *__restrict__ n_rows, int G, int R, int C, int TB, int n_layers, float in_scale,
+          float acc_scale, float head_scale, float out_scale, int gate_lo, int gate_hi) {
+    using GEO = Geo<NW_, NB_, D_, RB_>;
+    constexpr int NW = GEO::NW, NB = GEO::NB, D = GEO::D, CH = GEO::CH, RS = GEO::RS;
+    __shared__ __attribute__((aligned(256))) unsigned char lds[GEO::LDS_BYTES];
+    const int n_live = n_rows ? min(*n_rows, G) : G;
+    if (n_live <= gate_lo || n_live > gate_hi) return;     // the launch only runs for row counts in (gate_lo, gate_hi]
+    const int g0 = blockIdx.x * TB;                        // first dense row of the workgroup
+    if (g0 >= n_live) return;                              // whole workgroup, before any barrier
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cells = R * C, n_tower = 9 + 9 * NW * (n_layers - 1), crs = (GEO::RB ? 16 : C) * RS;
+
+    // the weight stream starts first: D chunks in flight before anything else is touched
+    const uint32_t voff = (uint32_t)(wave * 4096 + lane * 16);
+    WChunk<2> W[D];
+#pragma unroll
+    for (int j = 0; j < D; j++) load_w(W[j], weights + (size_t)min(j, n_tower - 1) * GEO::CHUNK_BYTES, voff);
+
+    stage_planes<GEO>(lds, planes, rows, g0, n_live, C, cells, TB, in_scale);
     LaneGeo<GEO> geo;
     make_lane_geo<GEO>(geo, lane, R, C, TB);
     const int n16 = lane & 15, kg = lane >> 4;
     unsigned char *res_lds = lds + GEO::RES_OFF + (wave * 2 * NB) * 1024 + lane * 16;   // slot (mb * NB + nb) * 1 KB, lane-private
     int chunk = 0;
-    // (acc1 + acc2) * 2^-kw + bias (+ residual) + ReLU in f32, split again, back to LDS (activations, bias rows and residual
-    // live in the 2^ka-scaled domain).  A lane holds output channels co0 + 0..3 (co0 = 32*wave + 16*mb + 4*kg) of column
-    // nb*16 + n16.  KEEP: the output is a block input x, kept for the skip.
+    // epilogue_quad per (M block, column block), back to LDS.  A lane holds output channels co0 + 0..3 (co0 = 32*wave + 16*mb + 4*kg)
+    // of column nb*16 + n16.
     auto epilogue = [&](const int L, f32x4 (&acc1)[NB][2], f32x4 (&acc2)[NB][2], auto conv2_tag, auto keep_tag) {
         constexpr bool CONV2 = decltype(conv2_tag)::value, KEEP = decltype(keep_tag)::value;
         const float *bl = bias + L * CH + wave * 32;          // uniform address: scalar loads, pinned in SGPRs before the selects
@@ -309,19 +415,11 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
             const uint32_t rowoff = (uint32_t)((nb * 16 + n16) * RS);
 #pragma unroll
             for (int mb = 0; mb < 2; mb++) {
-                f32x4 v;
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[nb][mb][i] + acc2[nb][mb][i], acc_scale, bq[mb][i]);
-                if (CONV2) v += *(const f32x4 *)(res_lds + (mb * NB + nb) * 1024);
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = relu_keep_nan(v[i]);
-                if (KEEP) *(f32x4 *)(res_lds + (mb * NB + nb) * 1024) = v;
-                uint32_t h01, l01, h23, l23;
-                split_pair((f32x2){v[0], v[1]}, h01, l01);
-                split_pair((f32x2){v[2], v[3]}, h23, l23);
+                u32x2 hi, lo;
+                epilogue_quad<CONV2, KEEP, relu_keep_nan>(acc1[nb][mb], acc2[nb][mb], acc_scale, bq[mb], res_lds + (mb * NB + nb) * 1024, hi, lo);
                 const uint32_t co2 = (uint32_t)((wave * 32 + mb * 16 + kg * 4) * 2);
-                *(u32x2 *)(lds + rowoff + co2) = (u32x2){h01, h23};
-                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = (u32x2){l01, l23};
+                *(u32x2 *)(lds + rowoff + co2) = hi;
+                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = lo;
             }
         }
     };
@@ -341,71 +439,9 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
         else epilogue(L, acc1, acc2, std::false_type{}, std::false_type{});
     }
     __syncthreads();
-    if (out_heads) {
-        // 1x1 head convs (neural_network.py:113, 118): unit hm = head * 2 + M block (16 of a head's 32 channels), dealt to the
-        // waves round-robin; a wave runs its units over every column block.  head_w: [hm 4][kq NW][part 2][lane 64][8 f16].
-        // (the per-lane geometry is derived again from a laundered lane id: kept alive from the prologue it would sit in
-        // scratch across the whole tower)
-        int lane2 = lane;
-        asm volatile("" : "+v"(lane2));
-        const int n16 = lane2 & 15, kg = lane2 >> 4;
-        for (int hm = wave; hm < 4; hm += NW) {
-            const int head = hm >> 1, mb = hm & 1;
-            f16x8 wh[NW], wl[NW];
-#pragma unroll
-            for (int kq = 0; kq < NW; kq++) {
-                const unsigned char *p = head_w + ((size_t)(hm * NW + kq) * 2) * 1024 + lane2 * 16;
-                wh[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
-                wl[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + 1024));
-            }
-            const float *hb = head_bias + head * 32 + mb * 16;      // uniform: scalar loads
-            float sb[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                sb[k] = hb[k];
-                asm volatile("" : "+s"(sb[k]));
-            }
-            f32x4 b;
-#pragma unroll
-            for (int i = 0; i < 4; i++) b[i] = kg == 0 ? sb[i] : kg == 1 ? sb[4 + i] : kg == 2 ? sb[8 + i] : sb[12 + i];
-#pragma unroll
-            for (int nb = 0; nb < NB; nb++) {
-                const uint32_t xb = (uint32_t)((nb * 16 + n16) * RS + kg * 16);
-                f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kq = 0; kq < NW; kq++) {
-                    const f16x8 xh = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + kq * 64));
-                    const f16x8 xl = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + GEO::PART_BYTES + kq * 64));
-                    const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kq], xh, h2, 0, 0, 0);
-                    h1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xh, h1, 0, 0, 0);
-                    h2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xl, a, 0, 0, 0);
-                }
-                // features f32 [row][head][channel 32][cell] (the reference's NCHW flatten order)
-                int bd, cell;
-                col_board_cell<GEO>(nb * 16 + n16, C, cells, bd, cell);
-                const int gb = g0 + bd;
-                if (bd < TB && gb < n_live) {
-                    float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
-#pragma unroll
-                    for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
-                }
-            }
-        }
-        return;
-    }
-    for (int p = threadIdx.x; p < ncol * (CH / 4); p += NT) {   // activations [column][CH] f32 = (hi + lo) * 2^-ka
-        const int col = p / (CH / 4), ch4 = p % (CH / 4);
-        int b, cell;
-        col_board_cell<GEO>(col, C, cells, b, cell);
-        if (b < TB && g0 + b < n_live) {
-            const u32x2 ph = *(const u32x2 *)(lds + col * RS + ch4 * 8);
-            const u32x2 pl = *(const u32x2 *)(lds + GEO::PART_BYTES + col * RS + ch4 * 8);
-            const f32x2 v01 = join_pair(ph.x, pl.x), v23 = join_pair(ph.y, pl.y);
-            *(f32x4 *)(out + ((size_t)(g0 + b) * cells + cell) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
-        }
-    }
+    if (out_heads) heads_tail<GEO>(lds, head_w, head_bias, out_heads, g0, n_live, C, cells, TB, lane, wave, head_scale);
+    else store_activations<GEO>(lds, out, g0, n_live, C, cells, TB, out_scale);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // 2x2 WAVE GRID form of the row-aligned 8-block tower (k_tower_g22): 128 channels, R = 8, boards * C == 16, 8 column blocks (the
@@ -418,22 +454,19 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
 //     chunks (96 registers) next to 128 accumulators and 32 fragment registers: no AGPR <-> VGPR copies, no spill.
 //   * skips: wave nh = 0 drops block 0 at the three dy = -1 taps, nh = 1 block 7 at the three dy = +1 taps (3 of its 36 (tap,
 //     block) pairs).  nh selects one of two compiled copies of the tower, so the skips stay compile-time.
-//   * layer edges: the tap addresses are computed once per kernel (the peeled channel group reads at them directly, the looped one
-//     adds its channel offset), the bias rows sit in an LDS table (one ds_read_b128 per M block, no per-lane selects), and the
-//     ReLU is one v_maximum3_f32.
 // Every output element keeps its MFMA chain -- [layer][channel group][tap], acc1 / acc2, the same row and column of the same-shaped
-// MFMA with the same operands -- so the bits are k_tower_g's.  The prologue and the head / output tail are k_tower_g's, kept as a
-// copy so that the k_tower_g instantiations compile exactly as before.
-template <int D_> struct Geo22 {
-    static constexpr int NW = 4, NB = 8, NBW = 4, MBW = 4, D = D_, CH = 128, NCOL = 128;
-    static constexpr bool RB = true;
-    static constexpr int RS = 288, ZERO_OFF = NCOL * RS, PART_BYTES = ZERO_OFF + 512;
-    static constexpr int RES_OFF = 2 * PART_BYTES;                       // f32 residual: [wave][M block 4][column block 4] x 1 KB
-    static constexpr int BIAS_OFF = RES_OFF + NW * MBW * NBW * 1024;     // f32 bias rows [layer <= 21][CH]
-    static constexpr int LDS_BYTES = BIAS_OFF + 21 * CH * 4;
-    static constexpr int CHUNK_BYTES = NW * 4096;
-    static_assert(9 % D_ == 0, "ring position = tap % D");
-    static_assert(ZERO_OFF % 256 == 0 && PART_BYTES % 256 == 0 && LDS_BYTES <= 163840, "LDS layout");
+// MFMA with the same operands -- so the bits are k_tower_g's.  Both kernels call the one copy of stage_planes, mma_split,
+// for_each_tap, epilogue_quad, heads_tail and store_activations above.  What differs here is deliberate and stays: tap addresses
+// computed once per kernel (Taps22: the peeled channel group reads at them directly, the looped one adds its channel offset)
+// against rowbase / okmask selects (81 address registers do not fit at NB = 9); bias rows from an LDS table (one ds_read_b128 per
+// M block) against SGPRs and per-lane selects (NB = 9 has no LDS to spare); relu_max (one v_maximum3_f32) against relu_keep_nan;
+// the ring depth; the two weight offsets of load_w22; off22 against off_board; and run_chunk22 / run_layer22 next to run_chunk /
+// run_layer, whose scheduling barriers and address forms are what each form's speed consists of.
+template <int D_> struct Geo22 : Geo<4, 8, D_, true> {   // rows, parts, zero rows, RES_OFF and weight chunks of k_tower_g<4, 8, D, true>
+    static constexpr int NBW = 4, MBW = 4;                               // column blocks and M blocks of a wave
+    static constexpr int BIAS_OFF = Geo22::RES_OFF + Geo22::NW * MBW * NBW * 1024;   // behind the residual [wave][M block 4][block 4] x 1 KB
+    static constexpr int LDS_BYTES = BIAS_OFF + 21 * Geo22::CH * 4;     // f32 bias rows [layer <= 21][CH]; replaces the base's
+    static_assert(LDS_BYTES <= 163840, "LDS layout");
 };
 
 // NaN-keeping ReLU in one VALU, v_maximum3_f32 (IEEE 754-2019 maximum: a NaN operand gives a NaN, maximum(-0, +0) = +0): the bits
@@ -467,13 +500,10 @@ template <class GEO, int NH> __device__ __forceinline__ void make_taps22(Taps22 
     }
 }
 
-// this wave's A fragments of one weight chunk: [M block 4]{hi, lo}, 32 registers (k_tower_g's waves 2mh and 2mh + 1)
-struct WChunk22 {
-    f16x8 h[4], l[4];
-};
+// A wave's A fragments of one weight chunk are WChunk<4>: 32 registers, the fragments of k_tower_g's waves 2mh and 2mh + 1.
 // wbase: uniform chunk address; voff[2] = this lane's offsets of M blocks 0-1 and 2-3 (two registers, so that every load is
 // "uniform base + lane offset + immediate" with no per-chunk 64-bit address arithmetic)
-__device__ __forceinline__ void load_w22(WChunk22 &w, const unsigned char *wbase, const uint32_t (&voff)[2]) {
+__device__ __forceinline__ void load_w22(WChunk<4> &w, const unsigned char *wbase, const uint32_t (&voff)[2]) {
 #pragma unroll
     for (int m = 0; m < 4; m++) {
         const u32x4 *p = (const u32x4 *)(wbase + voff[m >> 1]);
@@ -481,31 +511,16 @@ __device__ __forceinline__ void load_w22(WChunk22 &w, const unsigned char *wbase
         w.l[m] = __builtin_bit_cast(f16x8, p[128 * (m & 1) + 64]);
     }
 }
-struct XWin22 {
-    f16x8 h[4], l[4];
-};
-
-// acc1 += w_hi * x_hi ;  acc2 += w_lo * x_hi + w_hi * x_lo for the four M blocks of one column block (12 MFMAs, mma6's order)
-template <bool ZERO>
-__device__ __forceinline__ void mma12(f32x4 (&acc1)[4], f32x4 (&acc2)[4], const WChunk22 &w, const f16x8 xh, const f16x8 xl) {
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.l[m], xh, ZERO ? z : acc2[m], 0, 0, 0);
-        acc1[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[m], xh, ZERO ? z : acc1[m], 0, 0, 0);
-        acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w.h[m], xl, a, 0, 0, 0);
-    }
-}
 
 // One chunk = tap J of an input-channel group: 48 MFMAs less the dropped pairs.  Right after the MFMAs of block b its fragment
 // slot takes the next chunk's fragment of block b (tap J + 1; the last tap reads the next channel group at koff_next).
 template <int NH, int J, bool ZERO>
-__device__ __forceinline__ void run_chunk22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], const WChunk22 &w, XWin22 &X,
+__device__ __forceinline__ void run_chunk22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], const WChunk<4> &w, XWin<4> &X,
                                             const unsigned char *lds_cur, const unsigned char *lds_next, const Taps22 &t, int part_bytes) {
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const bool mma = !off22<NH>(J, b), ld = !off22<NH>((J + 1) % 9, b);
-        if (mma) mma12<ZERO>(acc1[b], acc2[b], w, X.h[b], X.l[b]);
+        if (mma) mma_split<4, ZERO>(acc1[b], acc2[b], w, X.h[b], X.l[b]);
         if (ld) {
             const unsigned char *p = (J == 8 ? lds_next : lds_cur) + t.a[(J + 1) % 9][b];
             X.h[b] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
@@ -518,11 +533,11 @@ __device__ __forceinline__ void run_chunk22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4
 
 // One layer (stem: one channel group), as run_layer: ring position = tap % D, weight stream order [layer][kq][tap].
 template <class GEO, int NH, bool STEM>
-__device__ __forceinline__ void run_layer22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], WChunk22 (&W)[GEO::D], const unsigned char *lds,
+__device__ __forceinline__ void run_layer22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], WChunk<4> (&W)[GEO::D], const unsigned char *lds,
                                             const unsigned char *weights, const uint32_t (&voff)[2], int &chunk, int n_tower,
                                             const Taps22 &t) {
     constexpr int KQ = STEM ? 1 : GEO::NW, D = GEO::D;
-    XWin22 X;
+    XWin<4> X;
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         if (off22<NH>(0, b)) {   // this block skips the layer's first chunk (tap 0): its sums start from +0, as that chunk's would
@@ -541,29 +556,17 @@ __device__ __forceinline__ void run_layer22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4
         __builtin_amdgcn_sched_barrier(0);                       // one scheduling region per chunk (see run_layer)
         chunk++;
     };
-    auto taps = [&](auto zt, const unsigned char *cur, const unsigned char *nxt) {
-        step(std::integral_constant<int, 0>{}, zt, cur, cur);
-        step(std::integral_constant<int, 1>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 2>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 3>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 4>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 5>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 6>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 7>{}, std::false_type{}, cur, cur);
-        step(std::integral_constant<int, 8>{}, std::false_type{}, cur, nxt);
-    };
-    taps(std::true_type{}, lds, lds + 64);                        // channel group 0, peeled: reads at the tap addresses themselves
+    for_each_tap(step, std::true_type{}, lds, lds + 64);          // channel group 0, peeled: reads at the tap addresses themselves
 #pragma unroll 1
     for (int kq = 1; kq < KQ; kq++) {
         uint32_t cur = kq * 64, nxt = cur + 64;   // uniform channel-group offsets: one v_add per fragment address
         asm volatile("" : "+s"(cur), "+s"(nxt));
-        taps(std::false_type{}, lds + cur, lds + nxt);
+        for_each_tap(step, std::false_type{}, lds + cur, lds + nxt);
     }
 }
 
-// Everything of wave column half NH up to the last layer's epilogue: the weight ring and the prologue (as k_tower_g's, plus the
-// bias table), then the stem and the CH -> CH layers, each followed by its epilogue: (acc1 + acc2) * 2^-kw + bias (+ residual),
-// ReLU, split again, back to LDS.  A lane holds output channels 64mh + 16m + 4kg + 0..3 of column (4NH + b)*16 + n16.
+// Everything of wave column half NH up to the last layer's epilogue: the weight ring and the prologue (plus the bias table), then the
+// stem and the CH -> CH layers, each followed by its epilogue.  A lane holds output channels 64mh + 16m + 4kg + 0..3 of column (4NH + b)*16 + n16.
 template <class GEO, int NH>
 __device__ __forceinline__ void tower22(unsigned char *lds, const float *__restrict__ planes, const unsigned char *__restrict__ weights,
                                         const float *__restrict__ bias, const int *__restrict__ rows, int g0, int n_live, int R, int C,
@@ -572,36 +575,12 @@ __device__ __forceinline__ void tower22(unsigned char *lds, const float *__restr
     const int cells = R * C, n_tower = 9 + 9 * NW * (n_layers - 1);
     uint32_t voff[2] = {(uint32_t)((wave >> 1) * 8192 + lane * 16), (uint32_t)((wave >> 1) * 8192 + 4096 + lane * 16)};
     asm volatile("" : "+v"(voff[1]));
-    WChunk22 W[D];
+    WChunk<4> W[D];
 #pragma unroll
     for (int j = 0; j < D; j++) load_w22(W[j], weights + (size_t)min(j, n_tower - 1) * GEO::CHUNK_BYTES, voff);
 
-    for (int t = threadIdx.x; t < 128; t += NT)   // the zero rows of both parts (512 B each)
-        ((u32x2 *)(lds + GEO::ZERO_OFF + (t >> 6) * GEO::PART_BYTES))[t & 63] = (u32x2){0u, 0u};
     for (int i = threadIdx.x; i < n_layers * CH; i += NT) ((float *)(lds + GEO::BIAS_OFF))[i] = bias[i];
-    for (int col = threadIdx.x; col < GEO::NCOL; col += NT) {   // 5 planes -> channels 0..4 of a 32-channel zero-padded input
-        int b, cell;
-        col_board_cell<GEO>(col, C, cells, b, cell);
-        const int gb = g0 + b;
-        const bool live = b < TB && gb < n_live;
-        const int src = live ? (rows ? rows[gb] : gb) : 0;
-        float p[6];
-#pragma unroll
-        for (int k = 0; k < 5; k++) p[k] = live ? planes[((size_t)src * 5 + k) * cells + cell] * in_scale : 0.0f;
-        p[5] = 0.0f;
-        uint32_t hi[3], lo[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) split_pair((f32x2){p[2 * k], p[2 * k + 1]}, hi[k], lo[k]);
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        *(u32x4 *)(lds + col * RS) = (u32x4){hi[0], hi[1], hi[2], 0u};
-        *(u32x4 *)(lds + GEO::PART_BYTES + col * RS) = (u32x4){lo[0], lo[1], lo[2], 0u};
-#pragma unroll
-        for (int q = 1; q < 4; q++) {
-            *(u32x4 *)(lds + col * RS + 16 * q) = z;
-            *(u32x4 *)(lds + GEO::PART_BYTES + col * RS + 16 * q) = z;
-        }
-    }
-
+    stage_planes<GEO>(lds, planes, rows, g0, n_live, C, cells, TB, in_scale);
     const int mh = wave >> 1, n16 = lane & 15, kg = lane >> 4;
     Taps22 t;
     make_taps22<GEO, NH>(t, lane, R, C, TB);
@@ -618,19 +597,11 @@ __device__ __forceinline__ void tower22(unsigned char *lds, const float *__restr
             const uint32_t rowoff = (uint32_t)(((4 * NH + b) * 16 + n16) * RS);
 #pragma unroll
             for (int m = 0; m < 4; m++) {
-                f32x4 v;
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = __builtin_fmaf(acc1[b][m][i] + acc2[b][m][i], acc_scale, bq[m][i]);
-                if (CONV2) v += *(const f32x4 *)(res_lds + (m * 4 + b) * 1024);
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = relu_max(v[i]);
-                if (KEEP) *(f32x4 *)(res_lds + (m * 4 + b) * 1024) = v;
-                uint32_t h01, l01, h23, l23;
-                split_pair((f32x2){v[0], v[1]}, h01, l01);
-                split_pair((f32x2){v[2], v[3]}, h23, l23);
+                u32x2 hi, lo;
+                epilogue_quad<CONV2, KEEP, relu_max>(acc1[b][m], acc2[b][m], acc_scale, bq[m], res_lds + (m * 4 + b) * 1024, hi, lo);
                 const uint32_t co2 = (uint32_t)((mh * 64 + m * 16 + kg * 4) * 2);
-                *(u32x2 *)(lds + rowoff + co2) = (u32x2){h01, h23};
-                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = (u32x2){l01, l23};
+                *(u32x2 *)(lds + rowoff + co2) = hi;
+                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = lo;
             }
         }
     };
@@ -658,83 +629,19 @@ k_tower_g22(const float *__restrict__ planes, const unsigned char *__restrict__ 
             const int *__restrict__ rows, const int *__restrict__ n_rows, int G, int R, int C, int TB, int n_layers, float in_scale,
             float acc_scale, float head_scale, float out_scale, int gate_lo, int gate_hi) {
     using GEO = Geo22<D_>;
-    constexpr int NW = GEO::NW, NB = GEO::NB, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW;
     __shared__ __attribute__((aligned(256))) unsigned char lds[GEO::LDS_BYTES];
     const int n_live = n_rows ? min(*n_rows, G) : G;
     if (n_live <= gate_lo || n_live > gate_hi) return;
     const int g0 = blockIdx.x * TB;
     if (g0 >= n_live) return;
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, cells = R * C;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cells = R * C, ncol = TB * cells;            // == 16 * NB (checked on the host)
-
     // nh selects the compiled copy: everything up to the last layer's epilogue runs inside it, so no value crosses the branch
     if (wave & 1) tower22<GEO, 1>(lds, planes, weights, bias, rows, g0, n_live, R, C, TB, n_layers, lane, wave, in_scale, acc_scale);
     else tower22<GEO, 0>(lds, planes, weights, bias, rows, g0, n_live, R, C, TB, n_layers, lane, wave, in_scale, acc_scale);
     __syncthreads();
-    if (out_heads) {
-        // 1x1 head convs (neural_network.py:113, 118): unit hm = head * 2 + M block (16 of a head's 32 channels), dealt to the
-        // waves round-robin; a wave runs its units over every column block.  head_w: [hm 4][kq NW][part 2][lane 64][8 f16].
-        // (the per-lane geometry is derived again from a laundered lane id: kept alive from the prologue it would sit in
-        // scratch across the whole tower)
-        int lane2 = lane;
-        asm volatile("" : "+v"(lane2) : : "memory");      // and not hoisted above the tower: its head weights would sit in scratch
-        const int n16 = lane2 & 15, kg = lane2 >> 4;
-        for (int hm = wave; hm < 4; hm += NW) {
-            const int head = hm >> 1, mb = hm & 1;
-            f16x8 wh[NW], wl[NW];
-#pragma unroll
-            for (int kq = 0; kq < NW; kq++) {
-                const unsigned char *p = head_w + ((size_t)(hm * NW + kq) * 2) * 1024 + lane2 * 16;
-                wh[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)p);
-                wl[kq] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + 1024));
-            }
-            const float *hb = head_bias + head * 32 + mb * 16;      // uniform: scalar loads
-            float sb[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                sb[k] = hb[k];
-                asm volatile("" : "+s"(sb[k]));
-            }
-            f32x4 b;
-#pragma unroll
-            for (int i = 0; i < 4; i++) b[i] = kg == 0 ? sb[i] : kg == 1 ? sb[4 + i] : kg == 2 ? sb[8 + i] : sb[12 + i];
-#pragma unroll
-            for (int nb = 0; nb < NB; nb++) {
-                const uint32_t xb = (uint32_t)((nb * 16 + n16) * RS + kg * 16);
-                f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kq = 0; kq < NW; kq++) {
-                    const f16x8 xh = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + kq * 64));
-                    const f16x8 xl = __builtin_bit_cast(f16x8, *(const u32x4 *)(lds + xb + GEO::PART_BYTES + kq * 64));
-                    const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kq], xh, h2, 0, 0, 0);
-                    h1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xh, h1, 0, 0, 0);
-                    h2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kq], xl, a, 0, 0, 0);
-                }
-                // features f32 [row][head][channel 32][cell] (the reference's NCHW flatten order)
-                int bd, cell;
-                col_board_cell<GEO>(nb * 16 + n16, C, cells, bd, cell);
-                const int gb = g0 + bd;
-                if (bd < TB && gb < n_live) {
-                    float *o = out_heads + (((size_t)gb * 2 + head) * 32 + mb * 16 + kg * 4) * cells + cell;
-#pragma unroll
-                    for (int i = 0; i < 4; i++) o[i * cells] = relu_keep_nan(__builtin_fmaf(h1[i] + h2[i], head_scale, b[i]));
-                }
-            }
-        }
-        return;
-    }
-    for (int p = threadIdx.x; p < ncol * (CH / 4); p += NT) {   // activations [column][CH] f32 = (hi + lo) * 2^-ka
-        const int col = p / (CH / 4), ch4 = p % (CH / 4);
-        int b, cell;
-        col_board_cell<GEO>(col, C, cells, b, cell);
-        if (b < TB && g0 + b < n_live) {
-            const u32x2 ph = *(const u32x2 *)(lds + col * RS + ch4 * 8);
-            const u32x2 pl = *(const u32x2 *)(lds + GEO::PART_BYTES + col * RS + ch4 * 8);
-            const f32x2 v01 = join_pair(ph.x, pl.x), v23 = join_pair(ph.y, pl.y);
-            *(f32x4 *)(out + ((size_t)(g0 + b) * cells + cell) * CH + ch4 * 4) = (f32x4){v01.x, v01.y, v23.x, v23.y} * out_scale;
-        }
-    }
+    if (out_heads) heads_tail<GEO>(lds, head_w, head_bias, out_heads, g0, n_live, C, cells, TB, lane, wave, head_scale);
+    else store_activations<GEO>(lds, out, g0, n_live, C, cells, TB, out_scale);
 }
 
 // yy_nn_tower_g_relu_check: relu_max against relu_keep_nan, one bit pattern per thread and step
@@ -768,16 +675,9 @@ struct TgArgs {
     hipStream_t s;
 };
 
-template <int D> int launch_tg22(const TgArgs &a) {
-    tg::k_tower_g22<D><<<dim3((a.G + a.TB - 1) / a.TB), dim3(256), 0, a.s>>>(
-        a.planes, (const unsigned char *)a.weights, (const unsigned char *)a.head_w, a.bias, a.head_bias, a.out, a.out_heads, a.rows,
-        a.n_rows, a.G, a.R, a.C, a.TB, a.n_layers, a.sc[0], a.sc[1], a.sc[2], a.sc[3], a.gate_lo, a.gate_hi);
-    if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_nn_tower_g: launch failed");
-    return YY_OK;
-}
-
-template <int NW, int NB, int D, bool RB = false> int launch_tg(const TgArgs &a) {
-    tg::k_tower_g<NW, NB, D, RB><<<dim3((a.G + a.TB - 1) / a.TB), dim3(64 * NW), 0, a.s>>>(
+// every form runs 64 threads per 32-channel slice (nw slices) and TB boards per workgroup
+template <auto KERNEL> int launch_tg(int nw, const TgArgs &a) {
+    KERNEL<<<dim3((a.G + a.TB - 1) / a.TB), dim3(64 * nw), 0, a.s>>>(
         a.planes, (const unsigned char *)a.weights, (const unsigned char *)a.head_w, a.bias, a.head_bias, a.out, a.out_heads, a.rows,
         a.n_rows, a.G, a.R, a.C, a.TB, a.n_layers, a.sc[0], a.sc[1], a.sc[2], a.sc[3], a.gate_lo, a.gate_hi);
     if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_nn_tower_g: launch failed");
@@ -791,20 +691,20 @@ template <int NW, int NB, int D, bool RB = false> int launch_tg(const TgArgs &a)
 int dispatch_tg(int nw, int nb, int layout, const TgArgs &a) {
     const bool rb = layout != 1 && a.TB * a.C == 16 && nb == a.R;
     if (nw == 4) {
-        if (rb && nb == 8) return layout == 2 ? launch_tg<4, 8, 9, true>(a) : launch_tg22<3>(a);
-        if (rb && nb == 4) return launch_tg<4, 4, 9, true>(a);
+        if (rb && nb == 8) return layout == 2 ? launch_tg<tg::k_tower_g<4, 8, 9, true>>(nw, a) : launch_tg<tg::k_tower_g22<3>>(nw, a);
+        if (rb && nb == 4) return launch_tg<tg::k_tower_g<4, 4, 9, true>>(nw, a);
         switch (nb) {
-        case 4: return launch_tg<4, 4, 9>(a);
-        case 5: return launch_tg<4, 5, 9>(a);
-        case 6: return launch_tg<4, 6, 9>(a);
-        case 7: return launch_tg<4, 7, 9>(a);
-        case 8: return launch_tg<4, 8, 9>(a);
-        case 9: return launch_tg<4, 9, 9>(a);
+        case 4: return launch_tg<tg::k_tower_g<4, 4, 9, false>>(nw, a);
+        case 5: return launch_tg<tg::k_tower_g<4, 5, 9, false>>(nw, a);
+        case 6: return launch_tg<tg::k_tower_g<4, 6, 9, false>>(nw, a);
+        case 7: return launch_tg<tg::k_tower_g<4, 7, 9, false>>(nw, a);
+        case 8: return launch_tg<tg::k_tower_g<4, 8, 9, false>>(nw, a);
+        case 9: return launch_tg<tg::k_tower_g<4, 9, 9, false>>(nw, a);
         }
     } else if (nb == 4 || nb == 9) {
-        if (nw == 1) return nb == 4 ? launch_tg<1, 4, 9>(a) : launch_tg<1, 9, 3>(a);
-        if (nw == 2) return nb == 4 ? launch_tg<2, 4, 9>(a) : launch_tg<2, 9, 3>(a);
-        if (nw == 3) return nb == 4 ? launch_tg<3, 4, 9>(a) : launch_tg<3, 9, 3>(a);
+        if (nw == 1) return nb == 4 ? launch_tg<tg::k_tower_g<1, 4, 9, false>>(nw, a) : launch_tg<tg::k_tower_g<1, 9, 3, false>>(nw, a);
+        if (nw == 2) return nb == 4 ? launch_tg<tg::k_tower_g<2, 4, 9, false>>(nw, a) : launch_tg<tg::k_tower_g<2, 9, 3, false>>(nw, a);
+        if (nw == 3) return nb == 4 ? launch_tg<tg::k_tower_g<3, 4, 9, false>>(nw, a) : launch_tg<tg::k_tower_g<3, 9, 3, false>>(nw, a);
     }
     return yy_tower_set_err(YY_E_UNSUPPORTED, "yy_nn_tower_g: no kernel form for this (channels, column blocks)");
 }
