@@ -70,7 +70,7 @@ def test_tower_kernel_matches_torch_bf16_path():
     torch.manual_seed(0)
     game = pkg.YinYangGame(8, 8)
     rng = np.random.default_rng(3)
-    # G picks the kernel: <= 256 one board per workgroup, <= 512 two (yy_towerq.hip), above that four (yy_tower.hip)
+    # G picks the kernel: <= 256 one board per workgroup, <= 512 two (k_towerq), above that four (k_tower; both csrc/yy_tower.hip)
     for blocks, G in ((1, 7), (3, 300), (10, 130), (10, 1030)):
         net = pkg.YinYangNeuralNetwork(game, 128, blocks).cuda().eval()
         # non-trivial BatchNorm statistics and biases so that folding and the bias path are exercised
@@ -148,7 +148,7 @@ def test_tower_small_batch_kernels_bit_identical_to_main():
 
 @pytest.mark.parametrize("R", [12, 6])
 def test_tower_other_sizes_match_torch_bf16_path(R):
-    """12x12 and 6x6 (csrc/yy_towerq.hip <12,2> and <6,8>) variants: same checks as the 8x8 kernel -- tower activations within 2 bf16 ulps of
+    """12x12 and 6x6 (csrc/yy_tower.hip, k_towerq<12,2> and <6,8>) variants: same checks as the 8x8 kernel -- tower activations within 2 bf16 ulps of
     scale per layer against torch bf16 convolutions on the same folded weights, fused head features within 2 ulps,
     end-to-end policy 2e-2 / value 5e-2 abs against the torch bf16 path and the fp32 module."""
     import torch
@@ -193,6 +193,30 @@ def test_tower_other_sizes_match_torch_bf16_path(R):
             p, v = ev(planes)
             assert p.shape == (G, R * R) and float((p - p_r).abs().max()) < 2e-2 and float((v - v_r).abs().max()) < 5e-2
             assert float((p - p32).abs().max()) < 2e-2 and float((v - v32).abs().max()) < 5e-2
+
+
+@pytest.mark.parametrize("R", [6, 12])
+def test_tower_nine_tile_kernels_independent_of_batch(R):
+    """6x6 and 12x12 (csrc/yy_tower.hip, k_towerq<6,8> and <12,2>: 288 columns = nine tiles, at 6x6 tiles straddle boards): the lane
+    geometry, the epilogue and the head staging are per column, so a board's output must not depend on the batch it is evaluated in,
+    on its slot in the workgroup or on its side of a straddled tile: exact.  19 boards = 2 full workgroups of 8 plus 3 at 6x6, 9 full
+    workgroups of 2 plus 1 at 12x12; reversing the batch moves every board to another slot."""
+    import torch
+    import yinyang_game_alphazero_amd as pkg
+    E = pkg.engine
+    torch.manual_seed(2)
+    net = pkg.YinYangNeuralNetwork(pkg.YinYangGame(R, R), 128, 2).cuda().eval()
+    ev = pkg.BatchedEvaluator(net, "bf16")
+    rng = np.random.default_rng(19)
+    planes = E.encode_planes(torch.from_numpy(rng.integers(-1, 2, size=(19, R, R)).astype(np.int8)).cuda())
+    for fwd, w, b in ((E.tower_forward, ev.tower_w, ev.tower_b), (E.tower_heads_forward, ev.towerh_w, ev.towerh_b)):
+        full = fwd(planes, w, b, ev.tower_layers).view(torch.int16)
+        assert bool((full != 0).any())
+        rev = fwd(planes.flip(0).contiguous(), w, b, ev.tower_layers).view(torch.int16)
+        assert torch.equal(rev.flip(0), full)
+        for i in (0, 7, 18):
+            one = fwd(planes[i:i + 1].contiguous(), w, b, ev.tower_layers).view(torch.int16)
+            assert torch.equal(one[0], full[i]), i
 
 
 def test_f32_tower_kernel_matches_fp32_module():

@@ -35,7 +35,7 @@ class MctsConfig(C.Structure):
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip into libyy_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("yy_engine.hip", "yy_nn_epilogue.hip", "yy_tower.hip", "yy_towerq.hip", "yy_tower_f32.hip",
+    srcs = [os.path.join(CSRC, f) for f in ("yy_engine.hip", "yy_nn_epilogue.hip", "yy_tower.hip", "yy_tower_f32.hip",
                                             "yy_tower_h3r.hip", "yy_tower_g.hip", "yy_fc_heads.hip", "yy_selfplay.hip",
                                             "yy_bitboard.h", "yy_common.h")] + [HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):

@@ -1,5 +1,5 @@
-// yy_common.h -- what the .hip files of libyy_hip.so share: the error reporting behind yy_last_error() and a device
-// one-liner that more than one kernel file needs.
+// yy_common.h -- what the .hip files of libyy_hip.so share: the error reporting behind yy_last_error() and the device
+// one-liners that more than one kernel file needs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -23,3 +23,6 @@ static inline int yy_hip_fail(const char *what, hipError_t e) {
 // ReLU that keeps NaN (as torch.relu does): fmaxf(NaN, 0) is 0, which would turn an overflowed activation (hi = inf, lo = -inf
 // -> NaN in the next accumulators) back into a finite, wrong result.  Every other input gets fmaxf's result, bit for bit.
 __device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_isnan(v) ? v : fmaxf(v, 0.0f); }
+
+// Counted wait on the LDS-DMA weight ring (yy_tower.hip, yy_tower_f32.hip): at most N vector-memory loads still in flight.
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

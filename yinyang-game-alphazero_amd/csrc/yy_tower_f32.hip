@@ -36,12 +36,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 namespace tf32 {
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    if (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    if (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-}
 __device__ __forceinline__ void issue_chunk(const unsigned char *wchunk, unsigned char *lds, int slot, int wave, int lane) {
 #pragma unroll
     for (int r = 0; r < 4; r++) {

@@ -137,8 +137,8 @@ def bias_act_(x, bias, residual=None, relu=True):
 
 
 def tower_forward(planes, weights, bias, n_layers):
-    """Stem + residual tower in one LDS-resident MFMA kernel (csrc/yy_tower.hip, yy_towerq.hip).
-    planes f32 [G,5,R,R] (R = 8 or 12) -> bf16 activations as a channels-last tensor [G,128,R,R]."""
+    """Stem + residual tower in one LDS-resident MFMA kernel (csrc/yy_tower.hip: k_tower, k_towerq).
+    planes f32 [G,5,R,R] (R = 6, 8 or 12) -> bf16 activations as a channels-last tensor [G,128,R,R]."""
     G, _, R, Cc = planes.shape
     _need(planes, torch.float32, (G, 5, R, Cc), "planes")
     n_chunks = 9 + 18 * (n_layers - 1)
@@ -311,7 +311,7 @@ def compact_rows(flags, rows=None, n=None):
 
 
 def tower_heads_forward(planes, weights, bias, n_layers):
-    """Tower + fused 1x1 head convolutions: planes f32 [G,5,R,R] (R = 8 or 12) ->
+    """Tower + fused 1x1 head convolutions: planes f32 [G,5,R,R] (R = 6, 8 or 12) ->
     bf16 [G,2,32*R*R] = (policy features, value features) in the reference's flatten order."""
     G, _, R, Cc = planes.shape
     _need(planes, torch.float32, (G, 5, R, Cc), "planes")
