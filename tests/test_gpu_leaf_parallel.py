@@ -129,6 +129,53 @@ def test_lockstep_graph_equals_eager_with_rows_limit_and_inactive_games(pkg):
         assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
 
 
+@pytest.mark.parametrize("S,n_graphs", [(1, 0), (2, 0), (4, 0), (5, 1), (12, 2), (13, 2)])
+@pytest.mark.parametrize("K", [1, 3])
+def test_every_driver_agrees_on_short_searches(pkg, K, S, n_graphs):
+    """S steps of K descents around LockstepSearch's thresholds (eager_sims = 3, unroll = 4): S - 1 = 3 middle steps capture
+    nothing, 4 the one-step graph, 11 leave 8 = 2 * unroll after the warm-up and capture both, 12 replay the unrolled graph twice
+    and the one-step graph besides.  search() fused and unfused, LockstepSearch eager and replayed: one result."""
+    import torch
+    from yinyang_game_alphazero_amd.search import LockstepSearch
+    R, C, G, sims = 6, 6, 4, K * S
+    boards, players = (torch.from_numpy(a).cuda() for a in roots(R, C, G, 3, seed=7))
+    ev = lambda planes, **kw: hash_eval_torch(planes, PB, VB)
+
+    def lockstep(use_graph, searches):
+        def drive(mc):
+            ls = LockstepSearch(mc, ev, use_graph=use_graph, eager_sims=3, unroll=4)
+            for _ in range(searches):                                 # the second search is pure replay
+                ls.run(boards, players, sims)
+            assert len(ls.graphs) == (n_graphs if use_graph else 0)
+        return drive, searches
+
+    res = []
+    for drive, searches in ((lambda mc: mc.search(boards, players, ev, sims, fused=True), 1),
+                            (lambda mc: mc.search(boards, players, ev, sims, fused=False), 1), lockstep(False, 1), lockstep(True, 2)):
+        mc = pkg.engine.BatchedMCTS(G, R, C, sims, leaves_per_step=K)
+        try:
+            drive(mc)
+            counters = mc.status()
+            assert all(v % searches == 0 for v in counters.values())
+            res.append([t.cpu().numpy() for t in mc.root_counts(with_children=True) + mc.root_stats()]
+                       + [{k: v // searches for k, v in counters.items()}])
+        finally:
+            mc.close()
+    if n_graphs:                                                      # unroll = 1: the one-step graph only, same result
+        mc = pkg.engine.BatchedMCTS(G, R, C, sims, leaves_per_step=K)
+        try:
+            ls = LockstepSearch(mc, ev, use_graph=True, eager_sims=3, unroll=1)
+            ls.run(boards, players, sims)
+            assert len(ls.graphs) == 1
+            res.append([t.cpu().numpy() for t in mc.root_counts(with_children=True) + mc.root_stats()] + [mc.status()])
+        finally:
+            mc.close()
+    assert (res[0][3] == sims).all()
+    for other in res[1:]:
+        for a, b in zip(res[0], other):
+            assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
+
+
 def test_nan_in_a_later_row_stops_only_that_game(pkg):
     import torch
     R, C, G, sims, K = 6, 6, 3, 40, 4

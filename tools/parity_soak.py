@@ -48,7 +48,7 @@ while time.time() - t0 < budget:
                 noise[g, valid[g] == 1] = rng.dirichlet([0.3] * k)
     ctx = pkg.engine.BatchedMCTS(G, R, C, sims, aliased=not copied)
     ev = lambda planes: hash_eval_torch(planes, pb, vb)
-    from yinyang_game_alphazero_amd.self_play import LockstepSearch
+    from yinyang_game_alphazero_amd.search import LockstepSearch
     ls = LockstepSearch(ctx, ev, use_graph=bool(rng.random() < 0.5))
     ls.run(torch.from_numpy(boards).cuda(), torch.from_numpy(players).cuda(), sims,
            noise=torch.from_numpy(noise).cuda() if use_noise else None)

@@ -14,6 +14,7 @@ the winner whenever the loser is to move; here the winner is the colour with mor
 """
 import os
 import shutil
+import time
 
 import numpy as np
 import torch
@@ -21,7 +22,8 @@ import torch
 from . import engine
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
-from .self_play import LockstepSearch, generate_self_play_data
+from .search import LockstepSearch
+from .self_play import generate_self_play_data
 from .training import run_training_pipeline
 
 
@@ -112,6 +114,8 @@ class Arena:
         board object and mutates it (aliased boards), there is no pass handling -- a side without a move still
         searches, np.argmax of the uniform pi gives action 0, the illegal placement is ignored and the player flips (Q3) --
         and the scoring is the reference's.
+        num_simulations = 0: a search only expands the root, pi is uniform over all A actions (mcts.py:209-213) and its arg-max is
+        action 0, legal or not (an illegal placement is ignored and the player flips), as the reference's select_action does.
         leaves_per_step K > 1: leaf-parallel searches (MCTS leaves_per_step); copied boards only, so not with literal=True, and
         without evaluation reuse."""
         self.game = game
@@ -359,7 +363,6 @@ class AlphaZero:
         return promote
 
     def run(self):
-        import time
         for it in range(self.num_iterations):
             t0 = time.perf_counter()
             data_file = self.self_play(self.best_model_path)

@@ -480,6 +480,7 @@ class BatchedMCTS:
         self.planes = torch.zeros((self.rows, 5, self.R, self.C), dtype=torch.float32, device=self.device)
         self.needs_eval = torch.zeros(self.rows, dtype=torch.uint8, device=self.device)
         self._num_sims = self.max_sims
+        self.book, self.book_version, self._evaluator_owner = None, 0, None
 
     # -- lifetime
     def close(self):
@@ -588,18 +589,17 @@ class BatchedMCTS:
                 check(lib().yy_mcts_set_book(self._h, _p(book.meta), _p(book.table_keys), _p(book.value), _p(book.policy),
                                              book.cap, book.max_stones))
         self.book = book
-        self.book_version = getattr(self, "book_version", 0) + 1      # captured steps hold the table's pointers: LockstepSearch re-captures
+        self.book_version += 1      # captured steps hold the table's pointers: LockstepSearch re-captures
 
     def bind_evaluator(self, evaluator):
         """Evaluations kept across searches (keep_evaluations) and the opening book are results of ONE network: the engine-level
-        searches (self_play.LockstepSearch: SelfPlayEngine, MCTS, Arena) bind the context to their evaluator object; a search with
+        searches (search.LockstepSearch: SelfPlayEngine, MCTS, Arena) bind the context to their evaluator object; a search with
         another one clears the cache and drops the book instead of silently mixing two networks' numbers.  The low-level
         search() below takes any callable per call and does not bind: there clear_evaluation_cache() is the caller's job."""
-        owner = getattr(self, "_evaluator_owner", None)
-        if owner is not None and owner is not evaluator:
+        if self._evaluator_owner is not None and self._evaluator_owner is not evaluator:
             if self.keep_evaluations:
                 self.clear_evaluation_cache()
-            if getattr(self, "book", None) is not None:
+            if self.book is not None:
                 self.set_book(None)
         self._evaluator_owner = evaluator
 
@@ -612,25 +612,38 @@ class BatchedMCTS:
             check(lib().yy_mcts_reset_counters(self._h, _stream()))
 
     # -- the whole of MCTS.search for G games (mcts.py:275-343)
-    def search(self, boards, root_players, evaluator, num_sims, noise=None, eps=0.25, active=None, fused=True):
-        """evaluator(planes f32[G*K,5,R,C]) -> (policy f32[G*K,A] softmax, value f32[G*K]) on device.
-        Runs 1 + num_sims evaluator calls exactly like the reference (root call, then one per
-        simulation; with K leaves per step 1 + ceil(num_sims / K)) and returns the root visit counts int32 [G,A]."""
+    def run_search(self, boards, root_players, num_sims, evaluate, noise=None, eps=0.25, active=None, middle=None):
+        """The ONE statement of a search's C ABI call order; search() below and search.LockstepSearch.run drive it.
+        evaluate(root) -> (policy, value) of the leaf batch in self.planes, root=True on the root call (mcts.py:295, value discarded);
+        middle(n) issues the n = steps - 1 middle steps (default: n times [evaluate, step]).  num_sims == 0: the root only."""
         if num_sims > self.max_sims:
             raise _lib.YYError(-1, f"num_sims {num_sims} > max_sims {self.max_sims} the context was sized for")
         if self.K > 1:
-            self.set_num_sims(num_sims)
+            self.set_num_sims(num_sims)                        # the last step's descents follow from it on the device
         self.begin(boards, root_players, active)
-        policy, _ = evaluator(self.planes)
+        policy, _ = evaluate(True)
         self.expand_root(policy, noise, eps)
         self.select()
         n_steps = self.steps(num_sims)
-        for s in range(n_steps):
-            policy, value = evaluator(self.planes)
-            if fused and s + 1 < n_steps:
-                self.step(policy, value)
-            else:
-                self.expand_backup(policy, value)
-                if s + 1 < n_steps:
-                    self.select()
+        if n_steps == 0:
+            return
+        if middle is not None:
+            middle(n_steps - 1)
+        else:
+            for _ in range(n_steps - 1):
+                self.step(*evaluate(False))
+        self.expand_backup(*evaluate(False))                   # last simulation: no further select
+
+    def search(self, boards, root_players, evaluator, num_sims, noise=None, eps=0.25, active=None, fused=True):
+        """evaluator(planes f32[G*K,5,R,C]) -> (policy f32[G*K,A] softmax, value f32[G*K]) on device.
+        Runs 1 + num_sims evaluator calls exactly like the reference (root call, then one per
+        simulation; with K leaves per step 1 + ceil(num_sims / K)) and returns the root visit counts int32 [G,A].  fused=False:
+        every step but the last as expand_backup + select instead of the fused step kernel."""
+        def unfused(n):
+            for _ in range(n):
+                self.expand_backup(*evaluator(self.planes))
+                self.select()
+
+        self.run_search(boards, root_players, num_sims, lambda root: evaluator(self.planes), noise, eps, active,
+                        None if fused else unfused)
         return self.root_counts()

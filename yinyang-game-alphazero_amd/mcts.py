@@ -19,6 +19,8 @@ import torch
 
 from . import engine
 from .game import YinYangLogic
+from .network import BatchedEvaluator
+from .search import LockstepSearch
 
 
 class Node:
@@ -157,7 +159,7 @@ class MCTS:
         self.A = game.getActionSize()
         self.rowcol = bool(getattr(game, "rowcol_rule", False))
         self.device = device
-        self._ctx = {}
+        self._ctx, self._searches = {}, {}     # batch size -> context, -> (network, LockstepSearch on that context's buffers)
         self.use_graph = True          # hipGraph replay of the simulation step for device-resident evaluators
 
     def _context(self, G):
@@ -165,6 +167,7 @@ class MCTS:
         if ctx is None or ctx.max_sims < self.num_simulations:
             if ctx is not None:
                 ctx.close()
+                self._searches.pop(G, None)
             ctx = engine.BatchedMCTS(G, self.R, self.C, self.num_simulations, cpuct=self.cpuct,
                                      aliased=(self.board_semantics == "aliased"), rowcol=self.rowcol,
                                      device=self.device,
@@ -175,7 +178,6 @@ class MCTS:
 
     def _capturable(self, ev):
         """True for evaluators known to do device work only: the CUDA nn.Module's predict_batch and BatchedEvaluator."""
-        from .network import BatchedEvaluator
         net = self.neural_net
         return isinstance(net, BatchedEvaluator) or (isinstance(net, torch.nn.Module) and ev == getattr(net, "predict_batch", None))
 
@@ -196,10 +198,9 @@ class MCTS:
         if self.use_graph and self._capturable(ev) and self.num_simulations > 8:
             # device-resident evaluator: replay [forward + yy_mcts_step] from a hipGraph (one host call per simulation
             # instead of one per kernel); same launches, same results as the eager loop
-            from .self_play import LockstepSearch
-            cached = getattr(ctx, "_lockstep", None)       # lives and dies with the context whose buffers it captured;
+            cached = self._searches.get(boards.shape[0])
             if cached is None or cached[0] is not self.neural_net:   # holds the network it captured alive
-                cached = ctx._lockstep = (self.neural_net, LockstepSearch(ctx, ev, use_graph=True))
+                cached = self._searches[boards.shape[0]] = (self.neural_net, LockstepSearch(ctx, ev, use_graph=True))
             cached[1].run(boards, players, self.num_simulations, noise=noise, eps=self.dirichlet_epsilon, active=active)
         else:
             ctx.search(boards, players, ev, self.num_simulations, noise=noise, eps=self.dirichlet_epsilon, active=active)
@@ -271,4 +272,4 @@ class MCTS:
     def close(self):
         for ctx in self._ctx.values():
             ctx.close()
-        self._ctx = {}
+        self._ctx, self._searches = {}, {}

@@ -14,6 +14,7 @@ their slot so the batch stays full.  Episodes shard across ranks (one process pe
 signatures.  `reference_quirks=True` reproduces Q4/Q5 of SURVEY.md (always search and mask as
 player +1, never alternate the value labels); `board_semantics="aliased"` reproduces Q2.
 """
+import contextlib
 import os
 import time
 
@@ -24,123 +25,32 @@ from . import engine
 from .game import YinYangLogic
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
+from .search import LockstepSearch
 
 DRAW = 1e-4
 
 
-# =============================================================================== graph-replayed search
-class LockstepSearch:
-    """MCTS.search for G games with the simulation loop replayed from a hipGraph.
+def _opening_book(opening_book, game, evaluator, device):
+    """An engine.OpeningBook as it is; a stone count N -> the book of every position with <= N stones, None for N <= 0."""
+    if not isinstance(opening_book, int):
+        return opening_book
+    R, C = game.getBoardSize()
+    return (engine.OpeningBook(R, C, evaluator, opening_book, rowcol=bool(getattr(game, "rowcol_rule", False)), device=device)
+            if opening_book > 0 else None)
 
-    One graph = [evaluator forward on ctx.planes] + [yy_mcts_step]; everything in it is enqueued on
-    the capture stream (the C ABI takes the stream as an argument), so a replay costs one host call
-    instead of ~60 kernel launches."""
 
-    def __init__(self, ctx, evaluator, use_graph=True, eager_sims=3, unroll=None):
-        self.ctx, self.evaluator, self.use_graph = ctx, evaluator, use_graph
-        self.eager_sims = eager_sims
-        # simulations per replayed graph: besides the one-step graph a second one holds `unroll` consecutive steps
-        # (fewer host calls, and no graph-to-graph launch gap between the steps inside it); 1 = one-step graphs only
-        self.unroll = max(1, int(os.environ.get("YY_GRAPH_UNROLL", "8") if unroll is None else unroll))
-        self.graphs = {}       # evaluated rows -> captured step
-        self.timer = None      # optional object with start()/stop() bracketing every tree-kernel launch (bench.py)
-        self._policy = self._value = None
-        self._book_version = getattr(ctx, "book_version", 0)
-        self._graph_evaluator = evaluator
-
-    @property
-    def graph(self):
-        return self.graphs.get(self.ctx.G)
-
-    @graph.setter
-    def graph(self, g):
-        if g is None:
-            self.graphs.clear()
-        else:
-            self.graphs[self.ctx.G] = g
-
-    def _evaluate(self, rows, compact=False):
-        """Evaluator on the leaf rows of the first `rows` games (all searching games must sit there); returns full-height buffers.
-        compact: pass the step's needs_eval flags to an evaluator that can skip the rows whose leaf needs no evaluation
-        (terminal revisits, mcts.py:365-366; finished or idle slots).  With K leaves per step a game has K rows."""
-        ctx = self.ctx
-        full = getattr(ctx, "rows", ctx.G)         # G * K evaluator rows
-        rows = rows * (full // ctx.G)
-        kw = {}
-        if compact and getattr(self.evaluator, "supports_compaction", False):
-            kw["needs_eval"] = ctx.needs_eval if rows >= full else ctx.needs_eval[:rows]
-        if getattr(self.evaluator, "supports_static", False):
-            kw["static"] = id(self)                # private buffers: the results are consumed by the tree kernel before this search's next call
-        if rows >= full:
-            return self.evaluator(ctx.planes, **kw)
-        policy, value = self.evaluator(ctx.planes[:rows], **kw)
-        if self._policy is None:
-            self._policy = torch.zeros((full, policy.shape[1]), dtype=torch.float32, device=ctx.device)
-            self._value = torch.zeros(full, dtype=torch.float32, device=ctx.device)
-        self._policy[:rows].copy_(policy)
-        self._value[:rows].copy_(value)
-        return self._policy, self._value
-
-    def _sim_step(self, rows):
-        policy, value = self._evaluate(rows, compact=True)
-        if self.timer is not None:
-            self.timer.start()
-        self.ctx.step(policy, value)
-        if self.timer is not None:
-            self.timer.stop()
-
-    def run(self, boards, root_players, num_sims, noise=None, eps=0.25, active=None, rows=None):
-        """rows: evaluate only leaf rows [0, rows) -- the caller guarantees every active game has an index below it
-        (SelfPlayEngine packs the live games to the front when a batch drains).  One graph per distinct `rows`."""
-        ctx = self.ctx
-        ctx.bind_evaluator(self.evaluator)                     # kept evaluations / the book belong to ONE network (may drop the book)
-        if getattr(ctx, "book_version", 0) != self._book_version or self._graph_evaluator is not self.evaluator:
-            # a captured step has its kernel arguments frozen (the book's tables) and calls the evaluator it was captured with
-            self.graphs.clear()
-            self._book_version = getattr(ctx, "book_version", 0)
-            self._graph_evaluator = self.evaluator
-        rows = ctx.G if rows is None else min(int(rows), ctx.G)
-        K = getattr(ctx, "K", 1)
-        if K > 1:
-            ctx.set_num_sims(num_sims)                         # the last step's descents follow from it on the device
-        ctx.begin(boards, root_players, active)
-        policy, _ = self._evaluate(rows)                       # mcts.py:295, value discarded
-        ctx.expand_root(policy, noise, eps)
-        ctx.select()
-        done = 0
-        n_fused = (num_sims if K == 1 else ctx.steps(num_sims)) - 1
-        gkey = rows if not hasattr(self.evaluator, "form_key") else (rows, self.evaluator.form_key(id(self)))
-        graph = self.graphs.get(gkey)
-        if self.use_graph and graph is None and n_fused > self.eager_sims:
-            for _ in range(self.eager_sims):                   # warm-up (MIOpen algo search etc.) = real sims
-                self._sim_step(rows)
-                done += 1
-            torch.cuda.synchronize(ctx.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._sim_step(rows)
-            self.graphs[gkey] = graph
-            if self.unroll > 1 and n_fused - done >= 2 * self.unroll:
-                many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(many):
-                    for _ in range(self.unroll):
-                        self._sim_step(rows)
-                self.graphs[(gkey, self.unroll)] = many
-        many = self.graphs.get((gkey, self.unroll)) if self.use_graph else None
-        if not self.use_graph:
-            graph = None
-        while done < n_fused:
-            if many is not None and n_fused - done >= self.unroll:
-                many.replay()
-                done += self.unroll
-                continue
-            if graph is not None:
-                graph.replay()
-            else:
-                self._sim_step(rows)
-            done += 1
-        policy, value = self._evaluate(rows, compact=True)     # last simulation: no further select
-        ctx.expand_backup(policy, value)
+def _play_to_completion(eng, progress=None):
+    """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples."""
+    moves = 0
+    while eng.n_alive > 0:
+        eng.play_move()
+        moves += 1
+        if moves % 8 == 0:
+            eng.ctx.status()     # a failed search (NaN from the evaluator, arena overflow) stops the run now, not at its end
+        if progress and moves % 10 == 0:
+            progress(eng)
+    eng.ctx.status()             # per-game search errors are sticky on the device: any failure of any move raises here
+    return eng.collect()
 
 
 # =============================================================================== batched engine
@@ -184,23 +94,16 @@ class SelfPlayEngine:
         self.stream = stream                       # HIP stream every launch of this engine goes to (None: the caller's current one)
         self._pending = None                       # a move enqueued by enqueue_move() and not yet finished
         self._evals_seen = 0                       # tree-context counter at the end of the last move (rows_hint)
-        if reuse_pass_value is None:
-            reuse_pass_value = (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
-        if reuse_transpositions is None:
-            reuse_transpositions = (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
-        if keep_evaluations is None:
-            keep_evaluations = (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
-        self.reuse_pass_value, self.reuse_transpositions = bool(reuse_pass_value), bool(reuse_transpositions)
-        self.keep_evaluations = bool(keep_evaluations)
+        self._stats_host = None                    # pinned record of the move's one host read, made at the first move
+        auto = (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
+        self.reuse_pass_value, self.reuse_transpositions, self.keep_evaluations = (
+            bool(auto if x is None else x) for x in (reuse_pass_value, reuse_transpositions, keep_evaluations))
         self.ctx = engine.BatchedMCTS(self.G, self.R, self.C, self.sims, cpuct=cpuct, aliased=self.aliased,
                                       rowcol=self.rowcol, device=self.device, reuse_pass_value=self.reuse_pass_value,
                                       reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations)
-        if isinstance(opening_book, int):
-            opening_book = (engine.OpeningBook(self.R, self.C, evaluator, opening_book, rowcol=self.rowcol, device=self.device)
-                            if opening_book > 0 else None)
-        self.book = opening_book
-        if opening_book is not None:
-            self.ctx.set_book(opening_book)
+        self.book = _opening_book(opening_book, game, evaluator, self.device)
+        if self.book is not None:
+            self.ctx.set_book(self.book)
         self.search = LockstepSearch(self.ctx, evaluator, use_graph=use_graph)
         self.seed = int(seed)                      # key of the per-game counter streams (csrc/yy_selfplay.hip)
         assert rng in ("philox", "numpy")
@@ -318,7 +221,6 @@ class SelfPlayEngine:
         return action
 
     def _on_stream(self):
-        import contextlib
         return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
 
     def play_move(self):
@@ -432,7 +334,7 @@ class SelfPlayEngine:
         fin_res = torch.where(done, ended, fin_res)
         fin_player = torch.where(done, self.players, fin_player)
         stats = torch.stack([searching.sum(), fin.sum()])                      # the move's one host read, taken in finish_move()
-        if getattr(self, "_stats_host", None) is None:
+        if self._stats_host is None:
             self._stats_host = torch.zeros(2, dtype=stats.dtype).pin_memory()
         self._stats_host.copy_(stats, non_blocking=True)
         event = torch.cuda.Event()
@@ -449,16 +351,7 @@ class SelfPlayEngine:
     def run(self, num_games, progress=None):
         """Play `num_games` games to completion; returns the examples (device tensors)."""
         self.begin_run(num_games)
-        moves = 0
-        while self.n_alive > 0:
-            self.play_move()
-            moves += 1
-            if moves % 8 == 0:
-                self.ctx.status()    # a failed search (NaN from the evaluator, arena overflow) stops the run now, not at its end
-            if progress and moves % 10 == 0:
-                progress(self)
-        self.ctx.status()            # per-game search errors are sticky on the device: any failure of any move raises here
-        return self.collect()
+        return _play_to_completion(self, progress)
 
     def collect(self):
         out, self.out = self.out, []
@@ -512,15 +405,10 @@ class SelfPlayLanes:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         K = max(1, min(int(lanes), int(concurrent_games)))
         self.game, self.evaluator, self.sims = game, evaluator, int(num_simulations)
-        if isinstance(opening_book, int):           # one book, shared read-only by every lane
-            R, C = game.getBoardSize()
-            opening_book = (engine.OpeningBook(R, C, evaluator, opening_book, rowcol=bool(getattr(game, "rowcol_rule", False)),
-                                               device=self.device) if opening_book > 0 else None)
-        self.book = opening_book
+        self.book = _opening_book(opening_book, game, evaluator, self.device)      # one book, shared read-only by every lane
         self.lanes = []
         for k in range(K):
             g_k = concurrent_games // K + (1 if k < concurrent_games % K else 0)
-            import contextlib
             with torch.cuda.device(self.device):
                 st = torch.cuda.Stream(device=self.device) if K > 1 else None
             # the lane's tensors are allocated under its own stream, so the caching allocator never recycles one of them
@@ -528,7 +416,7 @@ class SelfPlayLanes:
             with (torch.cuda.stream(st) if st is not None else contextlib.nullcontext()):
                 self.lanes.append(SelfPlayEngine(game, evaluator, num_simulations=num_simulations, concurrent_games=g_k, seed=seed,
                                                  device=self.device, first_game_index=first_game_index + k * game_index_stride,
-                                                 game_index_stride=K * game_index_stride, opening_book=opening_book, stream=st,
+                                                 game_index_stride=K * game_index_stride, opening_book=self.book, stream=st,
                                                  **engine_kwargs))
         torch.cuda.synchronize(self.device)      # evaluator weights / the book were written on the caller's stream
         ln = self.lanes[0]
@@ -557,16 +445,7 @@ class SelfPlayLanes:
         K = len(self.lanes)
         for k, l in enumerate(self.lanes):
             l.begin_run(shard_games(int(num_games), k, K)[0])
-        moves = 0
-        while self.n_alive > 0:
-            self.play_move()
-            moves += 1
-            if moves % 8 == 0:
-                self.ctx.status()    # a failed search (NaN from the evaluator, arena overflow) stops the run now, not at its end
-            if progress and moves % 10 == 0:
-                progress(self)
-        self.ctx.status()            # per-game search errors are sticky on the device: any failure of any move raises here
-        return self.collect()
+        return _play_to_completion(self, progress)
 
     def collect(self):
         torch.cuda.synchronize(self.device)
@@ -586,7 +465,6 @@ def shard_games(total, rank, world):
     union over ranks is exactly range(total) for any world size, so per-game ids do not depend on it."""
     count = total // world + (1 if rank < total % world else 0)
     return count, rank, world
-
 
 
 def example_capacity(total_games, world, rows_per_game):
