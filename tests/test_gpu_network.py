@@ -499,3 +499,27 @@ def test_evaluator_rows_do_not_depend_on_the_batch(R):
         p, v = ev(planes, needs_eval=flags, static=True)
         live = flags.bool()
         assert torch.equal(p[live], p_ref[idx][live]) and torch.equal(v[live], v_ref[idx][live]), ("compacted", M)
+
+
+@pytest.mark.parametrize("mode", ["f16x3", "f16x3r"])
+def test_split_f16_call_with_compaction_and_owner_buffers(mode):
+    """BatchedEvaluator.__call__ of both split-f16 towers with a row list and an owner's static buffers (8x8, 128 x 1, 5 boards,
+    rows 0 / 2 / 4 flagged): the flagged rows hold the bits of the dense call, and the owner's next call returns the same
+    tensor objects."""
+    import torch
+    import yinyang_game_alphazero_amd as pkg
+    net = _randomized_net(pkg, pkg.YinYangGame(8, 8), 1, 7)
+    ev = pkg.BatchedEvaluator(net, mode)
+    assert ev.mode == "f16x3" and ev.use_h3r == (mode == "f16x3r")
+    boards = np.random.default_rng(3).integers(-1, 2, size=(5, 8, 8)).astype(np.int8)
+    planes = pkg.engine.encode_planes(torch.from_numpy(boards).cuda())
+    p_all, v_all = ev(planes)
+    assert bool(torch.isfinite(p_all).all()) and bool((p_all.sum(1) - 1).abs().max() < 1e-5)
+    flags = torch.tensor([1, 0, 1, 0, 1], dtype=torch.uint8, device="cuda")
+    token = object()
+    p, v = ev(planes, needs_eval=flags, static=token)
+    keep = flags.bool()
+    assert torch.equal(p[keep], p_all[keep]) and torch.equal(v[keep], v_all[keep])
+    p2, v2 = ev(planes, needs_eval=flags, static=token)
+    assert p2 is p and v2 is v
+    assert torch.equal(p[keep], p_all[keep]) and torch.equal(v[keep], v_all[keep])
