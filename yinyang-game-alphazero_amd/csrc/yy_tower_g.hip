@@ -452,6 +452,9 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
 //   * weights: the packing of k_tower_g.  A wave's A operand is the 8 KB of k_tower_g's waves 2mh and 2mh+1 ([M block 4][part 2]
 //     [lane 64][8 f16]); both nh waves load the same bytes (the second request is served by the vector L1).  Ring of D = 3 such
 //     chunks (96 registers) next to 128 accumulators and 32 fragment registers: no AGPR <-> VGPR copies, no spill.
+//   * row ownership: a lane fetches its A rows so that the two M blocks of a pair hold 8 consecutive output channels of its column
+//     (load_w22, same packed bytes): the epilogue stores 16-byte pieces, 16 ds_write_b128 per lane and layer instead of 32
+//     ds_write_b64, 2-way instead of 4-way conflicted on the 32 store banks (288 B = 8 banks per column).
 //   * skips: wave nh = 0 drops block 0 at the three dy = -1 taps, nh = 1 block 7 at the three dy = +1 taps (3 of its 36 (tap,
 //     block) pairs).  nh selects one of two compiled copies of the tower, so the skips stay compile-time.
 // Every output element keeps its MFMA chain -- [layer][channel group][tap], acc1 / acc2, the same row and column of the same-shaped
@@ -460,7 +463,7 @@ k_tower_g(const float *__restrict__ planes, const unsigned char *__restrict__ we
 // computed once per kernel (Taps22: the peeled channel group reads at them directly, the looped one adds its channel offset)
 // against rowbase / okmask selects (81 address registers do not fit at NB = 9); bias rows from an LDS table (one ds_read_b128 per
 // M block) against SGPRs and per-lane selects (NB = 9 has no LDS to spare); relu_max (one v_maximum3_f32) against relu_keep_nan;
-// the ring depth; the two weight offsets of load_w22; off22 against off_board; and run_chunk22 / run_layer22 next to run_chunk /
+// the ring depth; the two weight offsets and the row ownership of load_w22; off22 against off_board; and run_chunk22 / run_layer22 next to run_chunk /
 // run_layer, whose scheduling barriers and address forms are what each form's speed consists of.
 template <int D_> struct Geo22 : Geo<4, 8, D_, true> {   // rows, parts, zero rows, RES_OFF and weight chunks of k_tower_g<4, 8, D, true>
     static constexpr int NBW = 4, MBW = 4;                               // column blocks and M blocks of a wave
@@ -500,15 +503,46 @@ template <class GEO, int NH> __device__ __forceinline__ void make_taps22(Taps22 
     }
 }
 
-// A wave's A fragments of one weight chunk are WChunk<4>: 32 registers, the fragments of k_tower_g's waves 2mh and 2mh + 1.
-// wbase: uniform chunk address; voff[2] = this lane's offsets of M blocks 0-1 and 2-3 (two registers, so that every load is
-// "uniform base + lane offset + immediate" with no per-chunk 64-bit address arithmetic)
+// A wave's A fragments of one weight chunk are WChunk<4>: 32 registers, rows of the fragments of k_tower_g's waves 2mh and 2mh + 1
+// (8 KB of the chunk: [fragment 4][part 2][lane slot 64][16 B], fragment f = channels 64mh + 16f .. + 15, slot = row + 16 * k group).
+// ROW OWNERSHIP: an MFMA's D rows 4kg + i sit in lane group kg, so with k_tower_g's rows a lane would hold channels 16m + 4kg + i of M
+// block m: four separated 8-byte pieces of its column's LDS row.  Here row 4kg + i of M block 2j + e is channel 32j + 8kg + 4e + i
+// instead: the two M blocks of pair j give a lane 8 consecutive channels, one 16-byte store per part (tower22's epilogue).  Which
+// channel a row of an M block stands for enters no output element's MFMA chain (same operands, same k order, same accumulator), so
+// every bit stays.  The re-assignment is done here, by where a lane fetches its A rows from: lane (r = lane & 15, q = lane >> 4)
+// reads, for M block 2j + e, fragment 2j + (r >> 3), slot 8 * ((r >> 2) & 1) + 4e + (r & 3) + 16q.  w22_lane is the lane's part of
+// that offset, w22_imm the part the instruction carries.
+constexpr uint32_t w22_lane(int lane) {
+    const int r = lane & 15, q = lane >> 4;
+    return (uint32_t)((r >> 3) * 2048 + (8 * ((r >> 2) & 1) + (r & 3) + 16 * q) * 16);
+}
+constexpr uint32_t w22_imm(int j, int e, int p) { return (uint32_t)(j * 4096 + e * 64 + p * 1024); }
+// over (j, e, p, lane) the 16-byte pieces fetched are each piece of the wave's 8 KB exactly once, and the piece of (j, e, p, lane)
+// is part p, k group q of channel 32j + 8 * (r >> 2) + 4e + (r & 3): row r = 4kg + i of M block 2j + e is channel 32j + 8kg + 4e + i
+constexpr bool w22_map_ok() {
+    bool seen[512] = {};
+    for (int j = 0; j < 2; j++)
+        for (int e = 0; e < 2; e++)
+            for (int p = 0; p < 2; p++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const uint32_t o = w22_imm(j, e, p) + w22_lane(lane);
+                    if (o % 16 != 0 || o >= 8192 || seen[o / 16]) return false;
+                    seen[o / 16] = true;
+                    const int frag = (int)(o / 2048), part = (int)(o / 1024) & 1, slot = (int)(o % 1024) / 16;
+                    const int r = lane & 15, kg = r >> 2, i = r & 3;
+                    if (part != p || (slot >> 4) != (lane >> 4) || 16 * frag + (slot & 15) != 32 * j + 8 * kg + 4 * e + i) return false;
+                }
+    return true;
+}
+static_assert(w22_map_ok(), "load_w22: a bijection onto the wave's 8 KB of a chunk that gives a lane 8 consecutive channels per M-block pair");
+// wbase: uniform chunk address; voff[j] = 8192 * mh + w22_imm(j, 0, 0) + w22_lane(lane) (two registers, so that every load is
+// "uniform base + lane offset + immediate" with no per-chunk 64-bit address arithmetic and every immediate fits the instruction)
 __device__ __forceinline__ void load_w22(WChunk<4> &w, const unsigned char *wbase, const uint32_t (&voff)[2]) {
 #pragma unroll
     for (int m = 0; m < 4; m++) {
-        const u32x4 *p = (const u32x4 *)(wbase + voff[m >> 1]);
-        w.h[m] = __builtin_bit_cast(f16x8, p[128 * (m & 1)]);
-        w.l[m] = __builtin_bit_cast(f16x8, p[128 * (m & 1) + 64]);
+        const unsigned char *p = wbase + voff[m >> 1];
+        w.h[m] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + w22_imm(0, m & 1, 0)));
+        w.l[m] = __builtin_bit_cast(f16x8, *(const u32x4 *)(p + w22_imm(0, m & 1, 1)));
     }
 }
 
@@ -566,14 +600,15 @@ __device__ __forceinline__ void run_layer22(f32x4 (&acc1)[4][4], f32x4 (&acc2)[4
 }
 
 // Everything of wave column half NH up to the last layer's epilogue: the weight ring and the prologue (plus the bias table), then the
-// stem and the CH -> CH layers, each followed by its epilogue.  A lane holds output channels 64mh + 16m + 4kg + 0..3 of column (4NH + b)*16 + n16.
+// stem and the CH -> CH layers, each followed by its epilogue.  A lane holds, of column (4NH + b)*16 + n16, output channels 64mh + 32j + 8kg + 4e + 0..3
+// in M block 2j + e (load_w22): 8 consecutive channels per pair j, stored as one 16-byte piece per part.
 template <class GEO, int NH>
 __device__ __forceinline__ void tower22(unsigned char *lds, const float *__restrict__ planes, const unsigned char *__restrict__ weights,
                                         const float *__restrict__ bias, const int *__restrict__ rows, int g0, int n_live, int R, int C,
                                         int TB, int n_layers, int lane, int wave, float in_scale, float acc_scale) {
     constexpr int NW = GEO::NW, D = GEO::D, CH = GEO::CH, RS = GEO::RS, NT = 64 * NW;
     const int cells = R * C, n_tower = 9 + 9 * NW * (n_layers - 1);
-    uint32_t voff[2] = {(uint32_t)((wave >> 1) * 8192 + lane * 16), (uint32_t)((wave >> 1) * 8192 + 4096 + lane * 16)};
+    uint32_t voff[2] = {(uint32_t)((wave >> 1) * 8192) + w22_imm(0, 0, 0) + w22_lane(lane), (uint32_t)((wave >> 1) * 8192) + w22_imm(1, 0, 0) + w22_lane(lane)};
     asm volatile("" : "+v"(voff[1]));
     WChunk<4> W[D];
 #pragma unroll
@@ -588,20 +623,25 @@ __device__ __forceinline__ void tower22(unsigned char *lds, const float *__restr
     int chunk = 0;
     auto epilogue = [&](const int L, f32x4 (&acc1)[4][4], f32x4 (&acc2)[4][4], auto conv2_tag, auto keep_tag) {
         constexpr bool CONV2 = decltype(conv2_tag)::value, KEEP = decltype(keep_tag)::value;
-        const unsigned char *bl = lds + GEO::BIAS_OFF + (L * CH + mh * 64 + kg * 4) * 4;
+        const unsigned char *bl = lds + GEO::BIAS_OFF + (L * CH + mh * 64 + kg * 8) * 4;
         f32x4 bq[4];
 #pragma unroll
-        for (int m = 0; m < 4; m++) bq[m] = *(const f32x4 *)(bl + m * 64);
+        for (int m = 0; m < 4; m++) bq[m] = *(const f32x4 *)(bl + (m >> 1) * 128 + (m & 1) * 16);
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const uint32_t rowoff = (uint32_t)(((4 * NH + b) * 16 + n16) * RS);
 #pragma unroll
-            for (int m = 0; m < 4; m++) {
-                u32x2 hi, lo;
-                epilogue_quad<CONV2, KEEP, relu_max>(acc1[b][m], acc2[b][m], acc_scale, bq[m], res_lds + (m * 4 + b) * 1024, hi, lo);
-                const uint32_t co2 = (uint32_t)((mh * 64 + m * 16 + kg * 4) * 2);
-                *(u32x2 *)(lds + rowoff + co2) = hi;
-                *(u32x2 *)(lds + GEO::PART_BYTES + rowoff + co2) = lo;
+            for (int j = 0; j < 2; j++) {
+                u32x2 hi[2], lo[2];
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const int m = 2 * j + e;
+                    epilogue_quad<CONV2, KEEP, relu_max>(acc1[b][m], acc2[b][m], acc_scale, bq[m], res_lds + (m * 4 + b) * 1024, hi[e], lo[e]);
+                }
+                // 16-byte pieces at row + 16 * k: the slots the B fragment reads use (one 8-lane store group = 8 columns of one piece)
+                const uint32_t co2 = (uint32_t)((mh * 64 + j * 32 + kg * 8) * 2);
+                *(u32x4 *)(lds + rowoff + co2) = (u32x4){hi[0].x, hi[0].y, hi[1].x, hi[1].y};
+                *(u32x4 *)(lds + GEO::PART_BYTES + rowoff + co2) = (u32x4){lo[0].x, lo[0].y, lo[1].x, lo[1].y};
             }
         }
     };
