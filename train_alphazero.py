@@ -7,7 +7,7 @@
 
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
---dist-backend, --reference-format.  `--mode train` runs
+--dist-backend, --reference-format, --leaves-per-step.  `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
 """
@@ -68,14 +68,27 @@ def parse_args(argv=None):
     p.add_argument("--channels", type=int, default=128)
     p.add_argument("--blocks", type=int, default=10)
     p.add_argument("--leaves-per-step", type=int, default=1,
-                   help="--mode evaluate: K descents per game per search step with virtual visits, evaluated in one batch (a "
-                        "search then takes ceil(simulations / K) evaluator calls; 1 = the reference's search; changes which "
-                        "moves are picked).  --mcts-threads stays inert")
+                   help="K descents per game per search step with virtual visits, evaluated in one batch (a search then takes "
+                        "ceil(simulations / K) evaluator calls; 1 = the reference's search; changes which moves are picked): the "
+                        "searches of --mode evaluate, of --mode self-play and of --mode train (self-play and arena).  In "
+                        "self-play K > 1 turns --evaluation-reuse auto off and builds no opening book (--opening-book-stones is "
+                        "ignored); not with --board-semantics aliased or --reference-quirks.  --mcts-threads stays inert")
     return p.parse_args(argv)
+
+
+def refused(args):
+    """The flag combinations no search runs with, as a one-line message (None: none), from the parsed flags alone."""
+    if args.leaves_per_step > 1 and args.mode in ("self-play", "train"):
+        for flag, given in (("--board-semantics aliased", args.board_semantics == "aliased"), ("--reference-quirks", args.reference_quirks)):
+            if given:
+                return f"train_alphazero.py: --leaves-per-step {args.leaves_per_step} searches copied boards without the reference's quirks: not with {flag}"
+    return None
 
 
 def main(argv=None):
     args = parse_args(argv)
+    if refused(args):
+        sys.exit(refused(args))
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -109,7 +122,7 @@ def main(argv=None):
                            num_simulations=args.simulations, num_epochs=args.epochs, num_workers=args.workers,
                            mcts_threads=args.mcts_threads, nn_mode=args.nn, concurrent_games=args.concurrent_games,
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
-                           lr=args.lr, batch_size=args.batch_size)
+                           lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -134,7 +147,8 @@ def main(argv=None):
                                        num_channels=args.channels, num_res_blocks=args.blocks,
                                        reference_format=args.reference_format,
                                        evaluation_reuse=None if args.evaluation_reuse == "auto" else False,
-                                       opening_book_stones=args.opening_book_stones, lanes=args.lanes or None)
+                                       opening_book_stones=0 if args.leaves_per_step > 1 else args.opening_book_stones,
+                                       lanes=args.lanes or None, leaves_per_step=args.leaves_per_step)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

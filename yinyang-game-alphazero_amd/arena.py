@@ -286,7 +286,10 @@ class AlphaZero:
     def __init__(self, game, model_dir="models", data_dir="data", num_iterations=100, num_episodes=100,
                  num_simulations=800, num_epochs=10, temperature_threshold=10, update_threshold=0.6, num_workers=1,
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
-                 concurrent_games=4096, device=None, lr=0.001, batch_size=64):
+                 concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1):
+        """leaves_per_step K > 1 (not in the reference): leaf-parallel searches in the loop's self-play (SelfPlayManager
+        leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step)."""
+        self.leaves_per_step = max(1, int(leaves_per_step))
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold
@@ -315,7 +318,8 @@ class AlphaZero:
                                        num_workers=self.num_workers, num_simulations=self.num_simulations,
                                        temperature_threshold=self.temperature_threshold, nn_mode=self.nn_mode,
                                        num_channels=self.num_channels, num_res_blocks=self.num_res_blocks,
-                                       concurrent_games=self.concurrent_games, seed=len(self.history))
+                                       concurrent_games=self.concurrent_games, seed=len(self.history),
+                                       leaves_per_step=self.leaves_per_step)
 
     def train(self):
         # the reference passes num_iterations=1 and ignores --epochs/--batch-size/--lr (alphazero.py:120-127,
@@ -343,7 +347,8 @@ class AlphaZero:
         mine = 2 * (pairs // world + (1 if rank < pairs % world else 0)) + (n % 2 if rank == 0 else 0)
         cur = _load_evaluator(self.game, current_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
-        res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank).play(mine)
+        res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
+                     leaves_per_step=self.leaves_per_step).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)

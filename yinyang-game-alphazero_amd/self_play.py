@@ -39,6 +39,30 @@ def _opening_book(opening_book, game, evaluator, device):
             if opening_book > 0 else None)
 
 
+def _leaf_parallel(leaves_per_step, board_semantics="copied", reference_quirks=False, evaluation_reuse=(), opening_book=None):
+    """K = leaves_per_step as the tree context takes it (>= 1).  K > 1 searches copied boards, evaluates every leaf and has no
+    book (engine.BatchedMCTS refuses the rest), and is not offered under the literal reproduction of the reference's play
+    (reference_quirks): a combination that asks for one of these EXPLICITLY raises ValueError -- on the host, before anything
+    touches the device.  evaluation_reuse: the reuse options as given (None = the default, which K > 1 resolves to off);
+    opening_book: an engine.OpeningBook or a stone count (None and counts <= 0 mean no book)."""
+    K = max(1, int(leaves_per_step))
+    if K == 1:
+        return K
+    bad = []
+    if board_semantics == "aliased":
+        bad.append('board_semantics="aliased"')
+    if reference_quirks:
+        bad.append("reference_quirks=True")
+    if any(x is not None and bool(x) for x in evaluation_reuse):
+        bad.append("evaluation reuse (reuse_pass_value / reuse_transpositions / keep_evaluations / evaluation_reuse)")
+    if opening_book is not None and not (isinstance(opening_book, int) and opening_book <= 0):
+        bad.append("an opening book")
+    if bad:
+        raise ValueError(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
+                         f"book -- not with {', '.join(bad)}")
+    return K
+
+
 def _play_to_completion(eng, progress=None):
     """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples."""
     moves = 0
@@ -60,7 +84,7 @@ class SelfPlayEngine:
                  board_semantics="copied", reference_quirks=False, use_graph=True, seed=0,
                  device=None, first_game_index=0, game_index_stride=1, compact_tail=True, row_tiers=None,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
-                 opening_book=None, stream=None, rng="philox", numpy_seeds=None):
+                 opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1):
         """reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
         declares `row_independent` (the split-f16 evaluator does).  The reference asks the network for every leaf: a node
         without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move order of the same search
@@ -77,8 +101,19 @@ class SelfPlayEngine:
         index) draws np.random.dirichlet at the game's first search (ai/mcts.py:305) and np.random.choice for every move
         (ai/self_play.py:146, 160) exactly where SelfPlayWorker.play_game draws from the global stream after np.random.seed(s) --
         a batch of games then replays the reference's transcripts move for move (tests: episodes_*.npz).  One host round
-        trip of (pi, legal mask) per move: a parity mode, not the throughput path."""
+        trip of (pi, legal mask) per move: a parity mode, not the throughput path.
+        leaves_per_step K > 1 (default 1 = the reference's search, today's launches and games): every search of the engine is
+        leaf-parallel (engine.BatchedMCTS leaves_per_step): K descents per game and step with virtual visits, their leaves
+        evaluated in one launch of up to K rows per game, ceil(num_simulations / K) steps per move -- for runs with few
+        concurrent games, where a step costs the same whatever it carries.  The move around the search is unchanged (pass
+        handling, root noise, the example record, the draws): it reads the root, and the root holds num_simulations visits at
+        any K.  The None defaults of the three reuse options then mean OFF and no book is built: the leaf-parallel selection
+        (k_mcts_multi) looks nothing up -- no kept pass value, no evaluation cache, no book -- and the tree context refuses the
+        combination at create.  Asking for one of them explicitly, for aliased boards or for reference_quirks together with
+        K > 1 raises ValueError.  It changes which moves a search picks."""
         assert board_semantics in ("aliased", "copied")
+        self.K = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks,
+                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book)
         self.game = game
         self.R, self.C = game.getBoardSize()
         self.A = self.R * self.C
@@ -95,12 +130,13 @@ class SelfPlayEngine:
         self._pending = None                       # a move enqueued by enqueue_move() and not yet finished
         self._evals_seen = 0                       # tree-context counter at the end of the last move (rows_hint)
         self._stats_host = None                    # pinned record of the move's one host read, made at the first move
-        auto = (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
+        auto = self.K == 1 and (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
         self.reuse_pass_value, self.reuse_transpositions, self.keep_evaluations = (
             bool(auto if x is None else x) for x in (reuse_pass_value, reuse_transpositions, keep_evaluations))
         self.ctx = engine.BatchedMCTS(self.G, self.R, self.C, self.sims, cpuct=cpuct, aliased=self.aliased,
                                       rowcol=self.rowcol, device=self.device, reuse_pass_value=self.reuse_pass_value,
-                                      reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations)
+                                      reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations,
+                                      leaves_per_step=self.K)
         self.book = _opening_book(opening_book, game, evaluator, self.device)
         if self.book is not None:
             self.ctx.set_book(self.book)
@@ -130,8 +166,9 @@ class SelfPlayEngine:
         self.positions = 0
         self._ar = torch.arange(G, device=dev)
         self._ones = torch.ones(G, dtype=torch.int8, device=dev)
-        # draining batch: once no new game will start, live games are packed to the front and only the first `rows`
-        # leaf rows are evaluated (rows = the smallest tier that holds them; one captured step per tier)
+        # draining batch: once no new game will start, live games are packed to the front and only the leaf rows of the first
+        # `rows` GAMES are evaluated (rows = the smallest tier that holds them; one captured step per tier).  rows and the tiers
+        # count games at any leaves_per_step: LockstepSearch turns them into rows * K evaluator rows
         self.compact_tail = bool(compact_tail)
         self.rows = G
         self.tiers = sorted({G} | ({m for m in range(1024, G, 1024)} | {m for m in (512, 256) if m < G}
@@ -239,7 +276,7 @@ class SelfPlayEngine:
             # the stream is idle here: rows the evaluator was asked for per step of this move (also surfaces a failed search now)
             evals = self.ctx.status()["evals"]
             if evals >= self._evals_seen:
-                self.evaluator.rows_hint(id(self.search), (evals - self._evals_seen) / float(self.sims + 1))
+                self.evaluator.rows_hint(id(self.search), (evals - self._evals_seen) / float(self.ctx.steps(self.sims) + 1))
             self._evals_seen = evals
         n_pos, n_fin = int(host[0]), int(host[1])
         self.positions += n_pos
@@ -401,7 +438,13 @@ class SelfPlayLanes:
     Lane k of K plays the games first_game_index + (k + j*K) * game_index_stride, j = 0, 1, ..."""
 
     def __init__(self, game, evaluator, num_simulations=800, concurrent_games=4096, lanes=2, seed=0, device=None,
-                 first_game_index=0, game_index_stride=1, opening_book=None, **engine_kwargs):
+                 first_game_index=0, game_index_stride=1, opening_book=None, leaves_per_step=1, **engine_kwargs):
+        """leaves_per_step: every lane's searches are leaf-parallel (SelfPlayEngine leaves_per_step; same defaults, same
+        refusals, raised here before the book or any lane is built).  The other keywords are SelfPlayEngine's."""
+        self.leaves_per_step = _leaf_parallel(leaves_per_step, engine_kwargs.get("board_semantics", "copied"),
+                                              engine_kwargs.get("reference_quirks", False),
+                                              [engine_kwargs.get(k) for k in ("reuse_pass_value", "reuse_transpositions", "keep_evaluations")],
+                                              opening_book)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         K = max(1, min(int(lanes), int(concurrent_games)))
         self.game, self.evaluator, self.sims = game, evaluator, int(num_simulations)
@@ -417,7 +460,7 @@ class SelfPlayLanes:
                 self.lanes.append(SelfPlayEngine(game, evaluator, num_simulations=num_simulations, concurrent_games=g_k, seed=seed,
                                                  device=self.device, first_game_index=first_game_index + k * game_index_stride,
                                                  game_index_stride=K * game_index_stride, opening_book=self.book, stream=st,
-                                                 **engine_kwargs))
+                                                 leaves_per_step=self.leaves_per_step, **engine_kwargs))
         torch.cuda.synchronize(self.device)      # evaluator weights / the book were written on the caller's stream
         ln = self.lanes[0]
         self.G = sum(l.G for l in self.lanes)
@@ -564,7 +607,10 @@ class SelfPlayWorker:
 
     def __init__(self, game, model_path, num_simulations=800, num_games=1, temperature_threshold=10,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
-                 board_semantics="aliased", reference_quirks=True, neural_net=None, device=None):
+                 board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1):
+        """leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
+        board_semantics="copied" and reference_quirks=False, which are not this class's defaults."""
+        self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks)
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
         self.temperature_threshold = temperature_threshold
@@ -580,7 +626,8 @@ class SelfPlayWorker:
         self.neural_net = neural_net
         self.mcts = MCTS(game, neural_net, num_simulations=num_simulations, cpuct=cpuct,
                          dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                         num_threads=num_parallel, board_semantics=board_semantics, device=device)
+                         num_threads=num_parallel, board_semantics=board_semantics, device=device,
+                         leaves_per_step=self.leaves_per_step)
 
     def play_game(self):
         game, examples = self.game, []
@@ -652,9 +699,14 @@ class SelfPlayManager:
                  temperature_threshold=10, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0,
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
-                 opening_book_stones=None, lanes=None):
+                 opening_book_stones=None, lanes=None, leaves_per_step=1):
         """evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
-        per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference."""
+        per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference.
+        leaves_per_step K > 1: leaf-parallel searches (SelfPlayEngine leaves_per_step); evaluation_reuse=None then means off and
+        opening_book_stones=None no book; evaluation_reuse=True, a book, aliased boards or reference_quirks with it raise
+        ValueError here."""
+        self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks, (evaluation_reuse,),
+                                              opening_book_stones)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -683,12 +735,12 @@ class SelfPlayManager:
         evaluator = BatchedEvaluator(net, self.nn_mode)
         book = self.opening_book_stones
         if book is None:
-            auto = (self.evaluation_reuse is not False and self.board_semantics == "copied" and mine >= 1024
+            auto = (self.leaves_per_step == 1 and self.evaluation_reuse is not False and self.board_semantics == "copied" and mine >= 1024
                     and self.game.getActionSize() <= 64 and getattr(evaluator, "row_independent", False))
             book = 8 if auto else 0
         slots = max(1, min(self.concurrent_games, mine))
         eng = SelfPlayLanes(self.game, evaluator, num_simulations=self.num_simulations, opening_book=int(book),
-                            lanes=self.lanes if self.lanes else (2 if slots >= 512 else 1),
+                            lanes=self.lanes if self.lanes else (2 if slots >= 512 else 1), leaves_per_step=self.leaves_per_step,
                              concurrent_games=slots, cpuct=self.cpuct,
                              dirichlet_alpha=self.dirichlet_alpha, dirichlet_epsilon=self.dirichlet_epsilon,
                              temperature_threshold=self.temperature_threshold, board_semantics=self.board_semantics,
@@ -708,15 +760,16 @@ class SelfPlayManager:
 
 
 def generate_self_play_data(game, model_path, output_dir, num_games=100, num_workers=1, num_simulations=800,
-                            reference_format=False, **engine_kwargs):
+                            reference_format=False, leaves_per_step=1, **engine_kwargs):
     """self_play.py:337-387: same arguments and the same file name pattern.  The .npz holds plain
     tensors (`states` int8 [N,R,C], `policies` float64 [N,A], `values` float64 [N]; `boards` is an
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
-    layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file."""
+    layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
+    leaves_per_step: SelfPlayManager's; the other keywords are SelfPlayManager's too."""
     os.makedirs(output_dir, exist_ok=True)
     games_per_worker = max(1, num_games // num_workers)               # :355 (remainder dropped)
     manager = SelfPlayManager(game, model_path, num_workers=num_workers, games_per_worker=games_per_worker,
-                              num_simulations=num_simulations, **engine_kwargs)
+                              num_simulations=num_simulations, leaves_per_step=leaves_per_step, **engine_kwargs)
     ex = manager.generate_games_parallel()
     filename = publish_examples_file(ex, output_dir, reference_format)
     generate_self_play_data.last_stats = manager.stats
