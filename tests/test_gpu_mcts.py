@@ -462,6 +462,90 @@ def test_opening_book_returns_the_same_search(pkg, shape, stones, G, rowcol):
         assert np.array_equal(res["book+cache"][0][g], O.search_hash(bh[g], int(ph[g]), sims, 1, 6, 4, flags=int(rowcol)).counts), g
 
 
+def _opening_batch(E, G):
+    """4x4 roots: the first half of the G games on the empty board, the other half after one legal ply on distinct cells."""
+    import torch
+    boards = torch.zeros((G, 4, 4), dtype=torch.int8, device="cuda")
+    players = torch.ones(G, dtype=torch.int8, device="cuda")
+    cells = torch.tensor([0, 1, 2, 3, 5, 6, 10, 15][:G // 2], dtype=torch.int32, device="cuda")
+    E.step_(boards[G // 2:], players[G // 2:], cells)
+    assert int((boards != 0).sum()) == G // 2 and int((players == -1).sum()) == G // 2
+    return boards, players
+
+
+def test_book_lookup_finds_every_position_the_book_stores(pkg):
+    """Book build (k_book_insert) and book lookup (leaf_lookup) must walk the same probe sequence: a search whose every leaf
+    has at most the book's 4 stones (3 simulations from roots with 0 or 1 stones: a leaf of simulation s has at most s stones
+    more than its root) may ask the evaluator only for positions the book does NOT store.  A lookup that drifted from the
+    build would still return the right counts, from evaluator rows for stored positions: those rows are what is caught."""
+    import torch
+    from hash_eval import hash_eval_torch
+    E = pkg.engine
+    G, sims = 16, 3
+    ev = lambda p: hash_eval_torch(p, 6, 4)
+    book = E.OpeningBook(4, 4, ev, 4)
+    boards, players = _opening_batch(E, G)
+    plain = E.BatchedMCTS(G, 4, 4, sims)
+    c0 = plain.search(boards, players, ev, sims)
+    want = (c0, *plain.root_stats(), plain.root_policy())
+    plain.status()
+    m = E.BatchedMCTS(G, 4, 4, sims)
+    m.set_book(book)
+    asked, calls = [], [0]
+
+    def recording(planes):
+        if calls[0] > 0:                                  # the root call evaluates every root: not a leaf lookup
+            rows = np.flatnonzero(m.needs_eval.cpu().numpy())
+            asked.extend(planes_to_boards(planes.cpu().numpy())[rows])
+        calls[0] += 1
+        return ev(planes)
+
+    c1 = m.search(boards, players, recording, sims)
+    got = (c1, *m.root_stats(), m.root_policy())
+    k = m.status()
+    stored = {tuple(r) for r in book.table_keys[book.meta != 0].cpu().numpy().tolist()}
+    assert len(stored) == book.stored
+    if asked:
+        black, white = E.pack_boards(torch.from_numpy(np.stack(asked)).cuda())
+        keys = torch.cat([black.t(), white.t()], dim=1).cpu().numpy().tolist()
+        assert not [r for r in keys if tuple(r) in stored]                                      # (a)
+    assert k["transposition_hits"] + k["evals"] + k["terminal_revisits"] + k["reused_values"] == sims * G, k   # (b)
+    assert k["evals"] == len(asked) and k["transposition_hits"] > 0, k                          # (c)
+    for a, b in zip(want, got):                                                                 # (d)
+        assert torch.equal(a, b)
+    plain.close()
+    m.close()
+
+
+def test_set_book_and_clear_update_the_launch_view(pkg):
+    """yy_mcts_set_book and yy_mcts_cache_clear act on what the NEXT launch sees: with the book set on top of a kept cache a
+    repeated search needs no evaluator row; with the book unset and the cache cleared it is the first search again, row for
+    row.  A launch view that still held the book's table would report more hits and fewer rows in the third search."""
+    import torch
+    from hash_eval import hash_eval_torch
+    E = pkg.engine
+    G, sims = 8, 32
+    ev = lambda p: hash_eval_torch(p, 6, 4)
+    book = E.OpeningBook(4, 4, ev, 4)
+    boards, players = _opening_batch(E, G)
+    m = E.BatchedMCTS(G, 4, 4, sims, reuse_transpositions=True, keep_evaluations=True)
+    c1 = m.search(boards, players, ev, sims)
+    k1 = m.status()
+    m.set_book(book)
+    m.reset_counters()
+    c2 = m.search(boards, players, ev, sims)
+    k2 = m.status()
+    m.set_book(None)
+    m.clear_evaluation_cache()
+    m.reset_counters()
+    c3 = m.search(boards, players, ev, sims)
+    k3 = m.status()
+    m.close()
+    assert torch.equal(c1, c2) and torch.equal(c1, c3)
+    assert k1["evals"] > 0 and k2["evals"] == 0, (k1, k2)
+    assert (k3["evals"], k3["transposition_hits"]) == (k1["evals"], k1["transposition_hits"]), (k1, k3)
+
+
 def test_evaluation_cache_with_aliased_boards_and_clear(pkg):
     """The cache is keyed by the position, so it also serves the literal aliased-board search (the shared board a leaf is
     evaluated on is looked up as it is at that moment); yy_mcts_cache_clear forgets everything (a new network)."""

@@ -484,116 +484,167 @@ struct GameState {
     int8_t root_player;
     uint8_t active, err, root_w_is_py;
     uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
-    int32_t leaf_src;       // >= 0: slot of the evaluation cache that holds this leaf's position (no evaluator row), else -1
-    int32_t leaf_ec_slot;   // leaf_src < 0: the cache slot this leaf's evaluation goes into
+    int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot)
+    int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
     uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
     int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
     LeafRec leaf;           // K = 1: the pending leaf
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
 };
 
-struct MultiDev {  // by-value kernel argument of the K > 1 kernels
-    int32_t K;
+// A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
+// game g's evaluation cache another (cache_of: a slice of the context's ec arrays).
+struct PosTable {
+    uint32_t *meta;         // [slots]  0 = never used; cache: epoch << 8 | stones, book: 1
+    uint64_t *key;          // [slots, 2*NW]  the position
+    float *val;             // [slots]  the evaluator's value
+    float *pol;             // [slots, A]  the evaluator's policy row
+    uint32_t mask;          // slots - 1 (slots is a power of two)
+};
+
+// The device's view of a context, the by-value argument of every context kernel: filled once by yy_mcts_create (the book
+// part by yy_mcts_set_book) and kept in the context, so that a launch passes what the host itself allocates through.
+struct MctsDev {
+    YYGeo geo;
+    int32_t G;
+    uint32_t aliased, reuse;
+    float cpuct;
+    int64_t node_cap, edge_cap, path_cap;
+    uint4 *edges, *nodes;
+    uint64_t *nboard, *gboard;
+    int32_t *path;
+    // evaluation cache (YY_FLAG_REUSE_TRANSPOSITIONS / YY_FLAG_KEEP_EVALUATIONS): the arrays of all G games, mask + 1 slots
+    // per game; meta == nullptr: off
+    PosTable ec;
+    uint32_t ec_keep;
+    // shared book of pre-evaluated positions (yy_mcts_set_book; arrays owned by the caller, read-only here); meta == nullptr: none
+    PosTable bk;
+    int32_t bk_stones;
+    GameState *state;
+    float *sqrt_tab;
+    int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
+};
+
+struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
+    int32_t K;               // leaves per step (1: one descent per game per step)
     LeafRec *leaves;         // [G*K]
     int32_t *mst;            // [G][2] = {simulations of the current search, descents of the pending step}
 };
 
 struct yy_mcts {
     yy_mcts_config cfg;
-    YYGeo geo;
-    int64_t node_cap, edge_cap, path_cap;
-    uint4 *edges, *nodes;
-    uint64_t *nboard, *gboard;
-    int32_t *path;
-    // evaluation cache (YY_FLAG_REUSE_TRANSPOSITIONS / YY_FLAG_KEEP_EVALUATIONS): per game ec_cap slots, open addressing
-    uint32_t *ec_meta;      // [G, ec_cap]  epoch << 8 | stones, 0 = never used
-    uint64_t *ec_key;       // [G, ec_cap, 2*NW]  the position
-    float *ec_val;          // [G, ec_cap]  the evaluator's value
-    float *ec_pol;          // [G, ec_cap, A]  the evaluator's policy row
-    int64_t ec_cap;
-    // shared book of pre-evaluated positions (yy_mcts_set_book; arrays owned by the caller, read-only here)
-    const uint32_t *bk_meta;
-    const uint64_t *bk_key;
-    const float *bk_val, *bk_pol;
-    int64_t bk_cap;
-    int bk_stones;
-    GameState *state;
-    float *sqrt_tab;
-    int32_t sqrt_len;       // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
-    int32_t K;              // leaves per step (1: one descent per game per step)
+    MctsDev dev;            // every pointer, capacity and the geometry live here only
+    MultiDev multi;
     int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
-    LeafRec *leaves;
-    int32_t *mst;
     uint64_t *scratch;      // [8] counters + overflow count
     uint64_t bytes;
     int pending;            // 1 = a select is pending an expand_backup
 };
 
-struct MctsDev {  // by-value kernel argument
-    YYGeo geo;
-    int32_t G;
-    uint32_t aliased, reuse;
-    float cpuct;
-    double eps;
-    int64_t node_cap, edge_cap, path_cap;
-    uint4 *edges, *nodes;
-    uint64_t *nboard, *gboard;
-    int32_t *path;
-    uint32_t *ec_meta;
-    uint64_t *ec_key;
-    float *ec_val, *ec_pol;
-    int32_t ec_cap;
-    uint32_t ec_keep;
-    const uint32_t *bk_meta;
-    const uint64_t *bk_key;
-    const float *bk_val, *bk_pol;
-    uint32_t bk_mask;
-    int32_t bk_stones;
-    GameState *state;
-    const float *sqrt_tab;
-    int32_t sqrt_n;
-};
+// ---- the position table: each of probe sequence, key compare and stone count exists once, for the cache, the book's
+// lookup and the book's build (k_book_insert)
+// The probe sequence of hash h in a table of mask + 1 slots: TT_PROBES slots from tt_first on, linear, wrapping.  visit(slot)
+// says whether to go on, that the position is not there, or that this is its slot: the slot is returned, else -1.
+enum TTStep { TT_NEXT, TT_MISS, TT_HIT };
+__device__ __forceinline__ uint32_t tt_first(uint64_t h, uint32_t mask) { return (uint32_t)h & mask; }
+template <class F> __device__ __forceinline__ int tt_probe(uint64_t h, uint32_t mask, F visit) {
+    uint32_t at = tt_first(h, mask);
+    for (int pr = 0; pr < TT_PROBES; pr++, at = (at + 1u) & mask) {
+        const TTStep r = visit(at);
+        if (r == TT_HIT) return (int)at;
+        if (r == TT_MISS) break;
+    }
+    return -1;
+}
+// slot `at` holds the position (black, white): every word is compared, the hash only picks the probe sequence
+template <int NW> __device__ __forceinline__ bool tt_key_is(const PosTable &t, uint32_t at, BB<NW> black, BB<NW> white) {
+    const uint64_t *k = t.key + (size_t)at * 2 * NW;
+    const BB<NW> ob = bb_uniform_load<NW>(k), ow = bb_uniform_load<NW>(k + NW);
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < NW; i++) same = same && ob.w[i] == black.w[i] && ow.w[i] == white.w[i];
+    return same;
+}
+template <int NW> __device__ __forceinline__ int pos_stones(BB<NW> black, BB<NW> white) { return bb_popc(black) + bb_popc(white); }
 
-static MctsDev make_dev(const yy_mcts *c) {
-    MctsDev d;
-    d.geo = c->geo;
-    d.G = c->cfg.G;
-    d.aliased = (c->cfg.flags & YY_FLAG_ALIASED) ? 1u : 0u;
-    d.reuse = (c->cfg.flags & YY_FLAG_REUSE_PASS_VALUE) ? 1u : 0u;
-    d.cpuct = c->cfg.cpuct;
-    d.eps = 0.0;
-    d.node_cap = c->node_cap;
-    d.edge_cap = c->edge_cap;
-    d.path_cap = c->path_cap;
-    d.edges = c->edges;
-    d.nodes = c->nodes;
-    d.nboard = c->nboard;
-    d.gboard = c->gboard;
-    d.path = c->path;
-    d.ec_meta = c->ec_meta;
-    d.ec_key = c->ec_key;
-    d.ec_val = c->ec_val;
-    d.ec_pol = c->ec_pol;
-    d.ec_cap = (int32_t)c->ec_cap;
-    d.ec_keep = (c->cfg.flags & YY_FLAG_KEEP_EVALUATIONS) ? 1u : 0u;
-    d.bk_meta = c->bk_meta;
-    d.bk_key = c->bk_key;
-    d.bk_val = c->bk_val;
-    d.bk_pol = c->bk_pol;
-    d.bk_mask = (uint32_t)(c->bk_cap - 1);
-    d.bk_stones = c->bk_stones;
-    d.state = c->state;
-    d.sqrt_tab = c->sqrt_tab;
-    d.sqrt_n = c->sqrt_len;
-    return d;
+template <int NW> __device__ __forceinline__ PosTable cache_of(const MctsDev &d, const int g) {
+    const size_t o = (size_t)g * ((size_t)d.ec.mask + 1);
+    return PosTable{d.ec.meta + o, d.ec.key + o * 2 * NW, d.ec.val + o, d.ec.pol + o * d.geo.A, d.ec.mask};
 }
 
-static MultiDev make_multi(const yy_mcts *c) {
-    MultiDev m;
-    m.K = c->K;
-    m.leaves = c->leaves;
-    m.mst = c->mst;
-    return m;
+// Where a leaf's evaluation comes from (GameState.leaf_src): the evaluator, slot s of the game's cache, slot s of the book
+#define SRC_NONE (-1)
+__device__ __forceinline__ int src_cache(uint32_t s) { return (int)s; }
+__device__ __forceinline__ int src_book(uint32_t s) { return -2 - (int)s; }
+
+// Evaluation cache: the evaluator is a function of the position alone (the planes encode the board, not the side to move),
+// so a position it has already seen -- another move order inside this search, a pass node visited again, with
+// YY_FLAG_KEEP_EVALUATIONS an earlier search of the same game, or one of the book -- needs no evaluator row: the stored
+// policy row and value ARE this leaf's evaluation.  Returns the leaf_src of the position (black, white); on SRC_NONE with a
+// cache, `slot` is where cache_store puts the fresh evaluation (else -1).
+template <int NW>
+__device__ __forceinline__ int leaf_lookup(const MctsDev &d, const GameState *st, const int g, BB<NW> black, BB<NW> white,
+                                           int &slot) {
+    slot = -1;
+    if (!d.ec.meta && !d.bk.meta) return SRC_NONE;
+    const uint64_t h = bb_hash<NW>(black.w, white.w);
+    // the shared book: positions of the first plies evaluated once for ALL games before play; read-only
+    if (d.bk.meta && pos_stones<NW>(black, white) <= d.bk_stones) {
+        const int at = tt_probe(h, d.bk.mask, [&](uint32_t at) {
+            if (rfl((int)d.bk.meta[at]) == 0) return TT_MISS;                      // never used: the position is not in the book
+            return tt_key_is<NW>(d.bk, at, black, white) ? TT_HIT : TT_NEXT;
+        });
+        if (at >= 0) return src_book((uint32_t)at);
+    }
+    if (!d.ec.meta) return SRC_NONE;
+    const PosTable t = cache_of<NW>(d, g);
+    const uint32_t ep = (uint32_t)rfl((int)st->ec_epoch);
+    const int rstones = rfl(st->root_stones);
+    const int at = tt_probe(h, t.mask, [&](uint32_t at) {
+        const uint32_t m = (uint32_t)rfl((int)t.meta[at]);
+        if (m == 0u) { if (slot < 0) slot = (int)at; return TT_MISS; }             // never used: the position is not in the table
+        const bool cur = (m >> 8) == ep;
+        if ((cur || d.ec_keep) && tt_key_is<NW>(t, at, black, white)) return TT_HIT;
+        // replaceable: another epoch, or a position that cannot come back (a leaf has more stones than the root)
+        if (slot < 0 && (!cur || (int)(m & 0xFFu) <= rstones)) slot = (int)at;
+        return TT_NEXT;
+    });
+    if (slot < 0) slot = (int)tt_first(h, t.mask);                                 // every probed entry is live: replace the first
+    return at >= 0 ? src_cache((uint32_t)at) : SRC_NONE;
+}
+
+// the evaluation of game g's pending leaf: its policy row and value, from the evaluator's row g or the slot `src` names.
+// value == nullptr: the root call, whose value is discarded (mcts.py:288; yy_mcts_expand_root is not given it)
+struct LeafEval { const float *prow; float v; };
+template <int NW>
+__device__ __forceinline__ LeafEval leaf_eval(const MctsDev &d, const int g, const int src, const float *policy,
+                                              const float *value) {
+    if (src == SRC_NONE) return LeafEval{policy + (size_t)g * d.geo.A, value ? rflf(value[g]) : 0.0f};
+    const bool book = src < SRC_NONE;
+    const PosTable t = book ? d.bk : cache_of<NW>(d, g);
+    const size_t s = (size_t)(book ? -2 - src : src);
+    return LeafEval{t.pol + s * d.geo.A, rflf(t.val[s])};
+}
+
+// a fresh evaluation (the evaluator's row g, value v) of game g's pending leaf goes into the cache slot leaf_lookup chose
+template <int NW>
+__device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *st, const int g, const float *policy,
+                                            const float v) {
+    const PosTable t = cache_of<NW>(d, g);
+    const size_t slot = (size_t)rfl(st->leaf_ec_slot);
+    const int lane = lane_id(), A = d.geo.A;
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const int cell = j * 64 + lane;
+        if (cell < A) t.pol[slot * A + cell] = policy[(size_t)g * A + cell];
+    }
+    if (lane == 0) {
+        const uint64_t *board = st->leaf.board;
+#pragma unroll
+        for (int i = 0; i < 2 * NW; i++) t.key[slot * 2 * NW + i] = board[i];
+        t.val[slot] = v;
+        t.meta[slot] = (st->ec_epoch << 8) | (uint32_t)(pos_stones<NW>(bb_load<NW>(board), bb_load<NW>(board + NW)) & 0xFF);
+    }
 }
 
 __device__ __forceinline__ uint32_t node_pack(int k, uint32_t flags, int player) {
@@ -693,7 +744,7 @@ __device__ __forceinline__ void leaf_store(LeafRec *rec, BB<NW> black, BB<NW> wh
 template <int NW>
 __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, const int g, const LeafRec *rec,
                                             const int32_t *path, const float *prow, const float v, const bool hold,
-                                            const bool aliased, const double *noise) {
+                                            const bool aliased, const double *noise, const double eps) {
     if (v != v) return false;   // a NaN from the evaluator must not enter the statistics
     const int lane = lane_id();
     const int A = d.geo.A;
@@ -728,7 +779,7 @@ __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, con
     } else {                                                                    // mcts.py:71-89
         const int k = bb_popc(mask);
         if (n_edges + k > (int)d.edge_cap) return false;
-        const float keep = (float)(1.0 - d.eps);
+        const float keep = (float)(1.0 - eps);
         // a game whose noise row is all zero over its legal moves drew no noise (a Dirichlet draw
         // sums to 1): it keeps the raw priors, like add_exploration_noise=False (mcts.py:298)
         bool mix = false;
@@ -752,7 +803,7 @@ __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, con
                 bad |= (p != p);
                 if (mix) {                                                      // mcts.py:310-312
                     const float kp = __fmul_rn(keep, p);
-                    p = (float)__dadd_rn((double)kp, __dmul_rn(d.eps, noise[(size_t)g * A + cell]));
+                    p = (float)__dadd_rn((double)kp, __dmul_rn(eps, noise[(size_t)g * A + cell]));
                 }
                 edges[base + mbcnt(mask.w[j])] =
                     make_uint4(__float_as_uint(p), 0u, 0u, CHILD_NONE | ((uint32_t)cell << 24));
@@ -830,13 +881,11 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         rec->dup = -1;
         d.nodes[(size_t)g * d.node_cap] = make_uint4(0u, node_pack(0, 0, players[g]), 0u, 0u);
     }
-    if (d.ec_meta && lane_id() == 0) {
+    if (d.ec.meta && lane_id() == 0) {
         // Entries of an older epoch are the first to be replaced.  Without YY_FLAG_KEEP_EVALUATIONS every search is its own
         // epoch and only entries of the current one are looked at (reuse inside one search); with it the epoch changes when
         // a game starts over from the empty board, so a game's searches share their evaluations.
-        int stones = 0;
-#pragma unroll
-        for (int i = 0; i < NW; i++) stones += yy_popc64(black.w[i]) + yy_popc64(white.w[i]);
+        const int stones = pos_stones<NW>(black, white);
         uint32_t ep = st->ec_epoch;
         if (!d.ec_keep || stones == 0 || ep == 0u) ep = (ep + 1u) & 0xFFFFFFu;
         if (ep == 0u) ep = 1u;
@@ -956,63 +1005,15 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         bool term;
         float tv;
         leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
-        // Evaluation cache: the evaluator is a function of the position alone (the planes encode the board, not the side to
-        // move), so a position it has already seen -- another move order inside this search, a pass node visited again, or,
-        // with YY_FLAG_KEEP_EVALUATIONS, an earlier search of the same game -- needs no evaluator row: the cached policy row
-        // and value ARE this leaf's evaluation.  Keys are compared in full; the hash only picks the probe sequence.
-        int src = -1, slot = -1;
-        uint64_t h = 0;
-        if (d.ec_meta || d.bk_meta) h = bb_hash<NW>(black.w, white.w);
-        if (d.bk_meta) {
-            // the shared book (yy_mcts_set_book): positions of the first plies evaluated once for ALL games before play; read-only
-            int stones = 0;
-#pragma unroll
-            for (int i = 0; i < NW; i++) stones += yy_popc64(black.w[i]) + yy_popc64(white.w[i]);
-            if (stones <= d.bk_stones) {
-                uint32_t at = (uint32_t)h & d.bk_mask;
-                for (int pr = 0; pr < TT_PROBES; pr++, at = (at + 1u) & d.bk_mask) {
-                    if (rfl((int)d.bk_meta[at]) == 0) break;
-                    const BB<NW> ob = bb_uniform_load<NW>(d.bk_key + (size_t)at * 2 * NW),
-                                 ow = bb_uniform_load<NW>(d.bk_key + (size_t)at * 2 * NW + NW);
-                    bool same = true;
-#pragma unroll
-                    for (int i = 0; i < NW; i++) same = same && ob.w[i] == black.w[i] && ow.w[i] == white.w[i];
-                    if (same) { src = -2 - (int)at; break; }
-                }
-            }
-        }
-        if (d.ec_meta && src == -1) {
-            const uint32_t *meta = d.ec_meta + (size_t)g * d.ec_cap;
-            const uint64_t *keys = d.ec_key + (size_t)g * d.ec_cap * 2 * NW;
-            const uint32_t mask_c = (uint32_t)d.ec_cap - 1u;
-            const uint32_t ep = (uint32_t)rfl((int)st->ec_epoch);
-            const int rstones = rfl(st->root_stones);
-            uint32_t at = (uint32_t)h & mask_c;
-            const uint32_t at0 = at;
-            for (int pr = 0; pr < TT_PROBES; pr++, at = (at + 1u) & mask_c) {
-                const uint32_t m = (uint32_t)rfl((int)meta[at]);
-                if (m == 0u) { if (slot < 0) slot = (int)at; break; }        // never used: the position is not in the table
-                const bool cur = (m >> 8) == ep;
-                if (cur || d.ec_keep) {
-                    const BB<NW> ob = bb_uniform_load<NW>(keys + (size_t)at * 2 * NW),
-                                 ow = bb_uniform_load<NW>(keys + (size_t)at * 2 * NW + NW);
-                    bool same = true;
-#pragma unroll
-                    for (int i = 0; i < NW; i++) same = same && ob.w[i] == black.w[i] && ow.w[i] == white.w[i];
-                    if (same) { src = (int)at; break; }
-                }
-                // replaceable: another epoch, or a position that cannot come back (a leaf has more stones than the root)
-                if (slot < 0 && (!cur || (int)(m & 0xFFu) <= rstones)) slot = (int)at;
-            }
-            if (slot < 0) slot = (int)at0;                                     // every probed entry is live: replace the first
-        }
-        if (src == -1) write_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, black, white);
+        int slot;
+        const int src = leaf_lookup<NW>(d, st, g, black, white, slot);
+        if (src == SRC_NONE) write_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, black, white);
         leaf_store<NW>(&st->leaf, black, white, mask, lplayer, term, tv);
         if (lane == 0) {
             st->leaf_src = src;
             st->leaf_ec_slot = slot;
         }
-        need = src == -1;
+        need = src == SRC_NONE;
         if (!need && lane == 0) st->ctr[7] += 1;
     }
     if (lane == 0) {
@@ -1031,7 +1032,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
 // ---- expansion + backup: mcts.py:50-91 (expand_leaf), 147-156 + 406-412 (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, const float *policy,
-                                                 const float *value, const double *noise) {
+                                                 const float *value, const double *noise, const double eps) {
     GameState *st = d.state + g;
     const int lane = lane_id();
     const int kind = rfl((int)st->leaf.kind);
@@ -1049,40 +1050,18 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
     } else if (kind == K_REUSE) {
         v = rflf(__uint_as_float(nodes[node].w));                                   // the np.float32 the evaluator returned for this node
     } else {
-        const int A = d.geo.A;
-        const int src = ((d.ec_meta || d.bk_meta) && kind != K_ROOTINIT) ? rfl(st->leaf_src) : -1;
-        const bool copy = src != -1;             // evaluation taken from the game's cache (slot src >= 0) or the book (slot -2 - src)
-        const float *prow = src >= 0 ? d.ec_pol + ((size_t)g * d.ec_cap + src) * A
-                                     : copy ? d.bk_pol + (size_t)(-2 - src) * A : policy + (size_t)g * A;
-        v = (kind == K_ROOTINIT) ? 0.0f
-            : src >= 0 ? rflf(d.ec_val[(size_t)g * d.ec_cap + src]) : copy ? rflf(d.bk_val[-2 - src]) : rflf(value[g]);
-        // a pass node keeps its value (not from the root call of mcts.py:288: that value is discarded and
-        // yy_mcts_expand_root is not given it -- a pass root keeps the value of its first simulation)
-        const bool hold = d.reuse && kind != K_ROOTINIT;
-        if (!expand_leaf<NW>(d, st, g, &st->leaf, path, prow, v, hold, d.aliased != 0u, noise)) {
+        // the root call of mcts.py:288 looks nothing up, and its value is discarded: yy_mcts_expand_root is not given it
+        const bool root = kind == K_ROOTINIT;
+        const int src = (root || !(d.ec.meta || d.bk.meta)) ? SRC_NONE : rfl(st->leaf_src);
+        const LeafEval ev = leaf_eval<NW>(d, g, src, policy, root ? nullptr : value);
+        v = ev.v;
+        const bool hold = d.reuse && !root;   // a pass node keeps its value; a pass root that of its first simulation
+        if (!expand_leaf<NW>(d, st, g, &st->leaf, path, ev.prow, v, hold, d.aliased != 0u, noise, eps)) {
             // NaN from the evaluator or a full arena: the game stops searching, the error is sticky
             if (lane == 0) { st->err = st->err_ever = 1; st->leaf.kind = K_NONE; }
             return;
         }
-        if (d.ec_meta && !copy && kind != K_ROOTINIT) {                            // a fresh evaluation goes into the cache
-            const int slot = rfl(st->leaf_ec_slot);
-            const size_t e = (size_t)g * d.ec_cap + slot;
-#pragma unroll
-            for (int j = 0; j < NW; j++) {
-                const int cell = j * 64 + lane;
-                if (cell < A) d.ec_pol[e * A + cell] = policy[(size_t)g * A + cell];
-            }
-            if (lane == 0) {
-                int stones = 0;
-#pragma unroll
-                for (int i = 0; i < 2 * NW; i++) {
-                    d.ec_key[e * 2 * NW + i] = st->leaf.board[i];
-                    stones += yy_popc64(st->leaf.board[i]);
-                }
-                d.ec_val[e] = v;
-                d.ec_meta[e] = (st->ec_epoch << 8) | (uint32_t)(stones & 0xFF);
-            }
-        }
+        if (d.ec.meta && src == SRC_NONE && !root) cache_store<NW>(d, st, g, policy, v);
     }
     if (lane == 0) st->leaf.kind = K_NONE;
     if (kind == K_ROOTINIT) return;                                                 // no backup
@@ -1091,10 +1070,10 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
 
 template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do_backup, int do_sel,
                                                                const float *policy, const float *value,
-                                                               const double *noise, float *planes,
+                                                               const double *noise, double eps, float *planes,
                                                                uint8_t *needs_eval) {
     const int g = blockIdx.x;
-    if (do_backup) do_expand_backup<NW>(d, g, policy, value, noise);
+    if (do_backup) do_expand_backup<NW>(d, g, policy, value, noise, eps);
     if (do_backup && do_sel) __syncthreads();   // edges/nodes written above are re-read below by other lanes
     if (do_sel) do_select<NW>(d, g, planes, needs_eval);
 }
@@ -1218,7 +1197,7 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
 // (expand_leaf), then every descent backs its value up along its own path (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const MultiDev &m, const int g, const float *policy,
-                                                       const float *value, const double *noise) {
+                                                       const float *value, const double *noise, const double eps) {
     GameState *st = d.state + g;
     const int lane = lane_id();
     const int K = m.K;
@@ -1243,7 +1222,7 @@ __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const M
             v = rflf(value[row]);                                  // checked when the first occurrence was expanded
         } else {
             v = (kind == K_ROOTINIT) ? 0.0f : rflf(value[row]);
-            if (!expand_leaf<NW>(d, st, g, rec, path, policy + row * d.geo.A, v, false, false, noise)) {
+            if (!expand_leaf<NW>(d, st, g, rec, path, policy + row * d.geo.A, v, false, false, noise, eps)) {
                 // NaN from the evaluator or a full arena: the game stops, the error is sticky
                 if (lane == 0) { st->err = st->err_ever = 1; ms[1] = 0; }
                 return;
@@ -1258,10 +1237,10 @@ __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const M
 
 template <int NW> __global__ void __launch_bounds__(64) k_mcts_multi(MctsDev d, MultiDev m, int do_backup, int do_sel,
                                                                      const float *policy, const float *value,
-                                                                     const double *noise, float *planes,
+                                                                     const double *noise, double eps, float *planes,
                                                                      uint8_t *needs_eval) {
     const int g = blockIdx.x;
-    if (do_backup) do_expand_backup_multi<NW>(d, m, g, policy, value, noise);
+    if (do_backup) do_expand_backup_multi<NW>(d, m, g, policy, value, noise, eps);
     if (do_backup && do_sel) __syncthreads();
     if (do_sel) do_select_multi<NW>(d, m, g, planes, needs_eval);
 }
@@ -1381,41 +1360,48 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     yy_mcts *c = new yy_mcts();
     memset(c, 0, sizeof *c);
     c->cfg = *cfg;
-    c->K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     c->target_sims = cfg->max_sims;
+    MctsDev &d = c->dev;
+    MultiDev &m = c->multi;
+    d.G = cfg->G;
+    d.aliased = (cfg->flags & YY_FLAG_ALIASED) ? 1u : 0u;
+    d.reuse = (cfg->flags & YY_FLAG_REUSE_PASS_VALUE) ? 1u : 0u;
+    d.ec_keep = (cfg->flags & YY_FLAG_KEEP_EVALUATIONS) ? 1u : 0u;
+    d.cpuct = cfg->cpuct;
+    m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
-    c->sqrt_len = cfg->max_sims + 2 + (c->K > 1 ? c->K : 0);
-    yy_make_geo(&c->geo, cfg->R, cfg->C, cfg->flags & YY_FLAG_ROWCOL);
-    const int A = c->geo.A, NW = c->geo.NW;
-    c->node_cap = cfg->nodes_per_game > 0 ? cfg->nodes_per_game : (int64_t)cfg->max_sims + 2;
-    c->edge_cap = cfg->edges_per_game > 0 ? cfg->edges_per_game : ((int64_t)cfg->max_sims + 2) * A;
-    if (c->node_cap >= (int64_t)CHILD_NONE || c->edge_cap > 0x7FFFFFFFll)
+    d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
+    yy_make_geo(&d.geo, cfg->R, cfg->C, cfg->flags & YY_FLAG_ROWCOL);
+    const int A = d.geo.A, NW = d.geo.NW;
+    d.node_cap = cfg->nodes_per_game > 0 ? cfg->nodes_per_game : (int64_t)cfg->max_sims + 2;
+    d.edge_cap = cfg->edges_per_game > 0 ? cfg->edges_per_game : ((int64_t)cfg->max_sims + 2) * A;
+    if (d.node_cap >= (int64_t)CHILD_NONE || d.edge_cap > 0x7FFFFFFFll)
         { delete c; return set_err(YY_E_UNSUPPORTED, "arena per game too large%s%s"); }
     // copied mode: every level places a stone, so depth <= A+1; aliased mode: depth <= sims
-    c->path_cap = (cfg->flags & YY_FLAG_ALIASED) ? (int64_t)cfg->max_sims + 2 : (int64_t)A + 2;
+    d.path_cap = d.aliased ? (int64_t)cfg->max_sims + 2 : (int64_t)A + 2;
     const size_t G = (size_t)cfg->G;
-    const bool copied = !(cfg->flags & YY_FLAG_ALIASED);
     const bool ec_on = (cfg->flags & (YY_FLAG_REUSE_TRANSPOSITIONS | YY_FLAG_KEEP_EVALUATIONS)) != 0;
     // slots per game: 4x the node arena (the positions of several searches of a game stay useful), fewer when the
     // policy rows of all games would exceed 48 GiB, never fewer than 2x the arena of one search
-    c->ec_cap = 64;
-    while (c->ec_cap < 4 * c->node_cap) c->ec_cap *= 2;
-    while (c->ec_cap > 2 * c->node_cap && (double)G * (double)c->ec_cap * A * 4.0 > 48.0 * 1073741824.0) c->ec_cap /= 2;
+    int64_t ec_cap = 64;
+    while (ec_cap < 4 * d.node_cap) ec_cap *= 2;
+    while (ec_cap > 2 * d.node_cap && (double)G * (double)ec_cap * A * 4.0 > 48.0 * 1073741824.0) ec_cap /= 2;
+    d.ec.mask = (uint32_t)(ec_cap - 1);
     struct { void **p; size_t n; } allocs[] = {
-        {(void **)&c->edges, G * c->edge_cap * sizeof(uint4)},
-        {(void **)&c->nodes, G * c->node_cap * sizeof(uint4)},
-        {(void **)&c->nboard, copied ? G * c->node_cap * 2 * NW * sizeof(uint64_t) : 8},
-        {(void **)&c->gboard, G * 2 * NW * sizeof(uint64_t)},
-        {(void **)&c->path, G * c->K * c->path_cap * sizeof(int32_t)},
-        {(void **)&c->state, G * sizeof(GameState)},
-        {(void **)&c->sqrt_tab, (size_t)c->sqrt_len * sizeof(float)},
-        {(void **)&c->leaves, c->K > 1 ? G * c->K * sizeof(LeafRec) : 0},
-        {(void **)&c->mst, c->K > 1 ? G * 2 * sizeof(int32_t) : 0},
+        {(void **)&d.edges, G * d.edge_cap * sizeof(uint4)},
+        {(void **)&d.nodes, G * d.node_cap * sizeof(uint4)},
+        {(void **)&d.nboard, d.aliased ? 8 : G * d.node_cap * 2 * NW * sizeof(uint64_t)},
+        {(void **)&d.gboard, G * 2 * NW * sizeof(uint64_t)},
+        {(void **)&d.path, G * m.K * d.path_cap * sizeof(int32_t)},
+        {(void **)&d.state, G * sizeof(GameState)},
+        {(void **)&d.sqrt_tab, (size_t)d.sqrt_n * sizeof(float)},
+        {(void **)&m.leaves, m.K > 1 ? G * m.K * sizeof(LeafRec) : 0},
+        {(void **)&m.mst, m.K > 1 ? G * 2 * sizeof(int32_t) : 0},
         {(void **)&c->scratch, 9 * sizeof(uint64_t)},
-        {(void **)&c->ec_meta, ec_on ? G * (size_t)c->ec_cap * sizeof(uint32_t) : 0},
-        {(void **)&c->ec_key, ec_on ? G * (size_t)c->ec_cap * 2 * NW * sizeof(uint64_t) : 0},
-        {(void **)&c->ec_val, ec_on ? G * (size_t)c->ec_cap * sizeof(float) : 0},
-        {(void **)&c->ec_pol, ec_on ? G * (size_t)c->ec_cap * A * sizeof(float) : 0},
+        {(void **)&d.ec.meta, ec_on ? G * (size_t)ec_cap * sizeof(uint32_t) : 0},
+        {(void **)&d.ec.key, ec_on ? G * (size_t)ec_cap * 2 * NW * sizeof(uint64_t) : 0},
+        {(void **)&d.ec.val, ec_on ? G * (size_t)ec_cap * sizeof(float) : 0},
+        {(void **)&d.ec.pol, ec_on ? G * (size_t)ec_cap * A * sizeof(float) : 0},
     };
     for (auto &a : allocs) {
         if (a.n == 0) continue;
@@ -1431,13 +1417,13 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         c->bytes += a.n;
     }
     // f32(math.sqrt(S)) table built with the host's correctly rounded double sqrt (mcts.py:130)
-    float *tab = new float[c->sqrt_len];
-    for (int s = 0; s < c->sqrt_len; s++) tab[s] = (float)sqrt((double)s);
-    hipError_t e = hipMemset(c->state, 0, G * sizeof(GameState));
-    if (e == hipSuccess) e = hipMemset(c->nodes, 0, G * c->node_cap * sizeof(uint4));
-    if (e == hipSuccess && c->ec_meta) e = hipMemset(c->ec_meta, 0, G * (size_t)c->ec_cap * sizeof(uint32_t));
-    if (e == hipSuccess && c->mst) e = hipMemset(c->mst, 0, G * 2 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(c->sqrt_tab, tab, (size_t)c->sqrt_len * sizeof(float), hipMemcpyHostToDevice);
+    float *tab = new float[d.sqrt_n];
+    for (int s = 0; s < d.sqrt_n; s++) tab[s] = (float)sqrt((double)s);
+    hipError_t e = hipMemset(d.state, 0, G * sizeof(GameState));
+    if (e == hipSuccess) e = hipMemset(d.nodes, 0, G * d.node_cap * sizeof(uint4));
+    if (e == hipSuccess && d.ec.meta) e = hipMemset(d.ec.meta, 0, G * (size_t)ec_cap * sizeof(uint32_t));
+    if (e == hipSuccess && m.mst) e = hipMemset(m.mst, 0, G * 2 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(d.sqrt_tab, tab, (size_t)d.sqrt_n * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     delete[] tab;
     if (e != hipSuccess) { yy_mcts_destroy(c); return set_err(YY_E_HIP, "arena initialisation: %s%s", hipGetErrorString(e)); }
@@ -1447,8 +1433,9 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
 
 extern "C" int yy_mcts_destroy(yy_mcts *c) {
     if (!c) return YY_OK;
-    void *ps[] = {c->edges, c->nodes, c->nboard, c->gboard, c->path, c->state, c->sqrt_tab, c->scratch, c->ec_meta, c->ec_key, c->ec_val, c->ec_pol,
-                  c->leaves, c->mst};
+    const MctsDev &d = c->dev;
+    void *ps[] = {d.edges, d.nodes, d.nboard, d.gboard, d.path, d.state, d.sqrt_tab, c->scratch, d.ec.meta, d.ec.key, d.ec.val, d.ec.pol,
+                  c->multi.leaves, c->multi.mst};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     delete c;
@@ -1471,10 +1458,8 @@ extern "C" int yy_mcts_memory_bytes(const yy_mcts *c, uint64_t *out) {
 extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *players, const uint8_t *active,
                              float *planes, yy_stream_t s) {
     if (!c || !boards || !players || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    MultiDev m = make_multi(c);
-    DISPATCH_NW(c->geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, m, c->target_sims, boards,
-                                               players, active, planes));
+    DISPATCH_NW(c->dev.geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi, c->target_sims,
+                                                   boards, players, active, planes));
     HIP_TRY(hipGetLastError());
     c->pending = 2;  // root expansion pending
     return YY_OK;
@@ -1482,15 +1467,12 @@ extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *pla
 
 static int launch_mcts(yy_mcts *c, int backup, int sel, const float *policy, const float *value, const double *noise,
                        double eps, float *planes, uint8_t *needs_eval, yy_stream_t s) {
-    MctsDev d = make_dev(c);
-    d.eps = eps;
-    if (c->K > 1) {
-        MultiDev m = make_multi(c);
-        DISPATCH_NW(c->geo.NW, k_mcts_multi<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, m, backup, sel,
-                                                   policy, value, noise, planes, needs_eval));
+    if (c->multi.K > 1) {
+        DISPATCH_NW(c->dev.geo.NW, k_mcts_multi<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi, backup, sel,
+                                                       policy, value, noise, eps, planes, needs_eval));
     } else {
-        DISPATCH_NW(c->geo.NW, k_mcts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, backup, sel,
-                                                   policy, value, noise, planes, needs_eval));
+        DISPATCH_NW(c->dev.geo.NW, k_mcts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, backup, sel,
+                                                       policy, value, noise, eps, planes, needs_eval));
     }
     HIP_TRY(hipGetLastError());
     return YY_OK;
@@ -1529,44 +1511,39 @@ extern "C" int yy_mcts_step(yy_mcts *c, const float *policy, const float *value,
 
 extern "C" int yy_mcts_root_counts(yy_mcts *c, int32_t *counts, float *cw, float *cp, yy_stream_t s) {
     if (!c || !counts) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    DISPATCH_NW(c->geo.NW,
-                k_root_counts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, counts, cw, cp));
+    DISPATCH_NW(c->dev.geo.NW,
+                k_root_counts<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, counts, cw, cp));
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
 
 extern "C" int yy_mcts_root_policy(yy_mcts *c, int tzero, double *pi, yy_stream_t s) {
     if (!c || !pi) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    DISPATCH_NW(c->geo.NW,
-                k_root_policy<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, tzero, pi));
+    DISPATCH_NW(c->dev.geo.NW,
+                k_root_policy<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, tzero, pi));
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
 
 extern "C" int yy_mcts_root_stats(yy_mcts *c, int32_t *visits, double *wsum, yy_stream_t s) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    hipLaunchKernelGGL(k_root_stats, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, d, visits, wsum);
+    hipLaunchKernelGGL(k_root_stats, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, c->dev, visits, wsum);
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
 
 extern "C" int yy_mcts_get_boards(yy_mcts *c, int8_t *boards, yy_stream_t s) {
     if (!c || !boards) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    DISPATCH_NW(c->geo.NW, k_get_boards<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(d, boards));
+    DISPATCH_NW(c->dev.geo.NW, k_get_boards<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, boards));
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
 
 extern "C" int yy_mcts_status(yy_mcts *c, int32_t *n_overflow, uint64_t *counters) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemset(c->scratch, 0, 9 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_status, dim3(64), dim3(256), 0, 0, d, c->scratch);
+    hipLaunchKernelGGL(k_status, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
     HIP_TRY(hipGetLastError());
     uint64_t h[9];
     HIP_TRY(hipMemcpy(h, c->scratch, sizeof h, hipMemcpyDeviceToHost));
@@ -1584,10 +1561,9 @@ template <int NW> __global__ void k_book_insert(const uint64_t *__restrict__ key
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t *k = keys + (size_t)i * 2 * NW;
-    uint32_t at = (uint32_t)bb_hash<NW>(k, k + NW) & mask;
-    int got = -1;
-    for (int pr = 0; pr < TT_PROBES; pr++, at = (at + 1u) & mask)
-        if (atomicCAS(&meta[at], 0u, 1u) == 0u) { got = (int)at; break; }      // keys are distinct: a taken slot is another position
+    // the sequence leaf_lookup walks; keys are distinct: a taken slot is another position
+    const int got = tt_probe(bb_hash<NW>(k, k + NW), mask,
+                             [&](uint32_t at) { return atomicCAS(&meta[at], 0u, 1u) == 0u ? TT_HIT : TT_NEXT; });
     if (got >= 0)
         for (int j = 0; j < 2 * NW; j++) tkeys[(size_t)got * 2 * NW + j] = k[j];
     slot_of[i] = got;      // -1: no free slot within the probe window (the position stays out of the book)
@@ -1609,24 +1585,26 @@ extern "C" int yy_book_insert(const uint64_t *keys, int n, int R, int C, uint32_
 extern "C" int yy_mcts_set_book(yy_mcts *c, const uint32_t *meta, const uint64_t *keys, const float *val, const float *pol,
                                 int64_t cap, int max_stones) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    if (!meta) { c->bk_meta = nullptr; c->bk_key = nullptr; c->bk_val = c->bk_pol = nullptr; c->bk_cap = 0; c->bk_stones = 0; return YY_OK; }
+    if (!meta) { c->dev.bk = PosTable{}; c->dev.bk_stones = 0; return YY_OK; }
     if (!keys || !val || !pol || cap < 64 || (cap & (cap - 1)) || cap > (1ll << 31) || max_stones < 1)
         return set_err(YY_E_INVALID, "yy_mcts_set_book: bad argument (cap must be a power of two)%s%s");
-    if (c->K > 1) return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_book: leaves_per_step > 1 does not support evaluation reuse%s%s");
-    c->bk_meta = meta; c->bk_key = keys; c->bk_val = val; c->bk_pol = pol; c->bk_cap = cap; c->bk_stones = max_stones;
+    if (c->multi.K > 1) return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_book: leaves_per_step > 1 does not support evaluation reuse%s%s");
+    // the caller's arrays are only read through this table (leaf_lookup, leaf_eval)
+    c->dev.bk = PosTable{(uint32_t *)meta, (uint64_t *)keys, (float *)val, (float *)pol, (uint32_t)(cap - 1)};
+    c->dev.bk_stones = max_stones;
     return YY_OK;
 }
 
 extern "C" int yy_mcts_cache_clear(yy_mcts *c, yy_stream_t s) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    if (c->ec_meta) HIP_TRY(hipMemsetAsync(c->ec_meta, 0, (size_t)c->cfg.G * (size_t)c->ec_cap * sizeof(uint32_t), (hipStream_t)s));
+    const PosTable &ec = c->dev.ec;
+    if (ec.meta) HIP_TRY(hipMemsetAsync(ec.meta, 0, (size_t)c->cfg.G * ((size_t)ec.mask + 1) * sizeof(uint32_t), (hipStream_t)s));
     return YY_OK;
 }
 
 extern "C" int yy_mcts_reset_counters(yy_mcts *c, yy_stream_t s) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    MctsDev d = make_dev(c);
-    hipLaunchKernelGGL(k_reset_counters, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, d);
+    hipLaunchKernelGGL(k_reset_counters, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, c->dev);
     HIP_TRY(hipGetLastError());
     return YY_OK;
 }
