@@ -136,7 +136,7 @@ typedef struct yy_mcts_config {
 
 /* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after
  * another, K_eff = min(K, simulations of this search not yet started) -- computed on the device from root.visits and the count
- * set by yy_mcts_set_num_sims, so that one captured step serves every step of a search.  The tree and its statistics do not
+ * set by yy_mcts_set_num_sims (or the game's own budget, yy_mcts_set_sim_budgets), so that one captured step serves every step of a search.  The tree and its statistics do not
  * change during these descents.  Descent j sees on every edge a virtual count v = the number of descents 0 .. j-1 of this step
  * that walked that edge, and scores a child with n = N + v, w = v > 0 ? f32(W - f32(v)) : W, in the float32 order of
  * mcts.py:97-145: S = sum over the children of (N + v), sq = f32(sqrt(S)), u = f32(f32(f32(cpuct*P)*sq) / f32(1+n)),
@@ -160,6 +160,15 @@ int yy_mcts_memory_bytes(const yy_mcts *ctx, uint64_t *out);
 /* Simulations of the searches begun after this call (0 = max_sims, the default); host only, read by yy_mcts_begin.  Used
  * by leaf-parallel contexts (K > 1) to run the last step of a search with fewer descents; K = 1 ignores it. */
 int yy_mcts_set_num_sims(yy_mcts *ctx, int32_t num_sims);
+/* Per-game simulation budgets of the searches begun after this call: budgets_dev = DEVICE int32 [G], or NULL = every game
+ * gets the scalar again (yy_mcts_set_num_sims at K > 1; no limit but the caller's step count at K = 1: today's search).  Host
+ * only: it stores the pointer, which every following yy_mcts_begin reads on its stream -- the array must stay valid until then
+ * -- and copies, clamped on the device to 0 .. max_sims, into the context.  The step kernels only see that copy, so one
+ * captured step serves every budget array.  K = 1: a game whose root holds budget[g] visits selects nothing (needs_eval[g] =
+ * 0, no arena and no counter touched, like an inactive game) and the following expand_backup / step skips it.  K > 1: K_eff =
+ * min(K, budget[g] - simulations started).  Budget 0 = the root expansion only.  The caller issues the steps of the largest
+ * budget; games of smaller budgets idle through the rest. */
+int yy_mcts_set_sim_budgets(yy_mcts *ctx, const int32_t *budgets_dev);
 
 /* MCTS.search prologue (mcts.py:288-295): fresh root per game from boards int8 [G,R,C] and
  * root_players int8 [G]; active uint8 [G] (NULL = all active; inactive games are skipped by every
@@ -342,7 +351,8 @@ int yy_nn_head_finish_f32(const float *logits, const float *hidden, int G, int A
 int yy_compact_rows(const uint8_t *flags, int G, int32_t *rows, int32_t *n, yy_stream_t stream);
 
 /* ------------------------------------------------------------------ episode-loop random draws
- * Counter-based (Philox4x32-10) replacements of the two draws the reference takes from numpy's global stream, keyed by
+ * Counter-based (Philox4x32-10) replacements of the two draws the reference takes from numpy's global stream (and the
+ * playout-cap draw, which the reference does not have), keyed by
  * (seed, GLOBAL game index, ply, purpose, element) so that a game's transcript does not depend on its slot, on the batch
  * size, on refill order or on the number of ranks.  All pointers are device pointers.
  *
@@ -357,6 +367,13 @@ int yy_selfplay_root_noise(uint64_t seed, const int64_t *game_id, const int32_t 
 int yy_selfplay_sample_actions(uint64_t seed, const int64_t *game_id, const int32_t *ply,
                                const uint8_t *searching, const double *pi, const uint8_t *mask, int G, int A,
                                int temperature_threshold, int32_t *action, yy_stream_t stream);
+
+/* yy_selfplay_draw_budgets: playout-cap randomisation.  One uniform u in [0, 1) per game with searching[g] != 0, keyed (seed,
+ * game_id[g], ply[g], purpose 3, element 0): is_full[g] = u < p_full, budgets[g] = is_full ? full_sims : fast_sims.  Games that
+ * are not searching get budget 0 and is_full 0.  budgets int32 [G] is what yy_mcts_set_sim_budgets takes; is_full uint8 [G]. */
+int yy_selfplay_draw_budgets(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *searching, int G,
+                             double p_full, int full_sims, int fast_sims, int32_t *budgets, uint8_t *is_full,
+                             yy_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@
 
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
---dist-backend, --reference-format, --leaves-per-step.  `--mode train` runs
+--dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability.  `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
 """
@@ -73,11 +73,24 @@ def parse_args(argv=None):
                         "searches of --mode evaluate, of --mode self-play and of --mode train (self-play and arena).  In "
                         "self-play K > 1 turns --evaluation-reuse auto off and builds no opening book (--opening-book-stones is "
                         "ignored); not with --board-semantics aliased or --reference-quirks.  --mcts-threads stays inert")
+    p.add_argument("--fast-simulations", type=int, default=None,
+                   help="self-play and train: playout-cap randomisation -- a move is searched with --simulations with probability "
+                        "--full-search-probability and with N simulations otherwise; only the fully searched moves become "
+                        "training examples (default: every move is searched in full)")
+    p.add_argument("--full-search-probability", type=float, default=1.0,
+                   help="share P in (0, 1] of the moves searched in full when --fast-simulations is given (default 1 = all)")
     return p.parse_args(argv)
 
 
 def refused(args):
     """The flag combinations no search runs with, as a one-line message (None: none), from the parsed flags alone."""
+    if args.mode in ("self-play", "train"):
+        if not 0.0 < args.full_search_probability <= 1.0:
+            return f"train_alphazero.py: --full-search-probability {args.full_search_probability} is outside (0, 1]"
+        if args.fast_simulations is not None and args.fast_simulations < 1:
+            return f"train_alphazero.py: --fast-simulations {args.fast_simulations} is below 1"
+        if args.fast_simulations is not None and args.fast_simulations > args.simulations:
+            return f"train_alphazero.py: --fast-simulations {args.fast_simulations} is above --simulations {args.simulations}"
     if args.leaves_per_step > 1 and args.mode in ("self-play", "train"):
         for flag, given in (("--board-semantics aliased", args.board_semantics == "aliased"), ("--reference-quirks", args.reference_quirks)):
             if given:
@@ -122,7 +135,8 @@ def main(argv=None):
                            num_simulations=args.simulations, num_epochs=args.epochs, num_workers=args.workers,
                            mcts_threads=args.mcts_threads, nn_mode=args.nn, concurrent_games=args.concurrent_games,
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
-                           lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step)
+                           lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
+                           fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -148,7 +162,9 @@ def main(argv=None):
                                        reference_format=args.reference_format,
                                        evaluation_reuse=None if args.evaluation_reuse == "auto" else False,
                                        opening_book_stones=0 if args.leaves_per_step > 1 else args.opening_book_stones,
-                                       lanes=args.lanes or None, leaves_per_step=args.leaves_per_step)
+                                       lanes=args.lanes or None, leaves_per_step=args.leaves_per_step,
+                                       fast_simulations=args.fast_simulations,
+                                       full_search_probability=args.full_search_probability)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

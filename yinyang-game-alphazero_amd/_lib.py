@@ -69,6 +69,7 @@ _SIGS = {
     "yy_mcts_destroy": [_vp],
     "yy_mcts_memory_bytes": [_vp, C.POINTER(C.c_uint64)],
     "yy_mcts_set_num_sims": [_vp, C.c_int32],
+    "yy_mcts_set_sim_budgets": [_vp, _vp],
     "yy_mcts_begin": [_vp, _vp, _vp, _vp, _vp, _vp],
     "yy_mcts_expand_root": [_vp, _vp, _vp, C.c_double, _vp],
     "yy_mcts_select": [_vp, _vp, _vp, _vp],
@@ -99,6 +100,7 @@ _SIGS = {
     "yy_nn_fc_heads_f16x3": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_selfplay_root_noise": [C.c_uint64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp],
     "yy_selfplay_sample_actions": [C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "yy_selfplay_draw_budgets": [C.c_uint64, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp],
     "yy_version": [],
 }
 

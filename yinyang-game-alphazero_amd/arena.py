@@ -23,7 +23,7 @@ from . import engine
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
 from .search import LockstepSearch
-from .self_play import generate_self_play_data
+from .self_play import _playout_cap, generate_self_play_data
 from .training import run_training_pipeline
 
 
@@ -286,10 +286,14 @@ class AlphaZero:
     def __init__(self, game, model_dir="models", data_dir="data", num_iterations=100, num_episodes=100,
                  num_simulations=800, num_epochs=10, temperature_threshold=10, update_threshold=0.6, num_workers=1,
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
-                 concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1):
+                 concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
+                 full_search_probability=1.0):
         """leaves_per_step K > 1 (not in the reference): leaf-parallel searches in the loop's self-play (SelfPlayManager
-        leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step)."""
+        leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step).
+        fast_simulations / full_search_probability: playout-cap randomisation in the loop's self-play (SelfPlayEngine's); the
+        arena always searches num_simulations."""
         self.leaves_per_step = max(1, int(leaves_per_step))
+        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold
@@ -319,7 +323,7 @@ class AlphaZero:
                                        temperature_threshold=self.temperature_threshold, nn_mode=self.nn_mode,
                                        num_channels=self.num_channels, num_res_blocks=self.num_res_blocks,
                                        concurrent_games=self.concurrent_games, seed=len(self.history),
-                                       leaves_per_step=self.leaves_per_step)
+                                       leaves_per_step=self.leaves_per_step, **self.playout_cap)
 
     def train(self):
         # the reference passes num_iterations=1 and ignores --epochs/--batch-size/--lr (alphazero.py:120-127,

@@ -31,7 +31,7 @@
 #include "yy_bitboard.h"
 #include "yy_common.h"
 
-#define YY_VERSION 101
+#define YY_VERSION 102
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -488,6 +488,7 @@ struct GameState {
     int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
     uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
     int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
+    int32_t budget;         // K = 1: simulations of this game's current search (k_begin); at root_N == budget selection stops
     LeafRec leaf;           // K = 1: the pending leaf
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
 };
@@ -536,6 +537,7 @@ struct yy_mcts {
     MctsDev dev;            // every pointer, capacity and the geometry live here only
     MultiDev multi;
     int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
+    const int32_t *budgets; // device int32 [G] of per-game simulation budgets for the next yy_mcts_begin; nullptr: target_sims for all
     uint64_t *scratch;      // [8] counters + overflow count
     uint64_t bytes;
     int pending;            // 1 = a select is pending an expand_backup
@@ -855,7 +857,11 @@ __device__ __forceinline__ void backup_path(uint4 *edges, const int32_t *path, c
 }
 
 // ---- root prologue: mcts.py:288-295
-template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, const int8_t *boards,
+// The simulation budget of game g: K > 1 keeps it in mst[2g], K = 1 in GameState.budget.  `budgets` (int32 [G], clamped to
+// 0 .. max_sims here) when the caller set one (yy_mcts_set_sim_budgets), else `target` for every game.  The pointer is an
+// argument of this kernel only: the step kernels read the stored budgets, so a captured step serves every budget array.
+template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, const int32_t *budgets,
+                                                                int max_sims, const int8_t *boards,
                                                                 const int8_t *players, const uint8_t *active,
                                                                 float *planes) {
     const int g = blockIdx.x;
@@ -875,6 +881,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         st->root_player = players[g];
         st->active = act;
         st->err = 0;
+        st->budget = budgets ? min(max(budgets[g], 0), max_sims) : target;
         rec->kind = act ? K_ROOTINIT : K_NONE;
         rec->node = 0;
         rec->path_len = 0;
@@ -912,7 +919,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         write_planes<NW>(planes + (size_t)g * K * 5 * d.geo.A, d.geo, black, white);
     }
     if (K > 1 && lane_id() == 0) {
-        m.mst[2 * g] = target;
+        m.mst[2 * g] = budgets ? min(max(budgets[g], 0), max_sims) : target;
         m.mst[2 * g + 1] = act ? 1 : 0;
     }
 }
@@ -922,7 +929,12 @@ template <int NW>
 __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *planes, uint8_t *needs_eval) {
     GameState *st = d.state + g;
     const int lane = lane_id();
-    if (!rfl((int)st->active) || rfl((int)st->err)) {
+    // a game whose root has had its budget of simulations selects nothing, like an inactive one: no arena, no counter.  The
+    // four fields are loaded before any of them is tested, so that they cost one round trip to memory, not one each
+    const int s_active = st->active, s_err = st->err, s_budget = st->budget;
+    int s_carry = st->root_N;
+    s_carry = rfl(s_carry);
+    if ((rfl(s_active) == 0) | (rfl(s_err) != 0) | (s_carry >= rfl(s_budget))) {
         if (lane == 0) {
             st->leaf.kind = K_NONE;
             if (needs_eval) needs_eval[g] = 0;
@@ -935,7 +947,6 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     int32_t *path = d.path + (size_t)g * d.path_cap;
 
     int node = 0, depth = 0, parent = -1, action = -1, kind;
-    int s_carry = rfl(st->root_N);
     uint64_t c_levels = 0, c_scan = 0;
     for (;;) {
         const uint4 hdr = nodes[node];
@@ -1449,6 +1460,12 @@ extern "C" int yy_mcts_set_num_sims(yy_mcts *c, int32_t num_sims) {
     return YY_OK;
 }
 
+extern "C" int yy_mcts_set_sim_budgets(yy_mcts *c, const int32_t *budgets_dev) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    c->budgets = budgets_dev;
+    return YY_OK;
+}
+
 extern "C" int yy_mcts_memory_bytes(const yy_mcts *c, uint64_t *out) {
     if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
     *out = c->bytes;
@@ -1458,7 +1475,8 @@ extern "C" int yy_mcts_memory_bytes(const yy_mcts *c, uint64_t *out) {
 extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *players, const uint8_t *active,
                              float *planes, yy_stream_t s) {
     if (!c || !boards || !players || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
-    DISPATCH_NW(c->dev.geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi, c->target_sims,
+    DISPATCH_NW(c->dev.geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi,
+                                                   c->multi.K > 1 ? c->target_sims : 0x7FFFFFFF, c->budgets, c->cfg.max_sims,
                                                    boards, players, active, planes));
     HIP_TRY(hipGetLastError());
     c->pending = 2;  // root expansion pending

@@ -1,4 +1,4 @@
-// yy_selfplay.hip -- the two random draws of the episode loop as counter-based streams keyed by the GLOBAL game index.
+// yy_selfplay.hip -- the random draws of the episode loop as counter-based streams keyed by the GLOBAL game index.
 //
 // Reference: the root Dirichlet noise np.random.dirichlet([alpha] * k) at the first move of a game
 // (src/yin_yang/ai/mcts.py:298-312, self_play.py:131) and the move choice np.random.choice (self_play.py:143-160) both
@@ -15,6 +15,7 @@
 //   purpose 1 = move choice: ONE uniform u in [0, 1) per (game, ply); temperature 1: first action whose running sum of
 //               pi[a] * mask[a] (ascending a, float64) exceeds u * total (uniform over the legal moves if the total is 0);
 //               temperature 0: the floor(u * n)-th of the n actions tied at max(pi).
+//   purpose 3 = playout cap (not in the reference): ONE uniform u in [0, 1) per (game, ply); u < p_full = a full search.
 // One game per wavefront; the inverse CDF runs on lane 0 (A <= 192) so that its float64 sums have one fixed order, which the
 // host restatement in tests/ reproduces bit for bit.
 #include <hip/hip_runtime.h>
@@ -193,6 +194,22 @@ __global__ void __launch_bounds__(64) k_sample_actions(uint64_t seed, const int6
     action[g] = pick;
 }
 
+// playout-cap randomisation: the simulation budget of every searching game's next search, and whether it is a full one
+__global__ void __launch_bounds__(256) k_draw_budgets(uint64_t seed, const int64_t *__restrict__ game_id,
+                                                      const int32_t *__restrict__ ply, const uint8_t *__restrict__ searching,
+                                                      int G, double p_full, int full_sims, int fast_sims,
+                                                      int32_t *__restrict__ budgets, uint8_t *__restrict__ is_full) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    bool full = false;
+    if (searching[g]) {
+        const U4 r = draw(seed, game_id[g], ply[g], 3, 0u);
+        full = u01(r.x, r.y) < p_full;
+    }
+    budgets[g] = !searching[g] ? 0 : full ? full_sims : fast_sims;
+    is_full[g] = full;
+}
+
 }   // namespace sp
 
 extern "C" int yy_selfplay_root_noise(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *draw,
@@ -214,5 +231,18 @@ extern "C" int yy_selfplay_sample_actions(uint64_t seed, const int64_t *game_id,
     sp::k_sample_actions<<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(seed, game_id, ply, searching, pi, mask, A,
                                                                    temperature_threshold, action);
     if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_selfplay_sample_actions: launch failed");
+    return YY_OK;
+}
+
+extern "C" int yy_selfplay_draw_budgets(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *searching,
+                                        int G, double p_full, int full_sims, int fast_sims, int32_t *budgets, uint8_t *is_full,
+                                        yy_stream_t s) {
+    if (G == 0) return YY_OK;
+    if (!game_id || !ply || !searching || !budgets || !is_full || G < 0 || full_sims < 0 || fast_sims < 0 ||
+        !(p_full >= 0.0 && p_full <= 1.0))
+        return yy_tower_set_err(YY_E_INVALID, "yy_selfplay_draw_budgets: bad argument");
+    sp::k_draw_budgets<<<dim3((G + 255) / 256), dim3(256), 0, (hipStream_t)s>>>(seed, game_id, ply, searching, G, p_full,
+                                                                                full_sims, fast_sims, budgets, is_full);
+    if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_selfplay_draw_budgets: launch failed");
     return YY_OK;
 }

@@ -6,6 +6,7 @@ ROCm device and the extension must be built, otherwise these functions raise.
 """
 import ctypes as ct
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -370,6 +371,21 @@ def sample_actions(seed, game_id, ply, searching, pi, mask, temperature_threshol
     return out
 
 
+def draw_budgets(seed, game_id, ply, searching, p_full, full_sims, fast_sims):
+    """Playout-cap draw, keyed by (seed, game_id, ply): one uniform u per searching game, is_full = u < p_full -> (budgets int32
+    [G] = full_sims or fast_sims, 0 where not searching; is_full uint8 [G]).  budgets is what BatchedMCTS.run_search takes."""
+    G = game_id.shape[0]
+    _need(game_id, torch.int64, (G,), "game_id")
+    _need(ply, torch.int32, (G,), "ply")
+    _need(searching, torch.uint8, (G,), "searching")
+    budgets = torch.empty(G, dtype=torch.int32, device=game_id.device)
+    is_full = torch.empty(G, dtype=torch.uint8, device=game_id.device)
+    with torch.cuda.device(game_id.device):
+        check(lib().yy_selfplay_draw_budgets(ct.c_uint64(int(seed) & (2 ** 64 - 1)), _p(game_id), _p(ply), _p(searching), G,
+                                             float(p_full), int(full_sims), int(fast_sims), _p(budgets), _p(is_full), _stream()))
+    return budgets, is_full
+
+
 # ------------------------------------------------------------------ shared book of pre-evaluated opening positions
 class OpeningBook:
     """Every position with at most `max_stones` stones that alternating legal play reaches from the empty board (8x8: 770 232
@@ -480,6 +496,7 @@ class BatchedMCTS:
         self.planes = torch.zeros((self.rows, 5, self.R, self.C), dtype=torch.float32, device=self.device)
         self.needs_eval = torch.zeros(self.rows, dtype=torch.uint8, device=self.device)
         self._num_sims = self.max_sims
+        self._budgets = None                   # device int32 [G] the next begin() reads (set_sim_budgets); None: the scalar
         self.book, self.book_version, self._evaluator_owner = None, 0, None
 
     # -- lifetime
@@ -509,6 +526,36 @@ class BatchedMCTS:
         if int(num_sims) != self._num_sims:
             check(lib().yy_mcts_set_num_sims(self._h, int(num_sims)))
             self._num_sims = int(num_sims)
+
+    def set_sim_budgets(self, budgets):
+        """Per-game simulation budgets (device int32 [G], clamped to 0 .. max_sims on the device) of the searches begun from now
+        on, or None = every game searches the scalar again.  The context keeps the tensor alive; begin() reads it."""
+        if budgets is None and getattr(self, "_budgets", None) is None:
+            return
+        if budgets is not None:
+            _need(budgets, torch.int32, (self.G,), "num_sims")
+        check(lib().yy_mcts_set_sim_budgets(self._h, _p(budgets)))
+        self._budgets = budgets
+
+    def _sim_budgets(self, num_sims, num_sims_bound):
+        """run_search's num_sims -> (the simulation count the host issues steps for, device budgets or None for an int)."""
+        if isinstance(num_sims, (int, np.integer)):
+            if num_sims > self.max_sims:
+                raise _lib.YYError(-1, f"num_sims {num_sims} > max_sims {self.max_sims} the context was sized for")
+            return int(num_sims), None
+        if isinstance(num_sims, torch.Tensor) and num_sims.device.type != "cpu":
+            if num_sims_bound is None:
+                raise ValueError("num_sims on the device needs num_sims_bound (an int no budget exceeds): the host counts the steps "
+                                 "without reading the tensor")
+            if not 0 <= int(num_sims_bound) <= self.max_sims:
+                raise ValueError(f"num_sims_bound {num_sims_bound} outside 0 .. max_sims {self.max_sims}")
+            return int(num_sims_bound), num_sims
+        arr = np.asarray(num_sims.numpy() if isinstance(num_sims, torch.Tensor) else num_sims)
+        if arr.shape != (self.G,) or arr.dtype.kind not in "iu":
+            raise ValueError(f"num_sims: expected an int or {self.G} integers (one budget per game), got shape {arr.shape} {arr.dtype}")
+        if arr.min() < 0 or arr.max() > self.max_sims:
+            raise ValueError(f"num_sims: budgets outside 0 .. max_sims {self.max_sims}")
+        return int(arr.max()), torch.from_numpy(arr.astype(np.int32)).to(self.device)
 
     # -- the C ABI, one method per entry point
     def begin(self, boards, root_players, active=None):
@@ -612,12 +659,17 @@ class BatchedMCTS:
             check(lib().yy_mcts_reset_counters(self._h, _stream()))
 
     # -- the whole of MCTS.search for G games (mcts.py:275-343)
-    def run_search(self, boards, root_players, num_sims, evaluate, noise=None, eps=0.25, active=None, middle=None):
+    def run_search(self, boards, root_players, num_sims, evaluate, noise=None, eps=0.25, active=None, middle=None,
+                   num_sims_bound=None):
         """The ONE statement of a search's C ABI call order; search() below and search.LockstepSearch.run drive it.
         evaluate(root) -> (policy, value) of the leaf batch in self.planes, root=True on the root call (mcts.py:295, value discarded);
-        middle(n) issues the n = steps - 1 middle steps (default: n times [evaluate, step]).  num_sims == 0: the root only."""
-        if num_sims > self.max_sims:
-            raise _lib.YYError(-1, f"num_sims {num_sims} > max_sims {self.max_sims} the context was sized for")
+        middle(n) issues the n = steps - 1 middle steps (default: n times [evaluate, step]).  num_sims == 0: the root only.
+        num_sims: an int (every game; the reference's search), or one budget per game (include/yy_engine.h,
+        yy_mcts_set_sim_budgets): a host array-like of G integers in 0 .. max_sims -- the steps of its maximum are issued, a
+        game stops selecting once its root holds its budget -- or a device int32 [G] tensor with num_sims_bound, an int no
+        budget exceeds (nothing is read back; values are clamped to 0 .. max_sims on the device)."""
+        num_sims, budgets = self._sim_budgets(num_sims, num_sims_bound)
+        self.set_sim_budgets(budgets)
         if self.K > 1:
             self.set_num_sims(num_sims)                        # the last step's descents follow from it on the device
         self.begin(boards, root_players, active)
@@ -634,16 +686,17 @@ class BatchedMCTS:
                 self.step(*evaluate(False))
         self.expand_backup(*evaluate(False))                   # last simulation: no further select
 
-    def search(self, boards, root_players, evaluator, num_sims, noise=None, eps=0.25, active=None, fused=True):
+    def search(self, boards, root_players, evaluator, num_sims, noise=None, eps=0.25, active=None, fused=True,
+               num_sims_bound=None):
         """evaluator(planes f32[G*K,5,R,C]) -> (policy f32[G*K,A] softmax, value f32[G*K]) on device.
         Runs 1 + num_sims evaluator calls exactly like the reference (root call, then one per
         simulation; with K leaves per step 1 + ceil(num_sims / K)) and returns the root visit counts int32 [G,A].  fused=False:
-        every step but the last as expand_backup + select instead of the fused step kernel."""
+        every step but the last as expand_backup + select instead of the fused step kernel.  num_sims / num_sims_bound: run_search's."""
         def unfused(n):
             for _ in range(n):
                 self.expand_backup(*evaluator(self.planes))
                 self.select()
 
         self.run_search(boards, root_players, num_sims, lambda root: evaluator(self.planes), noise, eps, active,
-                        None if fused else unfused)
+                        None if fused else unfused, num_sims_bound)
         return self.root_counts()

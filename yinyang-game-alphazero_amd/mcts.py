@@ -190,20 +190,26 @@ class MCTS:
         return _HostPredictEvaluator(net, ctx, self.R, self.C)
 
     # ---- batched entry point
-    def search_batch(self, boards, players, noise=None, active=None):
+    def search_batch(self, boards, players, noise=None, active=None, num_simulations=None):
         """boards int8 [G,R,C], players int8 [G] (device tensors) -> (pi float64 [G,A], ctx).
-        noise: None or float64 [G,A] Dirichlet draws scattered to the legal actions."""
+        noise: None or float64 [G,A] Dirichlet draws scattered to the legal actions.
+        num_simulations (not in the reference): None = the constructor's; an int, or a sequence of G ints = one simulation
+        budget per game (engine.BatchedMCTS.run_search), none above the constructor's num_simulations."""
         ctx = self._context(boards.shape[0])
         ev = self._evaluator(ctx)
-        if self.use_graph and self._capturable(ev) and self.num_simulations > 8:
+        sims = self.num_simulations if num_simulations is None else num_simulations
+        if not isinstance(sims, (int, np.integer)):
+            sims = np.asarray(sims.cpu() if isinstance(sims, torch.Tensor) else sims)
+        most = int(sims.max()) if isinstance(sims, np.ndarray) and sims.size else int(sims)
+        if self.use_graph and self._capturable(ev) and most > 8:
             # device-resident evaluator: replay [forward + yy_mcts_step] from a hipGraph (one host call per simulation
             # instead of one per kernel); same launches, same results as the eager loop
             cached = self._searches.get(boards.shape[0])
             if cached is None or cached[0] is not self.neural_net:   # holds the network it captured alive
                 cached = self._searches[boards.shape[0]] = (self.neural_net, LockstepSearch(ctx, ev, use_graph=True))
-            cached[1].run(boards, players, self.num_simulations, noise=noise, eps=self.dirichlet_epsilon, active=active)
+            cached[1].run(boards, players, sims, noise=noise, eps=self.dirichlet_epsilon, active=active)
         else:
-            ctx.search(boards, players, ev, self.num_simulations, noise=noise, eps=self.dirichlet_epsilon, active=active)
+            ctx.search(boards, players, ev, sims, noise=noise, eps=self.dirichlet_epsilon, active=active)
         if self.temperature in (0, 1.0):
             pi = ctx.root_policy(temperature_zero=(self.temperature == 0))
         else:
@@ -212,7 +218,8 @@ class MCTS:
         return pi, ctx
 
     # ---- reference API (mcts.py:275-343)
-    def search(self, board, player, add_exploration_noise=False):
+    def search(self, board, player, add_exploration_noise=False, num_simulations=None):
+        """num_simulations (not in the reference): this search's simulations when not the constructor's (never more)."""
         dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
         b = torch.from_numpy(np.ascontiguousarray(board.board, dtype=np.int8)[None]).to(dev)
         pl = torch.tensor([1 if player == 1 else -1], dtype=torch.int8, device=dev)
@@ -227,7 +234,7 @@ class MCTS:
                 noise = torch.from_numpy(nz).to(dev)
         ended = float(engine.game_ended(b, pl, self.rowcol)[0])
         terminal = 0 if ended == 0.0 else (ended if ended == 0.0001 else int(ended))
-        pi, ctx = self.search_batch(b, pl, noise=noise)
+        pi, ctx = self.search_batch(b, pl, noise=noise, num_simulations=num_simulations)
         counts, cw, cp = ctx.root_counts(with_children=True)
         visits, wsum = ctx.root_stats()
         if self.board_semantics == "aliased":

@@ -104,12 +104,14 @@ class LockstepSearch:
                 self._sim_step(rows)
                 done += 1
 
-    def run(self, boards, root_players, num_sims, noise=None, eps=0.25, active=None, rows=None):
+    def run(self, boards, root_players, num_sims, noise=None, eps=0.25, active=None, rows=None, num_sims_bound=None):
         """rows: evaluate only leaf rows [0, rows) -- the caller guarantees every active game has an index below it
-        (SelfPlayEngine packs the live games to the front when a batch drains).  One graph per distinct `rows`."""
+        (SelfPlayEngine packs the live games to the front when a batch drains).  One graph per distinct `rows`.
+        num_sims / num_sims_bound: an int or per-game budgets (engine.BatchedMCTS.run_search); the captured steps do not
+        depend on them."""
         ctx = self.ctx
         ctx.bind_evaluator(self.evaluator)                     # kept evaluations / the book belong to ONE network (may drop the book)
         self._drop_stale_graphs()
         rows = ctx.G if rows is None else min(int(rows), ctx.G)
         ctx.run_search(boards, root_players, num_sims, lambda root: self._evaluate(rows, compact=not root), noise, eps, active,
-                       lambda n: self._middle_steps(rows, n))
+                       lambda n: self._middle_steps(rows, n), num_sims_bound)

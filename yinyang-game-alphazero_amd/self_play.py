@@ -63,6 +63,24 @@ def _leaf_parallel(leaves_per_step, board_semantics="copied", reference_quirks=F
     return K
 
 
+def _playout_cap(num_simulations, fast_simulations, full_search_probability):
+    """Playout-cap randomisation as the engine takes it: the keywords to hand on -- {} when it is off (fast_simulations None, or
+    full_search_probability 1: every search is a full one, today's engine), else both values.  Raises ValueError naming the
+    argument for fast_simulations outside 1 .. num_simulations or full_search_probability outside (0, 1] -- on the host, before
+    anything touches the device."""
+    P = float(full_search_probability)
+    if not 0.0 < P <= 1.0:
+        raise ValueError(f"full_search_probability={full_search_probability}: the share of full searches lies in (0, 1]")
+    if fast_simulations is None:
+        return {}
+    fast = int(fast_simulations)
+    if fast < 1:
+        raise ValueError(f"fast_simulations={fast_simulations}: a fast search runs at least 1 simulation")
+    if fast > int(num_simulations):
+        raise ValueError(f"fast_simulations={fast_simulations}: a fast search runs no more than num_simulations={num_simulations}")
+    return {} if P == 1.0 else dict(fast_simulations=fast, full_search_probability=P)
+
+
 def _play_to_completion(eng, progress=None):
     """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples."""
     moves = 0
@@ -84,7 +102,8 @@ class SelfPlayEngine:
                  board_semantics="copied", reference_quirks=False, use_graph=True, seed=0,
                  device=None, first_game_index=0, game_index_stride=1, compact_tail=True, row_tiers=None,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
-                 opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1):
+                 opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1,
+                 fast_simulations=None, full_search_probability=1.0):
         """reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
         declares `row_independent` (the split-f16 evaluator does).  The reference asks the network for every leaf: a node
         without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move order of the same search
@@ -110,8 +129,18 @@ class SelfPlayEngine:
         any K.  The None defaults of the three reuse options then mean OFF and no book is built: the leaf-parallel selection
         (k_mcts_multi) looks nothing up -- no kept pass value, no evaluation cache, no book -- and the tree context refuses the
         combination at create.  Asking for one of them explicitly, for aliased boards or for reference_quirks together with
-        K > 1 raises ValueError.  It changes which moves a search picks."""
+        K > 1 raises ValueError.  It changes which moves a search picks.
+        fast_simulations N with full_search_probability P < 1 (not in the reference; default None / 1.0 = every search runs
+        num_simulations, today's engine and launches): playout-cap randomisation.  Every move draws one uniform per game from
+        the game's own counter stream (yy_selfplay_draw_budgets: keyed by seed, global game index and ply, so not by slot, batch
+        or rank): with probability P the game searches num_simulations, else N, in the same lockstep search (per-game budgets
+        on the device, include/yy_engine.h yy_mcts_set_sim_budgets; the host issues the steps of num_simulations and reads no
+        draw).  Root noise, pi, the temperature rule, the move draw and the z labels are unchanged; only the moves searched in
+        full are recorded as examples (their `ply` is the game's ply).  N outside 1 .. num_simulations or P outside (0, 1]
+        raises ValueError."""
         assert board_semantics in ("aliased", "copied")
+        cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        self.fast_sims, self.p_full = cap.get("fast_simulations"), cap.get("full_search_probability", 1.0)
         self.K = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks,
                                 (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book)
         self.game = game
@@ -159,6 +188,9 @@ class SelfPlayEngine:
         self.hist_state = torch.zeros((G, T, self.R, self.C), dtype=torch.int8, device=dev)
         self.hist_pi = torch.zeros((G, T, self.A), dtype=torch.float32, device=dev)
         self.hist_player = torch.zeros((G, T), dtype=torch.int8, device=dev)
+        # playout cap: the examples of a game are its fully searched moves only, so an example's index is not its ply
+        self.hist_ply = torch.zeros((G, T), dtype=torch.int64, device=dev) if self.fast_sims is not None else None
+        self.recorded = 0      # examples recorded so far (== positions without playout cap)
         self.out = []          # finished examples: tuples of device tensors
         self.games_started = 0
         self.games_finished = 0
@@ -177,7 +209,8 @@ class SelfPlayEngine:
     def _pack_live_games(self):
         """Once per tier change: stable permutation of every per-slot tensor, live games first."""
         perm = torch.argsort((~self.alive).to(torch.int8), stable=True)
-        for name in ("boards", "players", "ply", "n_ex", "alive", "game_id", "hist_state", "hist_pi", "hist_player"):
+        for name in ("boards", "players", "ply", "n_ex", "alive", "game_id", "hist_state", "hist_pi", "hist_player") + (
+                ("hist_ply",) if self.hist_ply is not None else ()):
             setattr(self, name, getattr(self, name).index_select(0, perm).contiguous())
 
     # ---- slots
@@ -214,7 +247,8 @@ class SelfPlayEngine:
         if self.quirks and self.aliased:
             states = self.boards[idx][:, None].expand(-1, self.T, -1, -1)               # Q5: all alias the final board
         gid = self.game_id[idx][:, None].expand(-1, self.T)
-        plyi = torch.arange(self.T, device=self.device)[None, :].expand(idx.numel(), -1)
+        plyi = (torch.arange(self.T, device=self.device)[None, :].expand(idx.numel(), -1) if self.hist_ply is None
+                else self.hist_ply[idx])
         self.out.append((states[sel], self.hist_pi[idx][sel], z[sel].to(torch.float32), gid[sel], plyi[sel]))
         self.games_finished += int(idx.numel())
         self.n_alive -= int(idx.numel())
@@ -280,6 +314,7 @@ class SelfPlayEngine:
             self._evals_seen = evals
         n_pos, n_fin = int(host[0]), int(host[1])
         self.positions += n_pos
+        self.recorded += int(host[2]) if self.fast_sims is not None else n_pos
         if n_fin:
             with self._on_stream():
                 self._finalize(fin, fin_res, fin_player)
@@ -344,14 +379,23 @@ class SelfPlayEngine:
         elif self.eps > 0:                                                     # add_noise = (step == 0), :131
             first = (searching & (self.ply == 0)).to(torch.uint8)
             noise = engine.root_noise(self.seed, self.game_id, self.ply, first, mask_u8, self.alpha)
-        self.search.run(self.boards, rp, self.sims, noise=noise, eps=self.eps, active=s_u8, rows=self.rows)
+        record = searching                                                     # the games whose move becomes an example
+        if self.fast_sims is None:
+            self.search.run(self.boards, rp, self.sims, noise=noise, eps=self.eps, active=s_u8, rows=self.rows)
+        else:                                                                  # playout cap: a full or a fast search, game by game
+            budgets, is_full = engine.draw_budgets(self.seed, self.game_id, self.ply, s_u8, self.p_full, self.sims, self.fast_sims)
+            self.search.run(self.boards, rp, budgets, noise=noise, eps=self.eps, active=s_u8, rows=self.rows,
+                            num_sims_bound=self.sims)
+            record = searching & is_full.bool()
         pi = self.ctx.root_policy()                                            # T == 1 distribution, :329
         # ---- record the example before the move (:140): fixed-shape scatter, rows of idle games rewrite themselves
         ar, slot = self._ar, self.n_ex.clamp_max(self.T - 1)
-        self.hist_state[ar, slot] = torch.where(searching[:, None, None], self.boards, self.hist_state[ar, slot])
-        self.hist_pi[ar, slot] = torch.where(searching[:, None], pi.to(torch.float32), self.hist_pi[ar, slot])
-        self.hist_player[ar, slot] = torch.where(searching, self.players, self.hist_player[ar, slot])
-        self.n_ex += searching.to(torch.int64)
+        self.hist_state[ar, slot] = torch.where(record[:, None, None], self.boards, self.hist_state[ar, slot])
+        self.hist_pi[ar, slot] = torch.where(record[:, None], pi.to(torch.float32), self.hist_pi[ar, slot])
+        self.hist_player[ar, slot] = torch.where(record, self.players, self.hist_player[ar, slot])
+        if self.hist_ply is not None:
+            self.hist_ply[ar, slot] = torch.where(record, self.ply.to(torch.int64), self.hist_ply[ar, slot])
+        self.n_ex += record.to(torch.int64)
         # ---- choose the action (:143-160) from the game's own stream
         if self.rng == "numpy":
             action = self._numpy_actions(searching, pi, mask_u8)
@@ -370,9 +414,10 @@ class SelfPlayEngine:
         fin |= done
         fin_res = torch.where(done, ended, fin_res)
         fin_player = torch.where(done, self.players, fin_player)
-        stats = torch.stack([searching.sum(), fin.sum()])                      # the move's one host read, taken in finish_move()
+        counts = [searching.sum(), fin.sum()] + ([record.sum()] if self.fast_sims is not None else [])
+        stats = torch.stack(counts)                                            # the move's one host read, taken in finish_move()
         if self._stats_host is None:
-            self._stats_host = torch.zeros(2, dtype=stats.dtype).pin_memory()
+            self._stats_host = torch.zeros(len(counts), dtype=stats.dtype).pin_memory()
         self._stats_host.copy_(stats, non_blocking=True)
         event = torch.cuda.Event()
         event.record()
@@ -438,9 +483,12 @@ class SelfPlayLanes:
     Lane k of K plays the games first_game_index + (k + j*K) * game_index_stride, j = 0, 1, ..."""
 
     def __init__(self, game, evaluator, num_simulations=800, concurrent_games=4096, lanes=2, seed=0, device=None,
-                 first_game_index=0, game_index_stride=1, opening_book=None, leaves_per_step=1, **engine_kwargs):
+                 first_game_index=0, game_index_stride=1, opening_book=None, leaves_per_step=1, fast_simulations=None,
+                 full_search_probability=1.0, **engine_kwargs):
         """leaves_per_step: every lane's searches are leaf-parallel (SelfPlayEngine leaves_per_step; same defaults, same
-        refusals, raised here before the book or any lane is built).  The other keywords are SelfPlayEngine's."""
+        refusals, raised here before the book or any lane is built).  fast_simulations / full_search_probability: playout-cap
+        randomisation in every lane (SelfPlayEngine's; checked here first).  The other keywords are SelfPlayEngine's."""
+        cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.leaves_per_step = _leaf_parallel(leaves_per_step, engine_kwargs.get("board_semantics", "copied"),
                                               engine_kwargs.get("reference_quirks", False),
                                               [engine_kwargs.get(k) for k in ("reuse_pass_value", "reuse_transpositions", "keep_evaluations")],
@@ -460,7 +508,7 @@ class SelfPlayLanes:
                 self.lanes.append(SelfPlayEngine(game, evaluator, num_simulations=num_simulations, concurrent_games=g_k, seed=seed,
                                                  device=self.device, first_game_index=first_game_index + k * game_index_stride,
                                                  game_index_stride=K * game_index_stride, opening_book=self.book, stream=st,
-                                                 leaves_per_step=self.leaves_per_step, **engine_kwargs))
+                                                 leaves_per_step=self.leaves_per_step, **cap, **engine_kwargs))
         torch.cuda.synchronize(self.device)      # evaluator weights / the book were written on the caller's stream
         ln = self.lanes[0]
         self.G = sum(l.G for l in self.lanes)
@@ -469,6 +517,7 @@ class SelfPlayLanes:
         self.ctx = _LaneCounters(self.lanes)
 
     positions = property(lambda self: sum(l.positions for l in self.lanes))
+    recorded = property(lambda self: sum(l.recorded for l in self.lanes))
     games_finished = property(lambda self: sum(l.games_finished for l in self.lanes))
     n_alive = property(lambda self: sum(l.n_alive for l in self.lanes))
 
@@ -607,10 +656,15 @@ class SelfPlayWorker:
 
     def __init__(self, game, model_path, num_simulations=800, num_games=1, temperature_threshold=10,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
-                 board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1):
+                 board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
+                 fast_simulations=None, full_search_probability=1.0):
         """leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
-        board_semantics="copied" and reference_quirks=False, which are not this class's defaults."""
+        board_semantics="copied" and reference_quirks=False, which are not this class's defaults.
+        fast_simulations N with full_search_probability P < 1 (not in the reference): playout-cap randomisation -- before every
+        search one np.random.random() from the global stream decides between num_simulations (probability P; the move is
+        recorded) and N simulations (not recorded).  Off (the defaults) draws nothing."""
         self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks)
+        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
         self.temperature_threshold = temperature_threshold
@@ -660,8 +714,15 @@ class SelfPlayWorker:
                 player = -player
                 continue
             passes = 0
-            pi, _root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0))
-            examples.append((board, pi, player))
+            if self.playout_cap:
+                full = np.random.random() < self.playout_cap["full_search_probability"]
+                pi, _root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0),
+                                             num_simulations=None if full else self.playout_cap["fast_simulations"])
+                if full:
+                    examples.append((board, pi, player))
+            else:
+                pi, _root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0))
+                examples.append((board, pi, player))
             if temperature == 0:
                 action = np.random.choice(np.where(pi == np.max(pi))[0])
             else:
@@ -699,14 +760,16 @@ class SelfPlayManager:
                  temperature_threshold=10, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0,
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
-                 opening_book_stones=None, lanes=None, leaves_per_step=1):
-        """evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
+                 opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0):
+        """fast_simulations / full_search_probability: playout-cap randomisation (SelfPlayEngine's; checked here).
+        evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference.
         leaves_per_step K > 1: leaf-parallel searches (SelfPlayEngine leaves_per_step); evaluation_reuse=None then means off and
         opening_book_stones=None no book; evaluation_reuse=True, a book, aliased boards or reference_quirks with it raise
         ValueError here."""
         self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks, (evaluation_reuse,),
                                               opening_book_stones)
+        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -747,7 +810,7 @@ class SelfPlayManager:
                              reference_quirks=self.reference_quirks, seed=1000 + self.seed,   # key of the per-game streams: the same on every rank
                              first_game_index=first, game_index_stride=stride, device=dev,
                              reuse_pass_value=self.evaluation_reuse, reuse_transpositions=self.evaluation_reuse,
-                             keep_evaluations=self.evaluation_reuse)
+                             keep_evaluations=self.evaluation_reuse, **self.playout_cap)
         t0 = time.perf_counter()
         ex = eng.run(mine) if mine > 0 else eng.collect()
         torch.cuda.synchronize(dev)
@@ -760,16 +823,18 @@ class SelfPlayManager:
 
 
 def generate_self_play_data(game, model_path, output_dir, num_games=100, num_workers=1, num_simulations=800,
-                            reference_format=False, leaves_per_step=1, **engine_kwargs):
+                            reference_format=False, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
+                            **engine_kwargs):
     """self_play.py:337-387: same arguments and the same file name pattern.  The .npz holds plain
     tensors (`states` int8 [N,R,C], `policies` float64 [N,A], `values` float64 [N]; `boards` is an
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
-    leaves_per_step: SelfPlayManager's; the other keywords are SelfPlayManager's too."""
+    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords are SelfPlayManager's too."""
+    cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
     games_per_worker = max(1, num_games // num_workers)               # :355 (remainder dropped)
     manager = SelfPlayManager(game, model_path, num_workers=num_workers, games_per_worker=games_per_worker,
-                              num_simulations=num_simulations, leaves_per_step=leaves_per_step, **engine_kwargs)
+                              num_simulations=num_simulations, leaves_per_step=leaves_per_step, **cap, **engine_kwargs)
     ex = manager.generate_games_parallel()
     filename = publish_examples_file(ex, output_dir, reference_format)
     generate_self_play_data.last_stats = manager.stats
