@@ -170,6 +170,25 @@ int yy_mcts_set_num_sims(yy_mcts *ctx, int32_t num_sims);
  * budget; games of smaller budgets idle through the rest. */
 int yy_mcts_set_sim_budgets(yy_mcts *ctx, const int32_t *budgets_dev);
 
+/* Tree reuse across moves (not in the reference's search; opt-in: a context that never calls this behaves as before).
+ * Re-root every game's tree at the child of its root under actions[g] (DEVICE int32 [G]); to be called after a completed
+ * search (no select pending: else YY_E_STATE) and before the next yy_mcts_begin; may be called several times in a row (own
+ * move, then the opponent's).  kept_visits: DEVICE int32 [G] or NULL: the visits the new root carries, 0 = nothing kept.
+ * A game keeps its subtree when it is active without error, 0 <= actions[g] < A, its root has an edge with that action whose
+ * child is a node that is not terminal and has children; every other game (action -1, an unvisited child, a pass root, ...)
+ * is left with an empty tree.  For a kept game the subtree is compacted, in place, to the front of the game's arenas (the
+ * child becomes node 0; edges stay contiguous per node and in ascending action; priors, visits, value sums, node flags, stored
+ * values and boards are carried bit for bit), root visits = the edge's N, root value sum = the edge's W (float32).
+ * The next yy_mcts_begin consumes the mark and continues from the kept tree only if boards[g] / root_players[g] are the kept
+ * node's and the game is active -- else it builds the fresh root of every search.  On a kept root yy_mcts_expand_root ignores
+ * the policy row and mixes a non-zero noise row into the STORED priors of the root's edges, p = f32(f64(f32(1-eps)*P) +
+ * eps*noise); the search then tops the root up: it stops at root.visits == budget (the game's entry of
+ * yy_mcts_set_sim_budgets, else the scalar of yy_mcts_set_num_sims -- which K = 1 honours for kept games only), and a kept
+ * root that already holds its budget selects nothing.  The caller issues the steps of the full budget.
+ * Copied boards and leaves_per_step <= 1 only: YY_FLAG_ALIASED or K > 1 return YY_E_UNSUPPORTED.  The first call allocates
+ * the context's remap array (int32 [G, nodes_per_game], counted by yy_mcts_memory_bytes from then on). */
+int yy_mcts_advance(yy_mcts *ctx, const int32_t *actions, int32_t *kept_visits, yy_stream_t stream);
+
 /* MCTS.search prologue (mcts.py:288-295): fresh root per game from boards int8 [G,R,C] and
  * root_players int8 [G]; active uint8 [G] (NULL = all active; inactive games are skipped by every
  * later call).  Writes the root planes float32 [G,5,R,C] for evaluator call #0. */

@@ -79,6 +79,10 @@ def parse_args(argv=None):
                         "training examples (default: every move is searched in full)")
     p.add_argument("--full-search-probability", type=float, default=1.0,
                    help="share P in (0, 1] of the moves searched in full when --fast-simulations is given (default 1 = all)")
+    p.add_argument("--tree-reuse", action="store_true",
+                   help="self-play, train and evaluate: every search continues from the subtree under the move played and tops its "
+                        "root up to the move's simulations, instead of starting from a fresh root (default off; changes which "
+                        "moves are picked; not with --leaves-per-step > 1 or --board-semantics aliased)")
     return p.parse_args(argv)
 
 
@@ -95,6 +99,11 @@ def refused(args):
         for flag, given in (("--board-semantics aliased", args.board_semantics == "aliased"), ("--reference-quirks", args.reference_quirks)):
             if given:
                 return f"train_alphazero.py: --leaves-per-step {args.leaves_per_step} searches copied boards without the reference's quirks: not with {flag}"
+    if args.tree_reuse:
+        if args.leaves_per_step > 1:
+            return f"train_alphazero.py: --tree-reuse re-roots the tree for one descent per step: not with --leaves-per-step {args.leaves_per_step}"
+        if args.board_semantics == "aliased" and args.mode == "self-play":
+            return "train_alphazero.py: --tree-reuse needs every node's own board: not with --board-semantics aliased"
     return None
 
 
@@ -136,7 +145,8 @@ def main(argv=None):
                            mcts_threads=args.mcts_threads, nn_mode=args.nn, concurrent_games=args.concurrent_games,
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
                            lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
-                           fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability)
+                           fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
+                           tree_reuse=args.tree_reuse)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -149,7 +159,7 @@ def main(argv=None):
             sys.exit(f"Model file not found: {model_path}")
         res = pkg.evaluate_vs_random(game, model_path, num_games=10, num_simulations=args.simulations, nn_mode=args.nn,
                                      num_channels=args.channels, num_res_blocks=args.blocks,
-                                     leaves_per_step=args.leaves_per_step)
+                                     leaves_per_step=args.leaves_per_step, tree_reuse=args.tree_reuse)
         print(json.dumps(res))
         return
     if not os.path.exists(model_path):           # same contract as the reference (train_alphazero.py:107-109)
@@ -164,7 +174,7 @@ def main(argv=None):
                                        opening_book_stones=0 if args.leaves_per_step > 1 else args.opening_book_stones,
                                        lanes=args.lanes or None, leaves_per_step=args.leaves_per_step,
                                        fast_simulations=args.fast_simulations,
-                                       full_search_probability=args.full_search_probability)
+                                       full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

@@ -70,6 +70,7 @@ _SIGS = {
     "yy_mcts_memory_bytes": [_vp, C.POINTER(C.c_uint64)],
     "yy_mcts_set_num_sims": [_vp, C.c_int32],
     "yy_mcts_set_sim_budgets": [_vp, _vp],
+    "yy_mcts_advance": [_vp, _vp, _vp, _vp],
     "yy_mcts_begin": [_vp, _vp, _vp, _vp, _vp, _vp],
     "yy_mcts_expand_root": [_vp, _vp, _vp, C.c_double, _vp],
     "yy_mcts_select": [_vp, _vp, _vp, _vp],

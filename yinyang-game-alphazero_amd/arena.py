@@ -23,7 +23,7 @@ from . import engine
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
 from .search import LockstepSearch
-from .self_play import _playout_cap, generate_self_play_data
+from .self_play import _playout_cap, _tree_reuse, generate_self_play_data
 from .training import run_training_pipeline
 
 
@@ -105,7 +105,7 @@ class Arena:
     between two fixed networks is deterministic, as the reference's is."""
 
     def __init__(self, game, player_a, player_b, num_simulations=800, cpuct=1.0, device=None, seed=0,
-                 reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1):
+                 reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1, tree_reuse=False):
         """evaluation_reuse: inside one search a position is evaluated once (pass values, other move orders) when both players
         are row-independent compacting evaluators (the float32-accurate BatchedEvaluator); the moves are the same.
         reference_scoring=True reproduces the reference's attribution literally (alphazero.py:206-218): the value of
@@ -117,8 +117,14 @@ class Arena:
         num_simulations = 0: a search only expands the root, pi is uniform over all A actions (mcts.py:209-213) and its arg-max is
         action 0, legal or not (an illegal placement is ignored and the player flips), as the reference's select_action does.
         leaves_per_step K > 1: leaf-parallel searches (MCTS leaves_per_step); copied boards only, so not with literal=True, and
-        without evaluation reuse."""
+        without evaluation reuse.
+        tree_reuse (default off = a fresh root every move): every searching player owns a tree context of its own -- a tree
+        holds ONE network's evaluations; one per colour it plays, because yy_mcts_begin drops the kept tree of a game that sits
+        out a search, and the games where a player is black and those where it is white search on alternate moves -- which is re-rooted after every move of the game, the own one and then the
+        opponent's (engine.BatchedMCTS.advance; the reference's two reuse_tree call sites, alphazero.py:346/364), and the
+        player's next search tops the kept root up to num_simulations.  Not with literal=True or leaves_per_step > 1."""
         self.game = game
+        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, "aliased" if literal else "copied")
         self.K = max(1, int(leaves_per_step))
         if self.K > 1 and literal:
             raise ValueError("leaves_per_step > 1 needs copied boards: literal=True searches the aliased board")
@@ -154,8 +160,16 @@ class Arena:
         ctx = engine.BatchedMCTS(G, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
                                  aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse,
                                  leaves_per_step=self.K)
+        own = []           # tree_reuse: (the player moves as A, its evaluator's search on its own context)
         try:
             search = LockstepSearch(ctx, dual, use_graph=dense)     # routed mode: the row sets change every move
+            if self.tree_reuse:
+                for is_a, ev, who in ((True, ev_a, self.pa), (False, ev_b, self.pb)):
+                    for par in (0, 1):                               # games par, par + 2, ...: the player has one colour in all of them
+                        n = len(range(par, G, 2))
+                        if who != "random" and n > 0:
+                            c = engine.BatchedMCTS(n, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev)
+                            own.append((is_a, par, LockstepSearch(c, ev, use_graph=dense)))
             result = torch.zeros(G, dtype=torch.int8, device=dev)   # +1 black won, -1 white won, 2 draw
             ended_at = torch.zeros(G, dtype=torch.float64, device=dev)
             T = 4 * self.A + 8
@@ -191,7 +205,13 @@ class Arena:
                     rand_rows |= ~a_to_move
                 action = torch.full((G,), -1, dtype=torch.int32, device=dev)
                 srch = movers & ~rand_rows
-                if bool(srch.any()):
+                for is_a, par, own_search in own:                        # tree_reuse: every player searches its own trees
+                    mine = (srch & (a_to_move if is_a else ~a_to_move))[par::2]
+                    if bool(mine.any()):
+                        own_search.run(boards[par::2].contiguous(), players[par::2].contiguous(), self.sims, noise=None,
+                                       active=mine.to(torch.uint8).contiguous())
+                        action[par::2] = torch.where(mine, _lowest_argmax(own_search.ctx.root_policy()), action[par::2])
+                if not own and bool(srch.any()):
                     dual.assign(a_to_move)
                     search.run(boards, players, self.sims, noise=None, active=srch.to(torch.uint8))
                     pi = ctx.root_policy()                               # search() returns the T == 1 distribution (:329)
@@ -208,6 +228,8 @@ class Arena:
                     rec_a[ar, slot] = torch.where(movers, action, rec_a[ar, slot])
                     rec_p[ar, slot] = torch.where(movers, players, rec_p[ar, slot])
                     n_moves += movers.to(torch.int64)
+                for _, par, own_search in own:                           # the move made, whoever made it: both players' trees follow it
+                    own_search.ctx.advance(torch.where(movers, action, torch.full_like(action, -1))[par::2].contiguous())
                 old = players.clone()
                 engine.step_(boards, players, action.contiguous(), self.rowcol)
                 players = torch.where(movers, players, old).contiguous()
@@ -221,8 +243,12 @@ class Arena:
                 ended_at = torch.where(over, ended, ended_at)
                 alive &= ~over
             ctx.status()
+            for _, _, own_search in own:
+                own_search.ctx.status()
         finally:
             ctx.close()
+            for _, _, own_search in own:
+                own_search.ctx.close()
         if record:
             self.transcript = dict(actions=rec_a.cpu().numpy(), players=rec_p.cpu().numpy(), n_moves=n_moves.cpu().numpy(),
                                    results=ended_at.cpu().numpy())
@@ -246,29 +272,38 @@ class RandomPlayer:
 class AlphaZeroPlayer:
     """alphazero.py:272-365: network + MCTS behind `play(board, player) -> action` (-1 = no move)."""
 
-    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1):
+    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1, tree_reuse=False):
+        """tree_reuse: play() re-roots the search tree at the move chosen and notify() at the opponent's reply (MCTS tree_reuse),
+        so that the next play() continues from the kept subtree."""
         self.game = game
+        self.tree_reuse = bool(tree_reuse)
         net = YinYangNeuralNetwork(game)
         if os.path.exists(model_path):
             net.load_model(model_path)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.neural_net = net.to(dev).eval()
         self.mcts = MCTS(game, self.neural_net, num_simulations=num_simulations, num_threads=num_threads,
-                         board_semantics="copied", device=dev, leaves_per_step=leaves_per_step)
+                         board_semantics="copied", device=dev, leaves_per_step=leaves_per_step,
+                         tree_reuse=tree_reuse)
         self.root = None
 
     def reset(self):
         self.root = None
+        if self.tree_reuse:
+            self.mcts.reuse_tree(None, None, 1, -1)
 
     def play(self, board, player):
         valid = self.game.getValidMoves(board, player)
         if np.sum(valid) == 0:
             return -1
-        return int(self.mcts.select_action(board, player, temperature=0, valid_moves=valid))
+        action = int(self.mcts.select_action(board, player, temperature=0, valid_moves=valid))
+        if self.tree_reuse:
+            self.mcts.reuse_tree(None, board, -player, action)                  # alphazero.py:346
+        return action
 
     def notify(self, board, action):
         """alphazero.py:354-364: keep the subtree under the opponent's move (the reference never searches from it either)."""
-        if self.root is not None:
+        if self.root is not None or self.tree_reuse:
             self.root = self.mcts.reuse_tree(self.root, board, -1, action)
 
 
@@ -287,11 +322,14 @@ class AlphaZero:
                  num_simulations=800, num_epochs=10, temperature_threshold=10, update_threshold=0.6, num_workers=1,
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
-                 full_search_probability=1.0):
+                 full_search_probability=1.0, tree_reuse=False):
         """leaves_per_step K > 1 (not in the reference): leaf-parallel searches in the loop's self-play (SelfPlayManager
         leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step).
         fast_simulations / full_search_probability: playout-cap randomisation in the loop's self-play (SelfPlayEngine's); the
-        arena always searches num_simulations."""
+        arena always searches num_simulations.
+        tree_reuse: the loop's self-play and its arena continue every search from the subtree under the move played
+        (SelfPlayEngine / Arena tree_reuse); not with leaves_per_step > 1."""
+        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step)
         self.leaves_per_step = max(1, int(leaves_per_step))
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
@@ -323,7 +361,8 @@ class AlphaZero:
                                        temperature_threshold=self.temperature_threshold, nn_mode=self.nn_mode,
                                        num_channels=self.num_channels, num_res_blocks=self.num_res_blocks,
                                        concurrent_games=self.concurrent_games, seed=len(self.history),
-                                       leaves_per_step=self.leaves_per_step, **self.playout_cap)
+                                       leaves_per_step=self.leaves_per_step, **self.playout_cap,
+                                       **(dict(tree_reuse=True) if self.tree_reuse else {}))
 
     def train(self):
         # the reference passes num_iterations=1 and ignores --epochs/--batch-size/--lr (alphazero.py:120-127,
@@ -352,7 +391,7 @@ class AlphaZero:
         cur = _load_evaluator(self.game, current_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
-                     leaves_per_step=self.leaves_per_step).play(mine)
+                     leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)
@@ -395,11 +434,11 @@ class AlphaZero:
 
 
 def evaluate_vs_random(game, model_path, num_games=10, num_simulations=800, nn_mode="auto", device=None,
-                       num_channels=128, num_res_blocks=10, leaves_per_step=1):
+                       num_channels=128, num_res_blocks=10, leaves_per_step=1, tree_reuse=False):
     """`--mode evaluate` (train_alphazero.py:124-243): the model against RandomPlayer, alternating colours.  leaves_per_step:
-    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search)."""
+    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search).  tree_reuse: Arena's."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     ev = _load_evaluator(game, model_path, dev, nn_mode, num_channels, num_res_blocks)
-    res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step).play(num_games)
+    res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse).play(num_games)
     return dict(alphazero_wins=res["a_wins"], random_wins=res["b_wins"], draws=res["draws"],
                 win_rate=res["a_wins"] / num_games)

@@ -31,7 +31,7 @@
 #include "yy_bitboard.h"
 #include "yy_common.h"
 
-#define YY_VERSION 102
+#define YY_VERSION 103
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -440,7 +440,7 @@ extern "C" int yy_rules_mask_terminal_bb(const uint64_t *black, const uint64_t *
 }
 
 // =============================================================================== MCTS context
-enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6 };
+enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6, K_ROOTKEPT = 7 };
 #define CHILD_NONE 0x00FFFFFFu
 #define NF_TERMINAL 1u
 #define NF_HASVALUE 2u   // childless node whose evaluator value (record .w) may be reused (YY_FLAG_REUSE_PASS_VALUE)
@@ -484,6 +484,9 @@ struct GameState {
     int8_t root_player;
     uint8_t active, err, root_w_is_py;
     uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
+    uint8_t kept;           // yy_mcts_advance left this game's tree re-rooted at node 0; consumed by the next yy_mcts_begin
+    uint8_t root_kept;      // the root of the current search is a kept node: its own first visit expanded it, so its children's
+                            // visits sum to root_N - 1 (a fresh root's: root_N)
     int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot)
     int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
     uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
@@ -539,6 +542,7 @@ struct yy_mcts {
     int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
     const int32_t *budgets; // device int32 [G] of per-game simulation budgets for the next yy_mcts_begin; nullptr: target_sims for all
     uint64_t *scratch;      // [8] counters + overflow count
+    int32_t *remap;         // [G][node_cap] old node index -> new one (k_advance); allocated by the first yy_mcts_advance
     uint64_t bytes;
     int pending;            // 1 = a select is pending an expand_backup
 };
@@ -860,8 +864,8 @@ __device__ __forceinline__ void backup_path(uint4 *edges, const int32_t *path, c
 // The simulation budget of game g: K > 1 keeps it in mst[2g], K = 1 in GameState.budget.  `budgets` (int32 [G], clamped to
 // 0 .. max_sims here) when the caller set one (yy_mcts_set_sim_budgets), else `target` for every game.  The pointer is an
 // argument of this kernel only: the step kernels read the stored budgets, so a captured step serves every budget array.
-template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, const int32_t *budgets,
-                                                                int max_sims, const int8_t *boards,
+template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, MultiDev m, int target, int kept_target,
+                                                                const int32_t *budgets, int max_sims, const int8_t *boards,
                                                                 const int8_t *players, const uint8_t *active,
                                                                 float *planes) {
     const int g = blockIdx.x;
@@ -871,7 +875,35 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
     const bool act = active ? (active[g] != 0) : true;
     BB<NW> black, white;
     board_to_bb<NW>(boards + (size_t)g * d.geo.A, d.geo.A, black, white);
-    if (lane_id() == 0) {
+    // Tree reuse: yy_mcts_advance left the subtree of the move played at node 0.  The mark is consumed here whatever follows, so
+    // that no tree is used twice; the tree is kept only for the position it was built for (board, side to move) of an active
+    // game -- a caller that advanced by one move and searches another position gets the fresh root of every search.
+    bool keep = false;
+    if (rfl((int)st->kept)) {
+        const uint64_t *nb = d.nboard + (size_t)g * d.node_cap * 2 * NW;
+        const BB<NW> kb = bb_uniform_load<NW>(nb), kw = bb_uniform_load<NW>(nb + NW);
+        bool same = act && rfl((int)players[g]) == rfl((int)st->root_player);
+#pragma unroll
+        for (int i = 0; i < NW; i++) same = same && kb.w[i] == black.w[i] && kw.w[i] == white.w[i];
+        keep = same;
+    }
+    if (keep) {
+        // the arena, root_N, root_W and root_player stay as yy_mcts_advance left them; the search tops the root up to the budget.
+        // K = 1 stores no scalar budget for a fresh root (the host issues exactly that many steps); a kept root needs it
+        if (lane_id() == 0) {
+            st->kept = 0;
+            st->root_kept = 1;
+            st->active = 1;
+            st->err = 0;
+            st->budget = budgets ? min(max(budgets[g], 0), max_sims) : kept_target;
+            rec->kind = K_ROOTKEPT;
+            rec->node = 0;
+            rec->path_len = 0;
+            rec->dup = -1;
+        }
+    } else if (lane_id() == 0) {
+        st->kept = 0;
+        st->root_kept = 0;
         st->n_nodes = 1;  // node 0 = root
         st->n_edges = 0;
         st->root_N = 0;
@@ -902,7 +934,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
     uint64_t *gbd = d.gboard + (size_t)g * 2 * NW;
     bb_store_lane0<NW>(gbd, black);
     bb_store_lane0<NW>(gbd + NW, white);
-    if (!d.aliased) {
+    if (!d.aliased && !keep) {
         uint64_t *nb = d.nboard + (size_t)g * d.node_cap * 2 * NW;
         bb_store_lane0<NW>(nb, black);
         bb_store_lane0<NW>(nb + NW, white);
@@ -914,8 +946,10 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
         BB<NW> mask;
         bool term;
         float tv;
-        leaf_rules<NW>(d.geo, gb, black, white, rp, mask, term, tv);
-        leaf_store<NW>(rec, black, white, mask, rp, term, tv);
+        if (!keep) {
+            leaf_rules<NW>(d.geo, gb, black, white, rp, mask, term, tv);
+            leaf_store<NW>(rec, black, white, mask, rp, term, tv);
+        }
         write_planes<NW>(planes + (size_t)g * K * 5 * d.geo.A, d.geo, black, white);
     }
     if (K > 1 && lane_id() == 0) {
@@ -932,6 +966,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     // a game whose root has had its budget of simulations selects nothing, like an inactive one: no arena, no counter.  The
     // four fields are loaded before any of them is tested, so that they cost one round trip to memory, not one each
     const int s_active = st->active, s_err = st->err, s_budget = st->budget;
+    const int s_kept = st->root_kept;
     int s_carry = st->root_N;
     s_carry = rfl(s_carry);
     if ((rfl(s_active) == 0) | (rfl(s_err) != 0) | (s_carry >= rfl(s_budget))) {
@@ -941,6 +976,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         }
         return;
     }
+    s_carry -= rfl(s_kept);   // a kept root (tree reuse) was itself expanded by its first visit: its children hold root_N - 1
     const GeoBB<NW> gb = geo_bb<NW>(d.geo);
     const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
     uint4 *edges = d.edges + (size_t)g * d.edge_cap;
@@ -1040,6 +1076,29 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
     }
 }
 
+// Root noise on a kept root (tree reuse): the root's edges exist, so the draw is mixed into their STORED priors with the very
+// sequence expand_leaf uses on a fresh root (mcts.py:310-312); a row that is zero over the root's moves drew nothing.  Only a
+// root is ever noised and yy_mcts_advance drops it, so the priors below a root are always the raw ones.
+__device__ __forceinline__ void noise_kept_root(const MctsDev &d, const int g, const uint4 *nodes, uint4 *edges,
+                                                const double *noise, const double eps) {
+    const int lane = lane_id();
+    const uint4 hdr = nodes[0];
+    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+    const double *nrow = noise + (size_t)g * d.geo.A;
+    uint64_t any = 0;
+    for (int j0 = 0; j0 < k; j0 += 64) {
+        const int j = j0 + lane;
+        any |= __ballot(j < k && nrow[edges[first + j].w >> 24] != 0.0);
+    }
+    if (!any) return;
+    const float keep = (float)(1.0 - eps);
+    for (int j = lane; j < k; j += 64) {
+        uint4 *e = edges + first + j;
+        const float kp = __fmul_rn(keep, __uint_as_float(e->x));
+        e->x = __float_as_uint((float)__dadd_rn((double)kp, __dmul_rn(eps, nrow[e->w >> 24])));
+    }
+}
+
 // ---- expansion + backup: mcts.py:50-91 (expand_leaf), 147-156 + 406-412 (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, const float *policy,
@@ -1050,6 +1109,11 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
     if (kind == K_NONE) return;
     const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
     uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    if (kind == K_ROOTKEPT) {   // yy_mcts_expand_root on a kept root: already expanded, the policy row is not read
+        if (noise) noise_kept_root(d, g, nodes, edges, noise, eps);
+        if (lane == 0) st->leaf.kind = K_NONE;
+        return;
+    }
     const int32_t *path = d.path + (size_t)g * d.path_cap;
     const int depth = rfl(st->leaf.path_len);
     const int node = rfl(st->leaf.node);
@@ -1256,6 +1320,147 @@ template <int NW> __global__ void __launch_bounds__(64) k_mcts_multi(MctsDev d, 
     if (do_sel) do_select_multi<NW>(d, m, g, planes, needs_eval);
 }
 
+// =============================================================================== tree reuse: re-root at the move played
+// k_advance re-roots game g's tree at the child of its root under actions[g] and compacts that child's subtree to the front of
+// the game's node, edge and board arenas, in place.  It relies on how expand_leaf grows a copied-board tree:
+//   * a node with children gets its record and its edge range in the same call (K_EXPAND; the root: k_begin + K_ROOTINIT before
+//     anything else), so node indices and the edge ranges of the nodes that have one both ascend in creation order;
+//   * a child is created after its parent: its index is the larger one;
+//   * a childless node that is expanded again (K_REEXPAND) has k = 0 again -- its board never changes -- so its first-edge
+//     field, the only one that does not ascend, names no edge.
+// Hence one ascending pass over the old indices decides membership (a node is kept iff its parent was, and the parent came
+// earlier), the new index of a kept node is its rank among the kept ones, and with new <= old for node records, boards and edge
+// ranges every move goes downwards onto records the pass has already left behind: no second copy of the arenas.  A second,
+// parallel pass rewrites the child indices inside the kept edges through remap[].
+// The chain over the nodes is serial; per 64 nodes it costs one round trip for the headers and the marks, plus one per KEPT node
+// for its edges (marks inside the 64-node window travel through LDS, the others through remap[]).
+template <int NW> __global__ void __launch_bounds__(64) k_advance(MctsDev d, const int32_t *actions, int32_t *kept_visits,
+                                                                  int32_t *remap_all) {
+    __shared__ int32_t win[64];
+    const int g = blockIdx.x, lane = lane_id();
+    GameState *st = d.state + g;
+    uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    uint64_t *nboard = d.nboard + (size_t)g * d.node_cap * 2 * NW;
+    int32_t *remap = remap_all + (size_t)g * d.node_cap;
+    const int n_nodes = rfl(st->n_nodes), n_edges = rfl(st->n_edges);
+    const int a = rfl(actions[g]);
+    const uint4 rhdr = nodes[0];
+    const int rk = node_k(rfl(rhdr.y)), rfirst = rfl((int)rhdr.x);
+    // ---- the edge of the move played, and whether its subtree is kept
+    int child = -1, keptN = 0;
+    float keptW = 0.0f;
+    bool ok = rfl((int)st->active) != 0 && rfl((int)st->err) == 0 && a >= 0 && a < d.geo.A && n_nodes <= (int)d.node_cap &&
+              rk > 0 && rfirst >= 0 && rfirst + rk <= n_edges && n_edges <= (int)d.edge_cap;
+    if (ok) {
+        ok = false;
+        for (int j0 = 0; j0 < rk; j0 += 64) {
+            const int j = j0 + lane;
+            const uint4 e = (j < rk) ? edges[rfirst + j] : make_uint4(0u, 0u, 0u, 0xFF000000u | CHILD_NONE);
+            const uint64_t hit = __ballot(j < rk && (int)(e.w >> 24) == a);
+            if (hit) {
+                const int l = (int)__ffsll((unsigned long long)hit) - 1;
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)e.w, l);
+                keptN = __builtin_amdgcn_readlane((int)e.y, l);
+                keptW = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)e.z, l));
+                child = (int)(w & CHILD_NONE);
+                ok = (w & CHILD_NONE) != CHILD_NONE && child > 0 && child < n_nodes;
+                break;
+            }
+        }
+    }
+    uint32_t chy = 0;
+    if (ok) {
+        chy = rfl(nodes[child].y);
+        ok = !(node_flags(chy) & NF_TERMINAL) && node_k(chy) > 0;   // a terminal or childless position is searched afresh
+    }
+    if (!ok) {
+        // nothing kept: the tree is emptied, so that a second advance finds no edge and the next yy_mcts_begin starts afresh
+        if (lane == 0) {
+            st->kept = 0;
+            st->n_nodes = 1;
+            st->n_edges = 0;
+            st->root_N = 0;
+            st->root_W = 0.0f;
+            st->root_W_py = 0.0;
+            st->root_w_is_py = 1;
+            nodes[0] = make_uint4(0u, node_pack(0, 0, node_player(rfl(rhdr.y))), 0u, 0u);
+            if (kept_visits) kept_visits[g] = 0;
+        }
+        return;
+    }
+    // ---- pass 1: membership, ranks and the moves, ascending
+    for (int i = child + lane; i < n_nodes; i += 64) remap[i] = (i == child) ? 0 : -1;
+    __syncthreads();
+    int rank = 0, ne = 0;          // kept nodes / kept edges so far == the next new index / first edge
+    bool bad = false;
+    for (int base = child; base < n_nodes; base += 64) {
+        __syncthreads();           // the marks earlier windows stored beyond themselves
+        const int mine = base + lane;
+        const uint4 hdr = (mine < n_nodes) ? nodes[mine] : make_uint4(0u, 0u, 0u, 0u);
+        win[lane] = (mine < n_nodes) ? remap[mine] : -1;
+        __syncthreads();
+        for (int t = 0; t < 64 && base + t < n_nodes; t++) {
+            if (rfl(win[t]) < 0) continue;
+            const int i = base + t;
+            const uint32_t hy = (uint32_t)__builtin_amdgcn_readlane((int)hdr.y, t);
+            const int first = __builtin_amdgcn_readlane((int)hdr.x, t);
+            const int k = (node_flags(hy) & NF_TERMINAL) ? 0 : node_k(hy);
+            if (k > 0 && (first < ne || first + k > n_edges)) { bad = true; break; }   // never in a tree expand_leaf built
+            for (int j0 = 0; j0 < k; j0 += 64) {
+                const int j = j0 + lane;
+                if (j < k) {
+                    const uint4 e = edges[first + j];
+                    edges[ne + j] = e;                                   // ne <= first: onto edges already moved or dropped
+                    const int c = (int)(e.w & CHILD_NONE);
+                    if ((e.w & CHILD_NONE) != CHILD_NONE && c > i && c < n_nodes) {
+                        if (c < base + 64) win[c - base] = 0;
+                        else remap[c] = 0;
+                    }
+                }
+            }
+            if (lane == 0) {
+                nodes[rank] = make_uint4(k > 0 ? (uint32_t)ne : 0u, hy, (uint32_t)__builtin_amdgcn_readlane((int)hdr.z, t),
+                                         (uint32_t)__builtin_amdgcn_readlane((int)hdr.w, t));
+                remap[i] = rank;
+            }
+            if (rank != i && lane < 2 * NW) nboard[(size_t)rank * 2 * NW + lane] = nboard[(size_t)i * 2 * NW + lane];
+            rank++;
+            ne += k;
+            __syncthreads();       // win[] marks of this node's children before the next node's test
+        }
+        if (bad) break;
+    }
+    __syncthreads();
+    // ---- pass 2: the child indices inside the kept edges
+    if (!bad)
+        for (int e = lane; e < ne; e += 64) {
+            const uint32_t w = edges[e].w;
+            const uint32_t c = w & CHILD_NONE;
+            if (c != CHILD_NONE) {
+                const int nc = (c < (uint32_t)n_nodes) ? remap[c] : -1;
+                edges[e].w = (w & 0xFF000000u) | (nc >= 0 ? (uint32_t)nc : CHILD_NONE);
+            }
+        }
+    if (lane == 0) {
+        if (bad) {                 // an inconsistent arena: the game fails like one whose arena overflowed
+            st->err = st->err_ever = 1;
+            st->kept = 0;
+            if (kept_visits) kept_visits[g] = 0;
+        } else {
+            st->n_nodes = rank;
+            st->n_edges = ne;
+            st->root_N = keptN;
+            st->root_W = keptW;
+            st->root_W_py = 0.0;
+            st->root_w_is_py = 0;
+            st->root_player = (int8_t)node_player(chy);
+            st->kept = 1;
+            if (kept_visits) kept_visits[g] = keptN;
+        }
+    }
+}
+
 template <int NW> __global__ void __launch_bounds__(64) k_root_counts(MctsDev d, int32_t *counts, float *cw, float *cp) {
     const int g = blockIdx.x, A = d.geo.A;
     const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
@@ -1446,7 +1651,7 @@ extern "C" int yy_mcts_destroy(yy_mcts *c) {
     if (!c) return YY_OK;
     const MctsDev &d = c->dev;
     void *ps[] = {d.edges, d.nodes, d.nboard, d.gboard, d.path, d.state, d.sqrt_tab, c->scratch, d.ec.meta, d.ec.key, d.ec.val, d.ec.pol,
-                  c->multi.leaves, c->multi.mst};
+                  c->multi.leaves, c->multi.mst, c->remap};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     delete c;
@@ -1476,10 +1681,31 @@ extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *pla
                              float *planes, yy_stream_t s) {
     if (!c || !boards || !players || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
     DISPATCH_NW(c->dev.geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi,
-                                                   c->multi.K > 1 ? c->target_sims : 0x7FFFFFFF, c->budgets, c->cfg.max_sims,
+                                                   c->multi.K > 1 ? c->target_sims : 0x7FFFFFFF, c->target_sims, c->budgets, c->cfg.max_sims,
                                                    boards, players, active, planes));
     HIP_TRY(hipGetLastError());
     c->pending = 2;  // root expansion pending
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_advance(yy_mcts *c, const int32_t *actions, int32_t *kept_visits, yy_stream_t s) {
+    if (!c || !actions) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (c->cfg.flags & YY_FLAG_ALIASED)
+        return set_err(YY_E_UNSUPPORTED, "yy_mcts_advance needs copied boards: with the aliased board a node's position changes between visits%s%s");
+    if (c->multi.K > 1) return set_err(YY_E_UNSUPPORTED, "yy_mcts_advance: leaves_per_step > 1 does not support tree reuse%s%s");
+    if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_advance with a select or a root expansion pending%s%s");
+    if (!c->remap) {
+        const size_t n = (size_t)c->cfg.G * c->dev.node_cap * sizeof(int32_t);
+        const hipError_t me = hipMalloc((void **)&c->remap, n);
+        if (me != hipSuccess) {
+            (void)hipGetLastError();
+            c->remap = nullptr;
+            return set_err(YY_E_NOMEM, "hipMalloc failed: %s%s", hipGetErrorString(me), " (tree reuse remap array)");
+        }
+        c->bytes += n;
+    }
+    DISPATCH_NW(c->dev.geo.NW, k_advance<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, actions, kept_visits, c->remap));
+    HIP_TRY(hipGetLastError());
     return YY_OK;
 }
 

@@ -566,6 +566,19 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_begin(self._h, _p(boards), _p(root_players), _p(active), _p(self.planes), _stream()))
 
+    def advance(self, actions):
+        """Tree reuse (include/yy_engine.h, yy_mcts_advance): re-root every game's tree at the child of its root under
+        actions[g] (device int32 [G]; -1 = keep nothing) after a finished search; may be called again for the opponent's reply.
+        Returns kept_visits (device int32 [G]): the visits the new root carries, 0 where the next search starts from a fresh
+        root.  The next begin() continues from the kept tree where its board and player are the kept node's, and the search
+        tops the root up to its budget.  Copied boards, leaves_per_step == 1."""
+        _need(actions, torch.int32, (self.G,), "actions")
+        kept = torch.empty(self.G, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_advance(self._h, _p(actions), _p(kept), _stream()))
+        self._advanced = True
+        return kept
+
     def expand_root(self, policy, noise=None, eps=0.25):
         _need(policy, torch.float32, (self.rows, self.A), "policy")
         if noise is not None:
@@ -670,8 +683,9 @@ class BatchedMCTS:
         budget exceeds (nothing is read back; values are clamped to 0 .. max_sims on the device)."""
         num_sims, budgets = self._sim_budgets(num_sims, num_sims_bound)
         self.set_sim_budgets(budgets)
-        if self.K > 1:
-            self.set_num_sims(num_sims)                        # the last step's descents follow from it on the device
+        if self.K > 1 or getattr(self, "_advanced", False):
+            # K > 1: the last step's descents follow from it on the device; K = 1: the budget of a kept root (tree reuse)
+            self.set_num_sims(num_sims)
         self.begin(boards, root_players, active)
         policy, _ = evaluate(True)
         self.expand_root(policy, noise, eps)

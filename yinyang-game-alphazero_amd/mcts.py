@@ -135,7 +135,7 @@ class _HostPredictEvaluator:
 class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
-                 board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1):
+                 board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False):
         """board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
         evaluation_reuse (not in the reference; default off = its evaluator call sequence): a position is evaluated once per
@@ -146,8 +146,15 @@ class MCTS:
         leaves_per_step K (not in the reference; default 1 = its search): leaf parallelism with virtual visits -- every step
         runs K descents per game and evaluates their leaves in one batch, so a search takes ceil(num_simulations / K)
         evaluator calls (include/yy_engine.h).  Needs board_semantics="copied" and no evaluation_reuse.  It changes which
-        moves a search picks."""
+        moves a search picks.
+        tree_reuse (default False = the reference, whose reuse_tree result never reaches search): reuse_tree() also re-roots
+        the tree on the device at the move taken (engine.BatchedMCTS.advance) and the next search(board, player) of that
+        position continues from the kept subtree, topping its root up to num_simulations; search_batch likewise after
+        advance_batch(actions).  Needs board_semantics="copied" and leaves_per_step == 1 (ValueError otherwise)."""
         assert board_semantics in ("aliased", "copied")
+        if tree_reuse and (board_semantics == "aliased" or max(1, int(leaves_per_step)) > 1):
+            raise ValueError('tree_reuse=True needs board_semantics="copied" and leaves_per_step == 1')
+        self.tree_reuse = bool(tree_reuse)
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
         self.num_threads = max(1, num_threads)
@@ -267,7 +274,18 @@ class MCTS:
         return np.random.choice(np.arange(len(action_probs)), p=action_probs)
 
     # ---- mcts.py:481-505; the reference never feeds the result back into search (dead code there)
+    def advance_batch(self, actions):
+        """tree_reuse: re-root the trees of the last search_batch at actions (device int32 [G], -1 = keep nothing); returns
+        kept_visits (device int32 [G]).  Call it once per move made, the opponent's included."""
+        if not self.tree_reuse:
+            raise ValueError("advance_batch needs MCTS(tree_reuse=True)")
+        return self._context(actions.shape[0]).advance(actions)
+
     def reuse_tree(self, old_root, board, player, action_taken):
+        if self.tree_reuse and 1 in self._ctx:
+            ctx = self._ctx[1]
+            a = -1 if action_taken is None else int(action_taken)
+            ctx.advance(torch.tensor([a], dtype=torch.int32, device=ctx.device))
         if old_root is not None and action_taken in old_root.children:
             new_root = old_root.children[action_taken]
             new_root.parent = None

@@ -63,6 +63,19 @@ def _leaf_parallel(leaves_per_step, board_semantics="copied", reference_quirks=F
     return K
 
 
+def _tree_reuse(tree_reuse, leaves_per_step=1, board_semantics="copied"):
+    """tree_reuse as the engine takes it.  The re-rooting kernel works on copied boards and one descent per step
+    (include/yy_engine.h, yy_mcts_advance): together with leaves_per_step > 1 or aliased boards it raises ValueError -- on the
+    host, before anything touches the device."""
+    if not tree_reuse:
+        return False
+    if max(1, int(leaves_per_step)) > 1:
+        raise ValueError(f"tree_reuse=True: the tree is re-rooted for one descent per step only -- not with leaves_per_step={leaves_per_step}")
+    if board_semantics == "aliased":
+        raise ValueError('tree_reuse=True: a kept subtree needs every node\'s own board -- not with board_semantics="aliased"')
+    return True
+
+
 def _playout_cap(num_simulations, fast_simulations, full_search_probability):
     """Playout-cap randomisation as the engine takes it: the keywords to hand on -- {} when it is off (fast_simulations None, or
     full_search_probability 1: every search is a full one, today's engine), else both values.  Raises ValueError naming the
@@ -103,7 +116,7 @@ class SelfPlayEngine:
                  device=None, first_game_index=0, game_index_stride=1, compact_tail=True, row_tiers=None,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0):
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
         """reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
         declares `row_independent` (the split-f16 evaluator does).  The reference asks the network for every leaf: a node
         without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move order of the same search
@@ -137,8 +150,17 @@ class SelfPlayEngine:
         on the device, include/yy_engine.h yy_mcts_set_sim_budgets; the host issues the steps of num_simulations and reads no
         draw).  Root noise, pi, the temperature rule, the move draw and the z labels are unchanged; only the moves searched in
         full are recorded as examples (their `ply` is the game's ply).  N outside 1 .. num_simulations or P outside (0, 1]
-        raises ValueError."""
+        raises ValueError.
+        tree_reuse (not in the reference's search; default off = every move starts from a fresh root, today's games and
+        launches): after the move draw every game's tree is re-rooted at the move played (engine.BatchedMCTS.advance; -1 = keep
+        nothing for the games that did not search or that ended), and the next search continues from that subtree and tops its
+        root up to the move's budget -- num_simulations, or the playout-cap draw.  The host issues the same steps; a game
+        whose kept root already holds part of its budget asks for fewer evaluator rows.  A kept tree belongs to its slot: when
+        the draining batch is packed (compact_tail) every tree is dropped once, so with tree_reuse a game's transcript depends
+        on when that happens.  It changes which moves a search picks.  Not with leaves_per_step > 1 or aliased boards:
+        ValueError."""
         assert board_semantics in ("aliased", "copied")
+        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
         cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.fast_sims, self.p_full = cap.get("fast_simulations"), cap.get("full_search_probability", 1.0)
         self.K = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks,
@@ -337,6 +359,8 @@ class SelfPlayEngine:
             if need < self.rows:
                 self._pack_live_games()
                 self.rows = need
+                if self.tree_reuse:                                            # the kept trees stayed in the old slots
+                    self.ctx.advance(torch.full((G,), -1, dtype=torch.int32, device=dev))
         ones = self._ones
         pending = self.alive.clone()
         searching = torch.zeros(G, dtype=torch.bool, device=dev)
@@ -414,6 +438,9 @@ class SelfPlayEngine:
         fin |= done
         fin_res = torch.where(done, ended, fin_res)
         fin_player = torch.where(done, self.players, fin_player)
+        if self.tree_reuse:
+            # re-root every tree at the move played; a game that ended (its slot may be refilled) or did not search keeps nothing
+            self.kept_visits = self.ctx.advance(torch.where(fin, torch.full_like(action, -1), action))
         counts = [searching.sum(), fin.sum()] + ([record.sum()] if self.fast_sims is not None else [])
         stats = torch.stack(counts)                                            # the move's one host read, taken in finish_move()
         if self._stats_host is None:
@@ -486,9 +513,10 @@ class SelfPlayLanes:
                  first_game_index=0, game_index_stride=1, opening_book=None, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, **engine_kwargs):
         """leaves_per_step: every lane's searches are leaf-parallel (SelfPlayEngine leaves_per_step; same defaults, same
-        refusals, raised here before the book or any lane is built).  fast_simulations / full_search_probability: playout-cap
+        refusals, raised here before the book or any lane is built).  tree_reuse=True (a SelfPlayEngine keyword): likewise.  fast_simulations / full_search_probability: playout-cap
         randomisation in every lane (SelfPlayEngine's; checked here first).  The other keywords are SelfPlayEngine's."""
         cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        _tree_reuse(engine_kwargs.get("tree_reuse", False), leaves_per_step, engine_kwargs.get("board_semantics", "copied"))
         self.leaves_per_step = _leaf_parallel(leaves_per_step, engine_kwargs.get("board_semantics", "copied"),
                                               engine_kwargs.get("reference_quirks", False),
                                               [engine_kwargs.get(k) for k in ("reuse_pass_value", "reuse_transpositions", "keep_evaluations")],
@@ -657,12 +685,16 @@ class SelfPlayWorker:
     def __init__(self, game, model_path, num_simulations=800, num_games=1, temperature_threshold=10,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0):
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
         """leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
         board_semantics="copied" and reference_quirks=False, which are not this class's defaults.
         fast_simulations N with full_search_probability P < 1 (not in the reference): playout-cap randomisation -- before every
         search one np.random.random() from the global stream decides between num_simulations (probability P; the move is
-        recorded) and N simulations (not recorded).  Off (the defaults) draws nothing."""
+        recorded) and N simulations (not recorded).  Off (the defaults) draws nothing.
+        tree_reuse=True (not in the reference's search): play_game hands the root and the move played to MCTS.reuse_tree, as
+        the reference does at self_play.py:192, and the next search continues from that subtree (MCTS tree_reuse); needs
+        board_semantics="copied"."""
+        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
         self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks)
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.game, self.model_path = game, model_path
@@ -681,7 +713,7 @@ class SelfPlayWorker:
         self.mcts = MCTS(game, neural_net, num_simulations=num_simulations, cpuct=cpuct,
                          dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                          num_threads=num_parallel, board_semantics=board_semantics, device=device,
-                         leaves_per_step=self.leaves_per_step)
+                         leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse)
 
     def play_game(self):
         game, examples = self.game, []
@@ -716,12 +748,12 @@ class SelfPlayWorker:
             passes = 0
             if self.playout_cap:
                 full = np.random.random() < self.playout_cap["full_search_probability"]
-                pi, _root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0),
-                                             num_simulations=None if full else self.playout_cap["fast_simulations"])
+                pi, root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0),
+                                            num_simulations=None if full else self.playout_cap["fast_simulations"])
                 if full:
                     examples.append((board, pi, player))
             else:
-                pi, _root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0))
+                pi, root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0))
                 examples.append((board, pi, player))
             if temperature == 0:
                 action = np.random.choice(np.where(pi == np.max(pi))[0])
@@ -738,6 +770,8 @@ class SelfPlayWorker:
                 nb.board = board.board.copy()
                 board = nb
             board, player = game.getNextState(board, player, action)
+            if self.tree_reuse:
+                self.mcts.reuse_tree(root, board, player, int(action))                 # self_play.py:192
             step += 1
             result = game.getGameEnded(board, player)
             if result != 0:
@@ -760,8 +794,10 @@ class SelfPlayManager:
                  temperature_threshold=10, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0,
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
-                 opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0):
+                 opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
+                 tree_reuse=False):
         """fast_simulations / full_search_probability: playout-cap randomisation (SelfPlayEngine's; checked here).
+        tree_reuse: every search continues from the subtree under the move played (SelfPlayEngine's; checked here).
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference.
         leaves_per_step K > 1: leaf-parallel searches (SelfPlayEngine leaves_per_step); evaluation_reuse=None then means off and
@@ -770,6 +806,7 @@ class SelfPlayManager:
         self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks, (evaluation_reuse,),
                                               opening_book_stones)
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -810,7 +847,8 @@ class SelfPlayManager:
                              reference_quirks=self.reference_quirks, seed=1000 + self.seed,   # key of the per-game streams: the same on every rank
                              first_game_index=first, game_index_stride=stride, device=dev,
                              reuse_pass_value=self.evaluation_reuse, reuse_transpositions=self.evaluation_reuse,
-                             keep_evaluations=self.evaluation_reuse, **self.playout_cap)
+                             keep_evaluations=self.evaluation_reuse, **self.playout_cap,
+                             **(dict(tree_reuse=True) if self.tree_reuse else {}))
         t0 = time.perf_counter()
         ex = eng.run(mine) if mine > 0 else eng.collect()
         torch.cuda.synchronize(dev)
@@ -829,7 +867,8 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     tensors (`states` int8 [N,R,C], `policies` float64 [N,A], `values` float64 [N]; `boards` is an
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
-    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords are SelfPlayManager's too."""
+    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords (tree_reuse among them) are
+    SelfPlayManager's too."""
     cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
     games_per_worker = max(1, num_games // num_workers)               # :355 (remainder dropped)
