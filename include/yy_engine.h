@@ -394,6 +394,55 @@ int yy_selfplay_draw_budgets(uint64_t seed, const int64_t *game_id, const int32_
                              double p_full, int full_sims, int fast_sims, int32_t *budgets, uint8_t *is_full,
                              yy_stream_t stream);
 
+/* ------------------------------------------------------------------ free-running self-play (not in the reference; opt-in)
+ * The move of the episode loop as a device kernel inside the search step (csrc/yy_selfplay_move.hip): a game whose search is
+ * complete -- no pending leaf, root.visits == its budget -- plays its move in the same step and sets up the root of its next
+ * search, while the other games of the context keep simulating.  One step is
+ *     <evaluator on planes, rows with needs_eval != 0>  ->  yy_mcts_step_selfplay
+ * and a move costs budget + 1 steps of that game only.  A game's transcript is the lockstep engine's bit for bit: pi, the
+ * example record, the move draw (yy_selfplay_sample_actions), getNextState, getGameEnded, up to two passes at the new position
+ * (flip on no move, end on the second, 0 -> 1e-4), the root prologue of yy_mcts_begin, the playout-cap draw
+ * (yy_selfplay_draw_budgets) and, at ply 0 with epsilon > 0, the noise row (yy_selfplay_root_noise; zeros at every other ply)
+ * are the same device functions.  A finished game's examples are labelled (z by player against the final player) and appended
+ * to the run's example buffer (rows reserved with one atomic add), and the run's next game starts in the slot from the empty
+ * board, black to move, with id first_game_index + k * stride (k from an atomic counter); past the target the slot goes idle.
+ * A game whose search failed (yy_mcts_status) is abandoned, its examples dropped, counted, and its slot refilled.
+ * Needs copied boards and leaves_per_step <= 1: else YY_E_UNSUPPORTED.  Re-rooting (yy_mcts_advance) is not offered here. */
+typedef struct yy_selfplay_config {
+    uint64_t seed;                   /* key of the per-game counter streams */
+    double dirichlet_alpha;          /* positive and finite when dirichlet_epsilon > 0 */
+    double dirichlet_epsilon;        /* 0: no noise, the step passes no noise array */
+    double full_search_probability;  /* playout cap: P (with fast_simulations > 0) */
+    int32_t temperature_threshold;
+    int32_t num_simulations;         /* budget of a (full) search, 1 .. max_sims of the context */
+    int32_t fast_simulations;        /* 0 = no playout cap; else 1 .. num_simulations */
+    int32_t reserved;
+    int64_t example_capacity;        /* rows of the example buffer; a run needs at most num_games * (R*C + 2) */
+} yy_selfplay_config;
+
+typedef struct yy_selfplay_run yy_selfplay_run; /* opaque; one per context */
+
+/* sync. Allocates, on the current device, the per-slot state (board, player, ply, game id, example history), the noise array
+ * float64 [G,A], the counters and the example buffer. */
+int yy_selfplay_run_create(yy_mcts *ctx, const yy_selfplay_config *cfg, yy_selfplay_run **out);
+int yy_selfplay_run_destroy(yy_selfplay_run *run);
+/* Starts a run of num_games games: counters and example buffer reset, game j < G starts in slot j (root pending, planes in row
+ * j, needs_eval[j] = 1), the other slots idle.  planes float32 [G,5,R,C] and needs_eval uint8 [G] are the step's. */
+int yy_selfplay_run_arm(yy_mcts *ctx, yy_selfplay_run *run, int64_t num_games, int64_t first_game_index, int64_t stride,
+                        float *planes, uint8_t *needs_eval, yy_stream_t stream);
+/* One step: yy_mcts_step's launch with the run's noise array (only a root expansion mixes noise) + the move kernel.  Two
+ * launches, no host read: capturable.  policy float32 [G,A] / value float32 [G] of the rows flagged by the previous call. */
+int yy_mcts_step_selfplay(yy_mcts *ctx, yy_selfplay_run *run, const float *policy, const float *value, float *planes,
+                          uint8_t *needs_eval, yy_stream_t stream);
+/* Asynchronous copy of the counters to out (HOST, pinned; uint64 [8]) on `stream`; no device synchronisation:
+ * {games started (may run past the target), finished, failed, positions searched, examples recorded, example rows reserved,
+ * games whose rows did not fit the buffer (nothing is written past it; the caller must treat > 0 as an error), target}. */
+int yy_selfplay_run_counters(yy_selfplay_run *run, uint64_t *out, yy_stream_t stream);
+/* Rows [first, first + count) of the example buffer, in the order the games finished, copied on `stream` to states int8
+ * [count,R,C], policies float32 [count,A], values float32 [count], game_id int64 [count], ply int64 [count] (device). */
+int yy_selfplay_run_examples(yy_selfplay_run *run, int64_t first, int64_t count, int8_t *states, float *policies,
+                             float *values, int64_t *game_id, int64_t *ply, yy_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,10 @@ def parse_args(argv=None):
                    help="self-play, train and evaluate: every search continues from the subtree under the move played and tops its "
                         "root up to the move's simulations, instead of starting from a fresh root (default off; changes which "
                         "moves are picked; not with --leaves-per-step > 1 or --board-semantics aliased)")
+    p.add_argument("--free-running", action="store_true",
+                   help="self-play and train: the games play their moves on the device, inside the search step, each as soon as its "
+                        "own search is complete, instead of in lockstep (default off; the same games; not with --leaves-per-step "
+                        "> 1, --board-semantics aliased, --reference-quirks or --tree-reuse)")
     return p.parse_args(argv)
 
 
@@ -104,6 +108,12 @@ def refused(args):
             return f"train_alphazero.py: --tree-reuse re-roots the tree for one descent per step: not with --leaves-per-step {args.leaves_per_step}"
         if args.board_semantics == "aliased" and args.mode == "self-play":
             return "train_alphazero.py: --tree-reuse needs every node's own board: not with --board-semantics aliased"
+    if args.free_running and args.mode in ("self-play", "train"):
+        for flag, given in ((f"--leaves-per-step {args.leaves_per_step}", args.leaves_per_step > 1),
+                            ("--board-semantics aliased", args.board_semantics == "aliased" and args.mode == "self-play"),
+                            ("--reference-quirks", args.reference_quirks and args.mode == "self-play"), ("--tree-reuse", args.tree_reuse)):
+            if given:
+                return f"train_alphazero.py: --free-running plays copied boards, one descent per step, a fresh root per move: not with {flag}"
     return None
 
 
@@ -146,7 +156,7 @@ def main(argv=None):
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
                            lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
                            fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
-                           tree_reuse=args.tree_reuse)
+                           tree_reuse=args.tree_reuse, free_running=args.free_running)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -174,7 +184,8 @@ def main(argv=None):
                                        opening_book_stones=0 if args.leaves_per_step > 1 else args.opening_book_stones,
                                        lanes=args.lanes or None, leaves_per_step=args.leaves_per_step,
                                        fast_simulations=args.fast_simulations,
-                                       full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse)
+                                       full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse,
+                                       free_running=args.free_running)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

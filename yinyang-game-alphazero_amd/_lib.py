@@ -33,11 +33,19 @@ class MctsConfig(C.Structure):
                 ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32)]
 
 
+class SelfPlayConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("dirichlet_alpha", C.c_double), ("dirichlet_epsilon", C.c_double),
+                ("full_search_probability", C.c_double), ("temperature_threshold", C.c_int32),
+                ("num_simulations", C.c_int32), ("fast_simulations", C.c_int32), ("reserved", C.c_int32),
+                ("example_capacity", C.c_int64)]
+
+
 def build(force=False, verbose=False):
     """Compile csrc/*.hip into libyy_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("yy_engine.hip", "yy_nn_epilogue.hip", "yy_tower.hip", "yy_tower_f32.hip",
                                             "yy_tower_h3r.hip", "yy_tower_g.hip", "yy_fc_heads.hip", "yy_selfplay.hip",
-                                            "yy_bitboard.h", "yy_common.h")] + [HEADER]
+                                            "yy_selfplay_move.hip", "yy_bitboard.h", "yy_common.h", "yy_tree.h",
+                                            "yy_draws.h")] + [HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -102,6 +110,12 @@ _SIGS = {
     "yy_selfplay_root_noise": [C.c_uint64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp],
     "yy_selfplay_sample_actions": [C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "yy_selfplay_draw_budgets": [C.c_uint64, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp],
+    "yy_selfplay_run_create": [_vp, C.POINTER(SelfPlayConfig), C.POINTER(_vp)],
+    "yy_selfplay_run_destroy": [_vp],
+    "yy_selfplay_run_arm": [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp],
+    "yy_mcts_step_selfplay": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "yy_selfplay_run_counters": [_vp, _vp, _vp],
+    "yy_selfplay_run_examples": [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
     "yy_version": [],
 }
 

@@ -23,7 +23,7 @@ from . import engine
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
 from .search import LockstepSearch
-from .self_play import _playout_cap, _tree_reuse, generate_self_play_data
+from .self_play import _free_running, _playout_cap, _tree_reuse, generate_self_play_data
 from .training import run_training_pipeline
 
 
@@ -322,7 +322,7 @@ class AlphaZero:
                  num_simulations=800, num_epochs=10, temperature_threshold=10, update_threshold=0.6, num_workers=1,
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
-                 full_search_probability=1.0, tree_reuse=False):
+                 full_search_probability=1.0, tree_reuse=False, free_running=False):
         """leaves_per_step K > 1 (not in the reference): leaf-parallel searches in the loop's self-play (SelfPlayManager
         leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step).
         fast_simulations / full_search_probability: playout-cap randomisation in the loop's self-play (SelfPlayEngine's); the
@@ -330,6 +330,8 @@ class AlphaZero:
         tree_reuse: the loop's self-play and its arena continue every search from the subtree under the move played
         (SelfPlayEngine / Arena tree_reuse); not with leaves_per_step > 1."""
         self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step)
+        # the loop's self-play lets its games move on the device (SelfPlayEngine free_running); the arena is unchanged
+        self.free_running = _free_running(free_running, leaves_per_step, tree_reuse=tree_reuse)
         self.leaves_per_step = max(1, int(leaves_per_step))
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
@@ -362,7 +364,8 @@ class AlphaZero:
                                        num_channels=self.num_channels, num_res_blocks=self.num_res_blocks,
                                        concurrent_games=self.concurrent_games, seed=len(self.history),
                                        leaves_per_step=self.leaves_per_step, **self.playout_cap,
-                                       **(dict(tree_reuse=True) if self.tree_reuse else {}))
+                                       **(dict(tree_reuse=True) if self.tree_reuse else {}),
+                                       **(dict(free_running=True) if self.free_running else {}))
 
     def train(self):
         # the reference passes num_iterations=1 and ignores --epochs/--batch-size/--lr (alphazero.py:120-127,

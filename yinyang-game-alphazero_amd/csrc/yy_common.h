@@ -9,6 +9,12 @@
 // Sets the calling thread's yy_last_error() text and returns `code` (defined in yy_engine.hip).
 extern "C" int yy_tower_set_err(int code, const char *msg);
 
+// The fused tree step (yy_mcts_step's launch) with the noise rows of the root expansions that are pending among the leaves
+// (defined in yy_engine.hip next to the kernel; the caller has checked the context's state).  Only root expansions mix noise.
+// Internal to libyy_hip.so: hidden visibility, not part of the C ABI of include/yy_engine.h.
+extern "C" __attribute__((visibility("hidden"))) int yy_mcts_step_noise(yy_mcts *ctx, const float *policy, const float *value, const double *noise, double eps,
+                                  float *planes, uint8_t *needs_eval, yy_stream_t stream);
+
 static inline int yy_hip_fail(const char *what, hipError_t e) {
     char msg[512];
     snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));

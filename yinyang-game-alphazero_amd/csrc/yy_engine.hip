@@ -30,8 +30,9 @@
 #include "../../include/yy_engine.h"
 #include "yy_bitboard.h"
 #include "yy_common.h"
+#include "yy_tree.h"
 
-#define YY_VERSION 103
+#define YY_VERSION 104
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -52,23 +53,6 @@ static int check_geo(int G, int R, int C) {
 }
 
 // ------------------------------------------------------------------------------------ helpers
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int rfl(int v) { return (int)__builtin_amdgcn_readfirstlane((uint32_t)v); }
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
-    return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v);
-}
-__device__ __forceinline__ float rflf(float v) { return __uint_as_float(rfl(__float_as_uint(v))); }
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-// number of set bits of m below this lane's position
-__device__ __forceinline__ int mbcnt(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Wave64 reductions on the VALU with DPP (row_shr 1/2/4/8 scan inside each 16-lane row, then row_bcast15 /
 // row_bcast31 across rows; lane 63 ends up with the total): ~6 dependent VALU ops instead of 6 LDS-crossbar
 // shuffles.  Used on the latency-critical PUCT descent.
@@ -108,77 +92,6 @@ __device__ __forceinline__ uint32_t wave_uadd(uint32_t v) {
 __device__ __forceinline__ uint32_t f32_key(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <int NW> __device__ __forceinline__ BB<NW> bb_uniform_load(const uint64_t *p) {
-    BB<NW> r;
-#pragma unroll
-    for (int i = 0; i < NW; i++) r.w[i] = rfl64(p[i]);
-    return r;
-}
-template <int NW> __device__ __forceinline__ void bb_store_lane0(uint64_t *p, BB<NW> b) {
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int i = 0; i < NW; i++) p[i] = b.w[i];
-    }
-}
-
-// wave-cooperative: int8 board (cell per lane) -> uniform bitboards via ballot
-template <int NW>
-__device__ __forceinline__ void board_to_bb(const int8_t *b, int A, BB<NW> &black, BB<NW> &white) {
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        int cell = j * 64 + lane_id();
-        int v = (cell < A) ? (int)b[cell] : 0;
-        black.w[j] = __ballot(v == 1);
-        white.w[j] = __ballot(v == -1);
-    }
-}
-template <int NW>
-__device__ __forceinline__ void bb_to_board(int8_t *b, int A, BB<NW> black, BB<NW> white) {
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        int cell = j * 64 + lane_id();
-        if (cell < A)
-            b[cell] = ((black.w[j] >> lane_id()) & 1) ? 1 : (((white.w[j] >> lane_id()) & 1) ? -1 : 0);
-    }
-}
-
-// row r of `occ` as the low C bits (C <= 16; may straddle a word boundary)
-template <int NW> __device__ __forceinline__ uint32_t bb_row_bits(BB<NW> occ, int r, int C) {
-    int s = r * C, w = s >> 6, o = s & 63;
-    uint64_t lo = 0, hi = 0;
-#pragma unroll
-    for (int i = 0; i < NW; i++) {
-        if (i == w) lo = occ.w[i];
-        if (i == w + 1) hi = occ.w[i];
-    }
-    uint64_t v = lo >> o;
-    if (o) v |= hi << (64 - o);
-    return (uint32_t)v & ((1u << C) - 1u);
-}
-
-// wave-cooperative board_to_input (neural_network.py:156-196): lane = cell, coalesced rows
-template <int NW>
-__device__ __forceinline__ void write_planes(float *out, const YYGeo &geo, BB<NW> black, BB<NW> white) {
-    const int A = geo.A, C = geo.C;
-    BB<NW> occ = black | white;
-    BB<NW> col0 = bb_load<NW>(geo.col0);
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        int cell = j * 64 + lane_id();
-        if (cell < A) {
-            int r = cell / C, c = cell - r * C;
-            bool bk = (black.w[j] >> lane_id()) & 1, wh = (white.w[j] >> lane_id()) & 1;
-            int rowk = __popc(bb_row_bits(occ, r, C));
-            int colk = bb_popc(occ & bb_shl(col0, c));
-            out[cell] = (!bk && !wh) ? 1.0f : 0.0f;
-            out[A + cell] = bk ? 1.0f : 0.0f;
-            out[2 * A + cell] = wh ? 1.0f : 0.0f;
-            out[3 * A + cell] = geo.rowfill[rowk];
-            out[4 * A + cell] = geo.colfill[colk];
-        }
-    }
 }
 
 // ------------------------------------------------------------------------- stateless kernels
@@ -244,12 +157,7 @@ __global__ void __launch_bounds__(RULES_BLOCK) k_step(int8_t *boards, int8_t *pl
         if (v == -1) white.w[a >> 6] |= 1ull << (a & 63);
     }
     const int p = players[g], a = actions[g];
-    bool ok = false;
-    if (a >= 0 && a < A) {  // yin_yang_logic.py:34 bounds check
-        bool pre = bb_pre2x2(black, white, gb);
-        BB<NW> m = (p == 1) ? bb_legal(black, white, pre, geo, gb) : bb_legal(white, black, pre, geo, gb);
-        ok = bb_test(m, a);
-    }
+    const bool ok = bb_play<NW>(geo, gb, black, white, p, a);
     if (ok) b[a] = (p == 1) ? 1 : -1;  // yin_yang_game.py:55-56
     players[g] = (int8_t)-p;           // yin_yang_game.py:58, regardless
     if (placed) placed[g] = ok;
@@ -267,13 +175,7 @@ __global__ void __launch_bounds__(RULES_BLOCK) k_game_ended(const int8_t *boards
     GeoBB<NW> gb = geo_bb<NW>(geo);
     BB<NW> black, white;
     lds_board_to_bb<NW>(lds + threadIdx.x * A, A, black, white);
-    bool pre = bb_pre2x2(black, white, gb);
-    BB<NW> mb = bb_legal(black, white, pre, geo, gb), mw = bb_legal(white, black, pre, geo, gb);
-    int res = bb_result_black(black, white, mb, mw);
-    double v = 0.0;
-    if (res == 2) v = 0.0001;                                   // yin_yang_game.py:107
-    else if (res != 0) v = (players[g] == 1) ? (double)res : (double)-res;
-    out[g] = v;
+    out[g] = bb_game_ended<NW>(geo, gb, black, white, players[g]);
     if (counts) {
         counts[2 * g] = bb_popc(black);
         counts[2 * g + 1] = bb_popc(white);
@@ -440,10 +342,6 @@ extern "C" int yy_rules_mask_terminal_bb(const uint64_t *black, const uint64_t *
 }
 
 // =============================================================================== MCTS context
-enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6, K_ROOTKEPT = 7 };
-#define CHILD_NONE 0x00FFFFFFu
-#define NF_TERMINAL 1u
-#define NF_HASVALUE 2u   // childless node whose evaluator value (record .w) may be reused (YY_FLAG_REUSE_PASS_VALUE)
 #define TT_PROBES 8
 
 // slot hash of a position: murmur3's 64-bit finalizer after every word -- positions of one search differ in a few bits, and a
@@ -461,91 +359,6 @@ template <int NW> __device__ __forceinline__ uint64_t bb_hash(const uint64_t *bl
     }
     return h;
 }
-
-// The pending leaf of one descent: what selection leaves for the expansion + backup that follows the evaluator.  K = 1 keeps
-// the one record of a game in its GameState; leaf-parallel steps (leaves_per_step K > 1) keep descent j of game g in
-// leaves[g*K + j].  board / mask / player / terminal / tv are set only for a leaf that is evaluated (leaf_store).
-struct LeafRec {
-    int32_t path_len, node;  // edges on the path == depth of the leaf; the leaf's node record when it already has one, else -1
-    int32_t dup;             // K > 1: >= 0: an earlier descent of this step that ended on the same leaf (its row is shared), else -1
-    float tv;                // terminal value of a freshly evaluated leaf (f32 of 1 / -1 / 1e-4)
-    uint8_t kind, terminal;
-    int8_t player;
-    uint8_t pad[5];
-    uint64_t board[2 * YY_MAX_NW];
-    uint64_t mask[YY_MAX_NW];
-};
-
-struct GameState {
-    int32_t n_nodes, n_edges;
-    int32_t root_N;
-    float root_W;
-    double root_W_py;       // root.value_sum while it is still a python float (terminal root only)
-    int8_t root_player;
-    uint8_t active, err, root_w_is_py;
-    uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
-    uint8_t kept;           // yy_mcts_advance left this game's tree re-rooted at node 0; consumed by the next yy_mcts_begin
-    uint8_t root_kept;      // the root of the current search is a kept node: its own first visit expanded it, so its children's
-                            // visits sum to root_N - 1 (a fresh root's: root_N)
-    int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot)
-    int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
-    uint32_t ec_epoch;      // entries of other epochs are replaceable (see k_begin)
-    int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
-    int32_t budget;         // K = 1: simulations of this game's current search (k_begin); at root_N == budget selection stops
-    LeafRec leaf;           // K = 1: the pending leaf
-    uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
-};
-
-// A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
-// game g's evaluation cache another (cache_of: a slice of the context's ec arrays).
-struct PosTable {
-    uint32_t *meta;         // [slots]  0 = never used; cache: epoch << 8 | stones, book: 1
-    uint64_t *key;          // [slots, 2*NW]  the position
-    float *val;             // [slots]  the evaluator's value
-    float *pol;             // [slots, A]  the evaluator's policy row
-    uint32_t mask;          // slots - 1 (slots is a power of two)
-};
-
-// The device's view of a context, the by-value argument of every context kernel: filled once by yy_mcts_create (the book
-// part by yy_mcts_set_book) and kept in the context, so that a launch passes what the host itself allocates through.
-struct MctsDev {
-    YYGeo geo;
-    int32_t G;
-    uint32_t aliased, reuse;
-    float cpuct;
-    int64_t node_cap, edge_cap, path_cap;
-    uint4 *edges, *nodes;
-    uint64_t *nboard, *gboard;
-    int32_t *path;
-    // evaluation cache (YY_FLAG_REUSE_TRANSPOSITIONS / YY_FLAG_KEEP_EVALUATIONS): the arrays of all G games, mask + 1 slots
-    // per game; meta == nullptr: off
-    PosTable ec;
-    uint32_t ec_keep;
-    // shared book of pre-evaluated positions (yy_mcts_set_book; arrays owned by the caller, read-only here); meta == nullptr: none
-    PosTable bk;
-    int32_t bk_stones;
-    GameState *state;
-    float *sqrt_tab;
-    int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
-};
-
-struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
-    int32_t K;               // leaves per step (1: one descent per game per step)
-    LeafRec *leaves;         // [G*K]
-    int32_t *mst;            // [G][2] = {simulations of the current search, descents of the pending step}
-};
-
-struct yy_mcts {
-    yy_mcts_config cfg;
-    MctsDev dev;            // every pointer, capacity and the geometry live here only
-    MultiDev multi;
-    int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
-    const int32_t *budgets; // device int32 [G] of per-game simulation budgets for the next yy_mcts_begin; nullptr: target_sims for all
-    uint64_t *scratch;      // [8] counters + overflow count
-    int32_t *remap;         // [G][node_cap] old node index -> new one (k_advance); allocated by the first yy_mcts_advance
-    uint64_t bytes;
-    int pending;            // 1 = a select is pending an expand_backup
-};
 
 // ---- the position table: each of probe sequence, key compare and stone count exists once, for the cache, the book's
 // lookup and the book's build (k_book_insert)
@@ -571,7 +384,6 @@ template <int NW> __device__ __forceinline__ bool tt_key_is(const PosTable &t, u
     for (int i = 0; i < NW; i++) same = same && ob.w[i] == black.w[i] && ow.w[i] == white.w[i];
     return same;
 }
-template <int NW> __device__ __forceinline__ int pos_stones(BB<NW> black, BB<NW> white) { return bb_popc(black) + bb_popc(white); }
 
 template <int NW> __device__ __forceinline__ PosTable cache_of(const MctsDev &d, const int g) {
     const size_t o = (size_t)g * ((size_t)d.ec.mask + 1);
@@ -653,25 +465,6 @@ __device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *s
     }
 }
 
-__device__ __forceinline__ uint32_t node_pack(int k, uint32_t flags, int player) {
-    return (uint32_t)k | (flags << 16) | ((uint32_t)(player & 0xFF) << 24);
-}
-__device__ __forceinline__ int node_k(uint32_t y) { return (int)(y & 0xFFFFu); }
-__device__ __forceinline__ uint32_t node_flags(uint32_t y) { return (y >> 16) & 0xFFu; }
-__device__ __forceinline__ int node_player(uint32_t y) { return (int)(int8_t)(y >> 24); }
-
-// getGameEnded(board, player) as float32 + the mask of `player` (yin_yang_game.py:80-110)
-template <int NW>
-__device__ __forceinline__ void leaf_rules(const YYGeo &geo, const GeoBB<NW> &gb, BB<NW> black, BB<NW> white,
-                                           int player, BB<NW> &mask, bool &terminal, float &tv) {
-    bool pre = bb_pre2x2(black, white, gb);
-    BB<NW> mb = bb_legal(black, white, pre, geo, gb), mw = bb_legal(white, black, pre, geo, gb);
-    int res = bb_result_black(black, white, mb, mw);
-    mask = (player == 1) ? mb : mw;
-    terminal = (res != 0);
-    tv = (res == 2) ? 0.0001f : ((player == 1) ? (float)res : (float)-res);
-}
-
 // ---- building blocks shared by the K = 1 and the K > 1 tree kernel: each float32 / float64 sequence of the parity contract
 // with the reference exists once, here.
 #define BEST_NONE 0x7FFFFFFF
@@ -724,23 +517,6 @@ __device__ __forceinline__ int leaf_position(const MctsDev &d, const GameState *
         else white = white | bb_bit<NW>(action);
     }
     return -pplayer;
-}
-
-// the position half of a leaf record: what the expansion needs of a leaf that is evaluated
-template <int NW>
-__device__ __forceinline__ void leaf_store(LeafRec *rec, BB<NW> black, BB<NW> white, BB<NW> mask, int player, bool term,
-                                           float tv) {
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int i = 0; i < NW; i++) {
-            rec->board[i] = black.w[i];
-            rec->board[NW + i] = white.w[i];
-            rec->mask[i] = mask.w[i];
-        }
-        rec->player = (int8_t)player;
-        rec->terminal = term;
-        rec->tv = tv;
-    }
 }
 
 // Node.expand (mcts.py:50-91) of the evaluated leaf `rec`: v is its value, prow its policy row (the evaluator's row, a cache
@@ -860,7 +636,7 @@ __device__ __forceinline__ void backup_path(uint4 *edges, const int32_t *path, c
     }
 }
 
-// ---- root prologue: mcts.py:288-295
+// ---- root prologue: mcts.py:288-295 (root_setup, yy_tree.h)
 // The simulation budget of game g: K > 1 keeps it in mst[2g], K = 1 in GameState.budget.  `budgets` (int32 [G], clamped to
 // 0 .. max_sims here) when the caller set one (yy_mcts_set_sim_budgets), else `target` for every game.  The pointer is an
 // argument of this kernel only: the step kernels read the stored budgets, so a captured step serves every budget array.
@@ -901,57 +677,9 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
             rec->path_len = 0;
             rec->dup = -1;
         }
-    } else if (lane_id() == 0) {
-        st->kept = 0;
-        st->root_kept = 0;
-        st->n_nodes = 1;  // node 0 = root
-        st->n_edges = 0;
-        st->root_N = 0;
-        st->root_W = 0.0f;
-        st->root_W_py = 0.0;
-        st->root_w_is_py = 1;
-        st->root_player = players[g];
-        st->active = act;
-        st->err = 0;
-        st->budget = budgets ? min(max(budgets[g], 0), max_sims) : target;
-        rec->kind = act ? K_ROOTINIT : K_NONE;
-        rec->node = 0;
-        rec->path_len = 0;
-        rec->dup = -1;
-        d.nodes[(size_t)g * d.node_cap] = make_uint4(0u, node_pack(0, 0, players[g]), 0u, 0u);
     }
-    if (d.ec.meta && lane_id() == 0) {
-        // Entries of an older epoch are the first to be replaced.  Without YY_FLAG_KEEP_EVALUATIONS every search is its own
-        // epoch and only entries of the current one are looked at (reuse inside one search); with it the epoch changes when
-        // a game starts over from the empty board, so a game's searches share their evaluations.
-        const int stones = pos_stones<NW>(black, white);
-        uint32_t ep = st->ec_epoch;
-        if (!d.ec_keep || stones == 0 || ep == 0u) ep = (ep + 1u) & 0xFFFFFFu;
-        if (ep == 0u) ep = 1u;
-        st->ec_epoch = ep;
-        st->root_stones = stones;
-    }
-    uint64_t *gbd = d.gboard + (size_t)g * 2 * NW;
-    bb_store_lane0<NW>(gbd, black);
-    bb_store_lane0<NW>(gbd + NW, white);
-    if (!d.aliased && !keep) {
-        uint64_t *nb = d.nboard + (size_t)g * d.node_cap * 2 * NW;
-        bb_store_lane0<NW>(nb, black);
-        bb_store_lane0<NW>(nb + NW, white);
-    }
-    if (act) {
-        // root.expand's rules (mcts.py:63-71) for the pending K_ROOTINIT expansion
-        const GeoBB<NW> gb = geo_bb<NW>(d.geo);
-        const int rp = rfl((int)players[g]);
-        BB<NW> mask;
-        bool term;
-        float tv;
-        if (!keep) {
-            leaf_rules<NW>(d.geo, gb, black, white, rp, mask, term, tv);
-            leaf_store<NW>(rec, black, white, mask, rp, term, tv);
-        }
-        write_planes<NW>(planes + (size_t)g * K * 5 * d.geo.A, d.geo, black, white);
-    }
+    root_setup<NW>(d, st, rec, g, black, white, rfl((int)players[g]), act, keep,
+                   budgets ? min(max(budgets[g], 0), max_sims) : target, planes + (size_t)g * K * 5 * d.geo.A);
     if (K > 1 && lane_id() == 0) {
         m.mst[2 * g] = budgets ? min(max(budgets[g], 0), max_sims) : target;
         m.mst[2 * g + 1] = act ? 1 : 0;
@@ -1131,7 +859,7 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
         const LeafEval ev = leaf_eval<NW>(d, g, src, policy, root ? nullptr : value);
         v = ev.v;
         const bool hold = d.reuse && !root;   // a pass node keeps its value; a pass root that of its first simulation
-        if (!expand_leaf<NW>(d, st, g, &st->leaf, path, ev.prow, v, hold, d.aliased != 0u, noise, eps)) {
+        if (!expand_leaf<NW>(d, st, g, &st->leaf, path, ev.prow, v, hold, d.aliased != 0u, root ? noise : nullptr, eps)) {
             // NaN from the evaluator or a full arena: the game stops searching, the error is sticky
             if (lane == 0) { st->err = st->err_ever = 1; st->leaf.kind = K_NONE; }
             return;
@@ -1485,43 +1213,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_root_counts(MctsDev d,
 
 // Node.get_children_distribution (mcts.py:183-215) for T == 1 and T == 0
 template <int NW> __global__ void __launch_bounds__(64) k_root_policy(MctsDev d, int tzero, double *pi) {
-    const int g = blockIdx.x, A = d.geo.A;
-    const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
-    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
-    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
-    const bool act = rfl((int)d.state[g].active) != 0;
-    int sum = 0, mx = 0;
-    if (act)
-        for (int j = lane_id(); j < k; j += 64) {
-            int n = (int)edges[first + j].y;
-            sum += n;
-            mx = max(mx, n);
-        }
-    sum = wave_sum(sum);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
-    double fill;
-    int nbest = 0;
-    if (tzero) {
-        // counts == max over ALL A actions (zeros included when max == 0), mcts.py:200-203
-        if (mx == 0) nbest = A;
-        else {
-            for (int j = lane_id(); j < k; j += 64) nbest += ((int)edges[first + j].y == mx);
-            nbest = wave_sum(nbest);
-        }
-        fill = (mx == 0) ? 1.0 / (double)A : 0.0;
-    } else {
-        fill = (sum > 0) ? 0.0 : 1.0 / (double)A;                                  // mcts.py:209-213
-    }
-    for (int a = lane_id(); a < A; a += 64) pi[(size_t)g * A + a] = act ? fill : 0.0;
-    __syncthreads();
-    if (!act) return;
-    if (tzero ? (mx > 0) : (sum > 0))
-        for (int j = lane_id(); j < k; j += 64) {
-            const uint4 e = edges[first + j];
-            const int a = (int)(e.w >> 24), n = (int)e.y;
-            pi[(size_t)g * A + a] = tzero ? ((n == mx) ? 1.0 / (double)nbest : 0.0) : (double)n / (double)sum;
-        }
+    root_distribution<NW>(d, blockIdx.x, tzero, pi + (size_t)blockIdx.x * d.geo.A);
 }
 
 __global__ void k_root_stats(MctsDev d, int32_t *visits, double *wsum) {
@@ -1751,6 +1443,12 @@ extern "C" int yy_mcts_step(yy_mcts *c, const float *policy, const float *value,
     if (!c || !policy || !value || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
     if (c->pending != 1) return set_err(YY_E_STATE, "yy_mcts_step without a pending select%s%s");
     return launch_mcts(c, 1, 1, policy, value, nullptr, 0.0, planes, needs_eval, s);
+}
+
+// yy_mcts_step with a noise array for the root expansions pending among the leaves (yy_common.h; yy_mcts_step_selfplay)
+extern "C" __attribute__((visibility("hidden"))) int yy_mcts_step_noise(yy_mcts *c, const float *policy, const float *value, const double *noise, double eps,
+                                  float *planes, uint8_t *needs_eval, yy_stream_t s) {
+    return launch_mcts(c, 1, 1, policy, value, noise, eps, planes, needs_eval, s);
 }
 
 extern "C" int yy_mcts_root_counts(yy_mcts *c, int32_t *counts, float *cw, float *cp, yy_stream_t s) {

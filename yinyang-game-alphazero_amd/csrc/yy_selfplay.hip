@@ -24,75 +24,9 @@
 #include "../../include/yy_engine.h"
 
 #include "yy_common.h"
+#include "yy_draws.h"   // the streams and the draws themselves: shared with the in-step move kernel (yy_selfplay_move.hip)
 
 namespace sp {
-
-struct U4 {
-    uint32_t x, y, z, w;
-};
-// Philox4x32-10 (Salmon et al., SC'11): counter c, key k
-__device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-// 53-bit uniform in [0, 1) from two words
-__device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {
-    return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1.0p-53;
-}
-// key = seed; counter = (game index lo, game index hi, ply << 8 | purpose, element)
-__device__ __forceinline__ U4 draw(uint64_t seed, int64_t game, int ply, int purpose, uint32_t element) {
-    const U4 c = {(uint32_t)game, (uint32_t)((uint64_t)game >> 32), ((uint32_t)ply << 8) | (uint32_t)purpose, element};
-    return philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// Gamma(alpha, 1): Marsaglia-Tsang on alpha' = alpha (+1 when alpha < 1), attempt t uses element = cell * 64 + t.
-// Returns g ~ Gamma(alpha'); the cell's value is g * ub^(1/alpha) when alpha < 1 (the boost), else g.
-__device__ double gamma_draw(uint64_t seed, int64_t game, int ply, int cell, double alpha, double &ub) {
-    const bool boost = alpha < 1.0;
-    const double a = boost ? alpha + 1.0 : alpha;
-    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-    double g = d;     // value if 64 attempts were all rejected (probability < 1e-80)
-    ub = 0.5;
-    for (int t = 0; t < 64; t++) {
-        const U4 r = draw(seed, game, ply, 0, (uint32_t)(cell * 64 + t));
-        const U4 q = draw(seed, game, ply, 2, (uint32_t)(cell * 64 + t));
-        const double u1 = 1.0 - u01(r.x, r.y), u2 = u01(r.z, r.w);      // u1 in (0, 1]
-        const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-        const double v1 = 1.0 + c * z;
-        if (v1 <= 0.0) continue;
-        const double v = v1 * v1 * v1;
-        const double u3 = 1.0 - u01(q.x, q.y);
-        if (log(u3) < 0.5 * z * z + d - d * v + d * log(v)) {
-            g = d * v;
-            ub = 1.0 - u01(q.z, q.w);
-            break;
-        }
-    }
-    return g;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // noise[g, a] = Dirichlet(alpha) over the legal cells of the games with draw[g] != 0 (zeros elsewhere: the tree kernel
 // treats an all-zero row as "no noise", mcts.py:298)
@@ -101,46 +35,20 @@ __global__ void __launch_bounds__(64) k_root_noise(uint64_t seed, const int64_t 
                                                    const uint8_t *__restrict__ mask, int A, double alpha,
                                                    double *__restrict__ noise) {
     const int g = blockIdx.x, lane = threadIdx.x;
-    const bool on = drawf[g] != 0, boost = alpha < 1.0;
-    double x[3] = {0.0, 0.0, 0.0}, gm[3] = {0.0, 0.0, 0.0}, ub[3] = {1.0, 1.0, 1.0}, part = 0.0;
+    const bool on = drawf[g] != 0;
     bool legal[3] = {false, false, false};
+    int64_t gid = 0;
+    int p = 0;
     if (on) {
-        const int64_t gid = game_id[g];
-        const int p = ply[g];
+        gid = game_id[g];
+        p = ply[g];
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             const int a = j * 64 + lane;
-            if (a < A && mask[(size_t)g * A + a]) {
-                legal[j] = true;
-                gm[j] = gamma_draw(seed, gid, p, a, alpha, ub[j]);
-                x[j] = boost ? gm[j] * pow(ub[j], 1.0 / alpha) : gm[j];
-                part += x[j];
-            }
+            legal[j] = a < A && mask[(size_t)g * A + a];
         }
     }
-    // one fixed summation order: lanes' partial sums (cells a, a+64, a+128) combined by the xor butterfly
-    double tot = wave_sum_f64(part);
-    if (on && tot < 0x1.0p-900) {       // wave-uniform: redo the row in log space, relative to the row's largest cell
-        double lx[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            lx[j] = !legal[j] ? -INFINITY : boost ? log(gm[j]) + log(ub[j]) / alpha : log(gm[j]);
-        const double m = wave_max_f64(fmax(fmax(lx[0], lx[1]), lx[2]));
-        part = 0.0;
-        if (m > -INFINITY) {            // at least one legal cell
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                x[j] = legal[j] ? exp(lx[j] - m) : 0.0;
-                part += x[j];
-            }
-        }
-        tot = wave_sum_f64(part);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int a = j * 64 + lane;
-        if (a < A) noise[(size_t)g * A + a] = (on && tot > 0.0) ? x[j] / tot : 0.0;
-    }
+    dirichlet_row(seed, gid, p, on, legal, A, alpha, noise + (size_t)g * A);
 }
 
 // self_play.py:143-160; action = -1 for games that are not searching
@@ -154,44 +62,9 @@ __global__ void __launch_bounds__(64) k_sample_actions(uint64_t seed, const int6
         action[g] = -1;
         return;
     }
-    const double *p = pi + (size_t)g * A;
     const uint8_t *m = mask + (size_t)g * A;
-    const U4 r = draw(seed, game_id[g], ply[g], 1, 0u);
-    const double u = u01(r.x, r.y);
-    int pick = -1;
-    if (ply[g] < temperature_threshold) {            // temperature 1: p = pi * valid / sum (:150-160)
-        double tot = 0.0;
-        int legal = 0;
-        for (int a = 0; a < A; a++) {
-            tot += m[a] ? p[a] : 0.0;
-            legal += m[a] != 0;
-        }
-        if (tot > 0.0) {
-            const double target = u * tot;
-            double c = 0.0;
-            for (int a = 0; a < A; a++) {
-                const double w = m[a] ? p[a] : 0.0;
-                c += w;
-                if (w > 0.0) {
-                    pick = a;                           // remembers the last action with mass (rounding guard)
-                    if (c > target) break;
-                }
-            }
-        } else if (legal > 0) {                         // uniform over the legal moves (:156-158)
-            int k = min((int)(u * (double)legal), legal - 1);
-            for (int a = 0; a < A; a++)
-                if (m[a] && k-- == 0) { pick = a; break; }
-        }
-    } else {                                            // temperature 0: random arg-max (:143-146)
-        double mx = p[0];
-        for (int a = 1; a < A; a++) mx = fmax(mx, p[a]);
-        int n = 0;
-        for (int a = 0; a < A; a++) n += (p[a] == mx);
-        int k = min((int)(u * (double)n), n - 1);
-        for (int a = 0; a < A; a++)
-            if (p[a] == mx && k-- == 0) { pick = a; break; }
-    }
-    action[g] = pick;
+    action[g] = pick_action(seed, game_id[g], ply[g], temperature_threshold, pi + (size_t)g * A,
+                            [m](int a) { return m[a] != 0; }, A);
 }
 
 // playout-cap randomisation: the simulation budget of every searching game's next search, and whether it is a full one
@@ -202,10 +75,7 @@ __global__ void __launch_bounds__(256) k_draw_budgets(uint64_t seed, const int64
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     bool full = false;
-    if (searching[g]) {
-        const U4 r = draw(seed, game_id[g], ply[g], 3, 0u);
-        full = u01(r.x, r.y) < p_full;
-    }
+    if (searching[g]) full = draw_full_search(seed, game_id[g], ply[g], p_full);
     budgets[g] = !searching[g] ? 0 : full ? full_sims : fast_sims;
     is_full[g] = full;
 }

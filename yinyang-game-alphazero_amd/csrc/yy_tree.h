@@ -1,0 +1,362 @@
+// yy_tree.h -- what the kernels that run ONE GAME PER WAVEFRONT share: the wave helpers, the records of the MCTS context
+// (yy_engine.hip owns the context; yy_selfplay_move.hip sets roots up and reads them inside the step), and the one copy of
+// every rule and formula that both the stateless / read-out kernels and the in-step move kernel apply: the root prologue
+// (k_begin), the root distribution (k_root_policy), getNextState (k_step) and getGameEnded (k_game_ended).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/yy_engine.h"
+#include "yy_bitboard.h"
+
+// ------------------------------------------------------------------------------------ helpers
+__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int rfl(int v) { return (int)__builtin_amdgcn_readfirstlane((uint32_t)v); }
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
+    return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v);
+}
+__device__ __forceinline__ float rflf(float v) { return __uint_as_float(rfl(__float_as_uint(v))); }
+__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+// number of set bits of m below this lane's position
+__device__ __forceinline__ int mbcnt(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int NW> __device__ __forceinline__ BB<NW> bb_uniform_load(const uint64_t *p) {
+    BB<NW> r;
+#pragma unroll
+    for (int i = 0; i < NW; i++) r.w[i] = rfl64(p[i]);
+    return r;
+}
+template <int NW> __device__ __forceinline__ void bb_store_lane0(uint64_t *p, BB<NW> b) {
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int i = 0; i < NW; i++) p[i] = b.w[i];
+    }
+}
+
+// wave-cooperative: int8 board (cell per lane) -> uniform bitboards via ballot
+template <int NW>
+__device__ __forceinline__ void board_to_bb(const int8_t *b, int A, BB<NW> &black, BB<NW> &white) {
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        int cell = j * 64 + lane_id();
+        int v = (cell < A) ? (int)b[cell] : 0;
+        black.w[j] = __ballot(v == 1);
+        white.w[j] = __ballot(v == -1);
+    }
+}
+template <int NW>
+__device__ __forceinline__ void bb_to_board(int8_t *b, int A, BB<NW> black, BB<NW> white) {
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        int cell = j * 64 + lane_id();
+        if (cell < A)
+            b[cell] = ((black.w[j] >> lane_id()) & 1) ? 1 : (((white.w[j] >> lane_id()) & 1) ? -1 : 0);
+    }
+}
+
+// row r of `occ` as the low C bits (C <= 16; may straddle a word boundary)
+template <int NW> __device__ __forceinline__ uint32_t bb_row_bits(BB<NW> occ, int r, int C) {
+    int s = r * C, w = s >> 6, o = s & 63;
+    uint64_t lo = 0, hi = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        if (i == w) lo = occ.w[i];
+        if (i == w + 1) hi = occ.w[i];
+    }
+    uint64_t v = lo >> o;
+    if (o) v |= hi << (64 - o);
+    return (uint32_t)v & ((1u << C) - 1u);
+}
+
+// wave-cooperative board_to_input (neural_network.py:156-196): lane = cell, coalesced rows
+template <int NW>
+__device__ __forceinline__ void write_planes(float *out, const YYGeo &geo, BB<NW> black, BB<NW> white) {
+    const int A = geo.A, C = geo.C;
+    BB<NW> occ = black | white;
+    BB<NW> col0 = bb_load<NW>(geo.col0);
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        int cell = j * 64 + lane_id();
+        if (cell < A) {
+            int r = cell / C, c = cell - r * C;
+            bool bk = (black.w[j] >> lane_id()) & 1, wh = (white.w[j] >> lane_id()) & 1;
+            int rowk = __popc(bb_row_bits(occ, r, C));
+            int colk = bb_popc(occ & bb_shl(col0, c));
+            out[cell] = (!bk && !wh) ? 1.0f : 0.0f;
+            out[A + cell] = bk ? 1.0f : 0.0f;
+            out[2 * A + cell] = wh ? 1.0f : 0.0f;
+            out[3 * A + cell] = geo.rowfill[rowk];
+            out[4 * A + cell] = geo.colfill[colk];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------ rules, one copy
+// getNextState (yin_yang_game.py:39-58, yin_yang_logic.py:24-34) of `player` playing `action`: the stone is placed iff the
+// action is on the board and legal; the caller flips the side to move regardless.  Returns whether it was placed.
+template <int NW>
+__device__ __forceinline__ bool bb_play(const YYGeo &geo, const GeoBB<NW> &gb, BB<NW> &black, BB<NW> &white, const int player,
+                                        const int action) {
+    bool ok = false;
+    if (action >= 0 && action < geo.A) {  // yin_yang_logic.py:34 bounds check
+        bool pre = bb_pre2x2(black, white, gb);
+        BB<NW> m = (player == 1) ? bb_legal(black, white, pre, geo, gb) : bb_legal(white, black, pre, geo, gb);
+        ok = bb_test(m, action);
+    }
+    if (ok) {                             // yin_yang_game.py:55-56
+        if (player == 1) black = black | bb_bit<NW>(action);
+        else white = white | bb_bit<NW>(action);
+    }
+    return ok;
+}
+
+// getGameEnded(board, player) (yin_yang_game.py:80-110) as the reference's float64: 0 ongoing, 1e-4 draw, +-1 for `player`
+template <int NW>
+__device__ __forceinline__ double bb_game_ended(const YYGeo &geo, const GeoBB<NW> &gb, BB<NW> black, BB<NW> white,
+                                                const int player) {
+    bool pre = bb_pre2x2(black, white, gb);
+    BB<NW> mb = bb_legal(black, white, pre, geo, gb), mw = bb_legal(white, black, pre, geo, gb);
+    int res = bb_result_black(black, white, mb, mw);
+    double v = 0.0;
+    if (res == 2) v = 0.0001;                                   // yin_yang_game.py:107
+    else if (res != 0) v = (player == 1) ? (double)res : (double)-res;
+    return v;
+}
+
+// =============================================================================== MCTS context records
+enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6, K_ROOTKEPT = 7 };
+#define CHILD_NONE 0x00FFFFFFu
+#define NF_TERMINAL 1u
+#define NF_HASVALUE 2u   // childless node whose evaluator value (record .w) may be reused (YY_FLAG_REUSE_PASS_VALUE)
+
+// The pending leaf of one descent: what selection leaves for the expansion + backup that follows the evaluator.  K = 1 keeps
+// the one record of a game in its GameState; leaf-parallel steps (leaves_per_step K > 1) keep descent j of game g in
+// leaves[g*K + j].  board / mask / player / terminal / tv are set only for a leaf that is evaluated (leaf_store).
+struct LeafRec {
+    int32_t path_len, node;  // edges on the path == depth of the leaf; the leaf's node record when it already has one, else -1
+    int32_t dup;             // K > 1: >= 0: an earlier descent of this step that ended on the same leaf (its row is shared), else -1
+    float tv;                // terminal value of a freshly evaluated leaf (f32 of 1 / -1 / 1e-4)
+    uint8_t kind, terminal;
+    int8_t player;
+    uint8_t pad[5];
+    uint64_t board[2 * YY_MAX_NW];
+    uint64_t mask[YY_MAX_NW];
+};
+
+struct GameState {
+    int32_t n_nodes, n_edges;
+    int32_t root_N;
+    float root_W;
+    double root_W_py;       // root.value_sum while it is still a python float (terminal root only)
+    int8_t root_player;
+    uint8_t active, err, root_w_is_py;
+    uint8_t err_ever;       // sticky: set with err, survives yy_mcts_begin, cleared only by yy_mcts_status
+    uint8_t kept;           // yy_mcts_advance left this game's tree re-rooted at node 0; consumed by the next yy_mcts_begin
+    uint8_t root_kept;      // the root of the current search is a kept node: its own first visit expanded it, so its children's
+                            // visits sum to root_N - 1 (a fresh root's: root_N)
+    int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot)
+    int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
+    uint32_t ec_epoch;      // entries of other epochs are replaceable (see root_setup)
+    int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
+    int32_t budget;         // K = 1: simulations of this game's current search (root_setup); at root_N == budget selection stops
+    LeafRec leaf;           // K = 1: the pending leaf
+    uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
+};
+
+// A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
+// game g's evaluation cache another (cache_of: a slice of the context's ec arrays).
+struct PosTable {
+    uint32_t *meta;         // [slots]  0 = never used; cache: epoch << 8 | stones, book: 1
+    uint64_t *key;          // [slots, 2*NW]  the position
+    float *val;             // [slots]  the evaluator's value
+    float *pol;             // [slots, A]  the evaluator's policy row
+    uint32_t mask;          // slots - 1 (slots is a power of two)
+};
+
+// The device's view of a context, the by-value argument of every context kernel: filled once by yy_mcts_create (the book
+// part by yy_mcts_set_book) and kept in the context, so that a launch passes what the host itself allocates through.
+struct MctsDev {
+    YYGeo geo;
+    int32_t G;
+    uint32_t aliased, reuse;
+    float cpuct;
+    int64_t node_cap, edge_cap, path_cap;
+    uint4 *edges, *nodes;
+    uint64_t *nboard, *gboard;
+    int32_t *path;
+    // evaluation cache (YY_FLAG_REUSE_TRANSPOSITIONS / YY_FLAG_KEEP_EVALUATIONS): the arrays of all G games, mask + 1 slots
+    // per game; meta == nullptr: off
+    PosTable ec;
+    uint32_t ec_keep;
+    // shared book of pre-evaluated positions (yy_mcts_set_book; arrays owned by the caller, read-only here); meta == nullptr: none
+    PosTable bk;
+    int32_t bk_stones;
+    GameState *state;
+    float *sqrt_tab;
+    int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
+};
+
+struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
+    int32_t K;               // leaves per step (1: one descent per game per step)
+    LeafRec *leaves;         // [G*K]
+    int32_t *mst;            // [G][2] = {simulations of the current search, descents of the pending step}
+};
+
+struct yy_mcts {
+    yy_mcts_config cfg;
+    MctsDev dev;            // every pointer, capacity and the geometry live here only
+    MultiDev multi;
+    int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
+    const int32_t *budgets; // device int32 [G] of per-game simulation budgets for the next yy_mcts_begin; nullptr: target_sims for all
+    uint64_t *scratch;      // [8] counters + overflow count
+    int32_t *remap;         // [G][node_cap] old node index -> new one (k_advance); allocated by the first yy_mcts_advance
+    uint64_t bytes;
+    int pending;            // 1 = a select is pending an expand_backup
+};
+
+template <int NW> __device__ __forceinline__ int pos_stones(BB<NW> black, BB<NW> white) { return bb_popc(black) + bb_popc(white); }
+
+__device__ __forceinline__ uint32_t node_pack(int k, uint32_t flags, int player) {
+    return (uint32_t)k | (flags << 16) | ((uint32_t)(player & 0xFF) << 24);
+}
+__device__ __forceinline__ int node_k(uint32_t y) { return (int)(y & 0xFFFFu); }
+__device__ __forceinline__ uint32_t node_flags(uint32_t y) { return (y >> 16) & 0xFFu; }
+__device__ __forceinline__ int node_player(uint32_t y) { return (int)(int8_t)(y >> 24); }
+
+// getGameEnded(board, player) as float32 + the mask of `player` (yin_yang_game.py:80-110)
+template <int NW>
+__device__ __forceinline__ void leaf_rules(const YYGeo &geo, const GeoBB<NW> &gb, BB<NW> black, BB<NW> white,
+                                           int player, BB<NW> &mask, bool &terminal, float &tv) {
+    bool pre = bb_pre2x2(black, white, gb);
+    BB<NW> mb = bb_legal(black, white, pre, geo, gb), mw = bb_legal(white, black, pre, geo, gb);
+    int res = bb_result_black(black, white, mb, mw);
+    mask = (player == 1) ? mb : mw;
+    terminal = (res != 0);
+    tv = (res == 2) ? 0.0001f : ((player == 1) ? (float)res : (float)-res);
+}
+
+// the position half of a leaf record: what the expansion needs of a leaf that is evaluated
+template <int NW>
+__device__ __forceinline__ void leaf_store(LeafRec *rec, BB<NW> black, BB<NW> white, BB<NW> mask, int player, bool term,
+                                           float tv) {
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            rec->board[i] = black.w[i];
+            rec->board[NW + i] = white.w[i];
+            rec->mask[i] = mask.w[i];
+        }
+        rec->player = (int8_t)player;
+        rec->terminal = term;
+        rec->tv = tv;
+    }
+}
+
+// ---- root prologue: mcts.py:288-295.  The root of game g's next search on the position (black, white) with `player` to move:
+// a fresh root (keep == false: the arena is reset, `budget` stored, a K_ROOTINIT expansion left pending in `rec` for an active
+// game) or, with keep, the tree yy_mcts_advance left (k_begin has written its state); for both the evaluation-cache epoch, the
+// root board and -- for an active game -- the planes of the root call, written to `planes_row`.
+template <int NW>
+__device__ __forceinline__ void root_setup(const MctsDev &d, GameState *st, LeafRec *rec, const int g, BB<NW> black, BB<NW> white,
+                                           const int player, const bool act, const bool keep, const int budget,
+                                           float *planes_row) {
+    if (!keep && lane_id() == 0) {
+        st->kept = 0;
+        st->root_kept = 0;
+        st->n_nodes = 1;  // node 0 = root
+        st->n_edges = 0;
+        st->root_N = 0;
+        st->root_W = 0.0f;
+        st->root_W_py = 0.0;
+        st->root_w_is_py = 1;
+        st->root_player = (int8_t)player;
+        st->active = act;
+        st->err = 0;
+        st->budget = budget;
+        rec->kind = act ? K_ROOTINIT : K_NONE;
+        rec->node = 0;
+        rec->path_len = 0;
+        rec->dup = -1;
+        d.nodes[(size_t)g * d.node_cap] = make_uint4(0u, node_pack(0, 0, player), 0u, 0u);
+    }
+    if (d.ec.meta && lane_id() == 0) {
+        // Entries of an older epoch are the first to be replaced.  Without YY_FLAG_KEEP_EVALUATIONS every search is its own
+        // epoch and only entries of the current one are looked at (reuse inside one search); with it the epoch changes when
+        // a game starts over from the empty board, so a game's searches share their evaluations.
+        const int stones = pos_stones<NW>(black, white);
+        uint32_t ep = st->ec_epoch;
+        if (!d.ec_keep || stones == 0 || ep == 0u) ep = (ep + 1u) & 0xFFFFFFu;
+        if (ep == 0u) ep = 1u;
+        st->ec_epoch = ep;
+        st->root_stones = stones;
+    }
+    uint64_t *gbd = d.gboard + (size_t)g * 2 * NW;
+    bb_store_lane0<NW>(gbd, black);
+    bb_store_lane0<NW>(gbd + NW, white);
+    if (!d.aliased && !keep) {
+        uint64_t *nb = d.nboard + (size_t)g * d.node_cap * 2 * NW;
+        bb_store_lane0<NW>(nb, black);
+        bb_store_lane0<NW>(nb + NW, white);
+    }
+    if (act) {
+        // root.expand's rules (mcts.py:63-71) for the pending K_ROOTINIT expansion
+        const GeoBB<NW> gb = geo_bb<NW>(d.geo);
+        BB<NW> mask;
+        bool term;
+        float tv;
+        if (!keep) {
+            leaf_rules<NW>(d.geo, gb, black, white, player, mask, term, tv);
+            leaf_store<NW>(rec, black, white, mask, player, term, tv);
+        }
+        write_planes<NW>(planes_row, d.geo, black, white);
+    }
+}
+
+// Node.get_children_distribution (mcts.py:183-215) of game g's root for T == 1 and T == 0 into pi[0 .. A) (float64; global
+// memory or LDS).  Every thread of the one-wavefront block calls it.
+template <int NW> __device__ __forceinline__ void root_distribution(const MctsDev &d, const int g, const int tzero, double *pi) {
+    const int A = d.geo.A;
+    const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
+    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    const bool act = rfl((int)d.state[g].active) != 0;
+    int sum = 0, mx = 0;
+    if (act)
+        for (int j = lane_id(); j < k; j += 64) {
+            int n = (int)edges[first + j].y;
+            sum += n;
+            mx = max(mx, n);
+        }
+    sum = wave_sum(sum);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+    double fill;
+    int nbest = 0;
+    if (tzero) {
+        // counts == max over ALL A actions (zeros included when max == 0), mcts.py:200-203
+        if (mx == 0) nbest = A;
+        else {
+            for (int j = lane_id(); j < k; j += 64) nbest += ((int)edges[first + j].y == mx);
+            nbest = wave_sum(nbest);
+        }
+        fill = (mx == 0) ? 1.0 / (double)A : 0.0;
+    } else {
+        fill = (sum > 0) ? 0.0 : 1.0 / (double)A;                                  // mcts.py:209-213
+    }
+    for (int a = lane_id(); a < A; a += 64) pi[a] = act ? fill : 0.0;
+    __syncthreads();
+    if (!act) return;
+    if (tzero ? (mx > 0) : (sum > 0))
+        for (int j = lane_id(); j < k; j += 64) {
+            const uint4 e = edges[first + j];
+            const int a = (int)(e.w >> 24), n = (int)e.y;
+            pi[a] = tzero ? ((n == mx) ? 1.0 / (double)nbest : 0.0) : (double)n / (double)sum;
+        }
+}

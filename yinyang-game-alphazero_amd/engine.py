@@ -386,6 +386,81 @@ def draw_budgets(seed, game_id, ply, searching, p_full, full_sims, fast_sims):
     return budgets, is_full
 
 
+# ------------------------------------------------------------------ free-running self-play (csrc/yy_selfplay_move.hip)
+class SelfPlayRun:
+    """The device state of a free-running self-play run on one BatchedMCTS context (include/yy_engine.h, yy_selfplay_run_*):
+    per-slot games and example histories, the noise array, the counters and the example buffer of `example_capacity` rows.
+    arm() starts a run; step(policy, value) is one capturable step (tree step with root noise + the move kernel);
+    poll_counters() enqueues an asynchronous copy of the counters into pinned memory; examples(n) copies the first n rows out."""
+
+    COUNTERS = ("started", "finished", "failed", "positions", "recorded", "rows", "overflow", "target")
+
+    def __init__(self, ctx, seed, num_simulations, example_capacity, dirichlet_alpha=0.3, dirichlet_epsilon=0.25,
+                 temperature_threshold=10, fast_simulations=None, full_search_probability=1.0):
+        self.ctx, self.capacity = ctx, int(example_capacity)
+        cfg = _lib.SelfPlayConfig(int(seed) & (2 ** 64 - 1), float(dirichlet_alpha), float(dirichlet_epsilon),
+                                  float(full_search_probability), int(temperature_threshold), int(num_simulations),
+                                  int(fast_simulations or 0), 0, self.capacity)
+        h = ct.c_void_p()
+        with torch.cuda.device(ctx.device):
+            check(lib().yy_selfplay_run_create(ctx._h, ct.byref(cfg), ct.byref(h)))
+        self._h = h
+        self.host, self._flip = torch.zeros((2, len(self.COUNTERS)), dtype=torch.int64).pin_memory(), 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            torch.cuda.synchronize(self.ctx.device)
+            lib().yy_selfplay_run_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def arm(self, num_games, first_game_index=0, stride=1):
+        ctx = self.ctx
+        with torch.cuda.device(ctx.device):
+            check(lib().yy_selfplay_run_arm(ctx._h, self._h, int(num_games), int(first_game_index), int(stride), _p(ctx.planes),
+                                            _p(ctx.needs_eval), _stream()))
+
+    def step(self, policy, value):
+        ctx = self.ctx
+        _need(policy, torch.float32, (ctx.rows, ctx.A), "policy")
+        _need(value, torch.float32, (ctx.rows,), "value")
+        with torch.cuda.device(ctx.device):
+            check(lib().yy_mcts_step_selfplay(ctx._h, self._h, _p(policy), _p(value), _p(ctx.planes), _p(ctx.needs_eval), _stream()))
+
+    def poll_counters(self):
+        """Enqueue the copy of the counters into one of two pinned records (alternating, so that the poll in flight never
+        writes the record being read) and return (event recorded behind the copy, record): the record is valid once
+        event.query() / event.synchronize() says so.  No device synchronisation."""
+        self._flip ^= 1
+        host = self.host[self._flip]
+        with torch.cuda.device(self.ctx.device):
+            check(lib().yy_selfplay_run_counters(self._h, ct.c_void_p(host.data_ptr()), _stream()))
+        event = torch.cuda.Event()
+        event.record()
+        return event, host
+
+    def counters(self, host):
+        """A completed poll's record as a dict."""
+        return dict(zip(self.COUNTERS, (int(x) for x in host.tolist())))
+
+    def examples(self, n):
+        """The first n rows of the example buffer (the order in which games finished) as the engine's example dict."""
+        ctx, dev, n = self.ctx, self.ctx.device, int(n)
+        out = dict(states=torch.empty((n, ctx.R, ctx.C), dtype=torch.int8, device=dev),
+                   policies=torch.empty((n, ctx.A), dtype=torch.float32, device=dev),
+                   values=torch.empty(n, dtype=torch.float32, device=dev),
+                   game_id=torch.empty(n, dtype=torch.int64, device=dev), ply=torch.empty(n, dtype=torch.int64, device=dev))
+        with torch.cuda.device(dev):
+            check(lib().yy_selfplay_run_examples(self._h, 0, n, _p(out["states"]), _p(out["policies"]), _p(out["values"]),
+                                                 _p(out["game_id"]), _p(out["ply"]), _stream()))
+        return out
+
+
 # ------------------------------------------------------------------ shared book of pre-evaluated opening positions
 class OpeningBook:
     """Every position with at most `max_stones` stones that alternating legal play reaches from the empty board (8x8: 770 232

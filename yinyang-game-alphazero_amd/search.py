@@ -104,6 +104,12 @@ class LockstepSearch:
                 self._sim_step(rows)
                 done += 1
 
+    def issue(self, n):
+        """n steps of whatever _sim_step issues, outside a search of run(): the free-running driver's call."""
+        self.ctx.bind_evaluator(self.evaluator)
+        self._drop_stale_graphs()
+        self._middle_steps(self.ctx.G, n)
+
     def run(self, boards, root_players, num_sims, noise=None, eps=0.25, active=None, rows=None, num_sims_bound=None):
         """rows: evaluate only leaf rows [0, rows) -- the caller guarantees every active game has an index below it
         (SelfPlayEngine packs the live games to the front when a batch drains).  One graph per distinct `rows`.
@@ -115,3 +121,22 @@ class LockstepSearch:
         rows = ctx.G if rows is None else min(int(rows), ctx.G)
         ctx.run_search(boards, root_players, num_sims, lambda root: self._evaluate(rows, compact=not root), noise, eps, active,
                        lambda n: self._middle_steps(rows, n), num_sims_bound)
+
+
+class FreeRunningSearch(LockstepSearch):
+    """The step of free-running self-play under LockstepSearch's capture scheme (a few eager steps, then the one-step graph and
+    the unrolled one, keyed by the evaluator's form_key): one step = [evaluator on the rows flagged by needs_eval] +
+    [engine.SelfPlayRun.step: the tree step with root noise + the move kernel].  The steps of all games are the same launch
+    sequence whatever the games are doing, so issue(n) replays it n times; nothing is read back."""
+
+    def __init__(self, ctx, evaluator, run, use_graph=True, eager_sims=3, unroll=None):
+        super().__init__(ctx, evaluator, use_graph=use_graph, eager_sims=eager_sims, unroll=unroll)
+        self.run_state = run              # the captured steps hold its pointers: a new run means a new FreeRunningSearch
+
+    def _sim_step(self, rows):
+        policy, value = self._evaluate(rows, compact=True)
+        if self.timer is not None:
+            self.timer.start()
+        self.run_state.step(policy, value)
+        if self.timer is not None:
+            self.timer.stop()

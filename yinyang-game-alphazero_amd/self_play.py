@@ -22,10 +22,11 @@ import numpy as np
 import torch
 
 from . import engine
+from ._lib import YY_E_ARENA, YYError
 from .game import YinYangLogic
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
-from .search import LockstepSearch
+from .search import FreeRunningSearch, LockstepSearch
 
 DRAW = 1e-4
 
@@ -94,8 +95,55 @@ def _playout_cap(num_simulations, fast_simulations, full_search_probability):
     return {} if P == 1.0 else dict(fast_simulations=fast, full_search_probability=P)
 
 
+def _free_running(free_running, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
+                  tree_reuse=False):
+    """free_running as the engine takes it.  The move kernel (csrc/yy_selfplay_move.hip) plays copied boards, one descent per
+    step, the per-game counter streams and a fresh root per move: every other combination raises ValueError -- on the host,
+    before anything touches the device.  Follow-ups: leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" and
+    tree_reuse (yy_mcts_advance empties the tree of every game it is not told to keep: re-rooting inside the step needs a
+    "leave alone" action first)."""
+    if not free_running:
+        return False
+    bad = []
+    if max(1, int(leaves_per_step)) > 1:
+        bad.append(f"leaves_per_step={leaves_per_step}")
+    if board_semantics == "aliased":
+        bad.append('board_semantics="aliased"')
+    if reference_quirks:
+        bad.append("reference_quirks=True")
+    if rng != "philox":
+        bad.append(f'rng="{rng}"')
+    if tree_reuse:
+        bad.append("tree_reuse=True")
+    if bad:
+        raise ValueError(f"free_running=True: the in-step move plays copied boards with one descent per step, the device's "
+                         f"counter streams and a fresh root per move -- not with {', '.join(bad)}")
+    return True
+
+
+def free_running_step_bound(num_games, slots, actions, num_simulations):
+    """Steps a free-running run of num_games games on `slots` slots can need at most.  A game is at most A + 2 moves of
+    num_simulations + 1 steps each = L steps; a free slot takes the next game at once (greedy list scheduling), so the last
+    game starts no later than the mean load num_games * L / slots and the run ends within (ceil(num_games / slots) + 1) * L.
+    The host stops with an error there instead of spinning: beyond it something is wrong."""
+    return (-(-int(num_games) // max(1, int(slots))) + 1) * (int(actions) + 2) * (int(num_simulations) + 1)
+
+
+def sort_examples(ex):
+    """The examples ordered by (game_id, ply), on their device: the order free-running runs return, whatever order the games
+    finished in."""
+    if ex["game_id"].numel() == 0:
+        return ex
+    span = int(ex["ply"].max()) + 1
+    order = torch.argsort(ex["game_id"] * span + ex["ply"], stable=True)
+    return {k: v.index_select(0, order) for k, v in ex.items()}
+
+
 def _play_to_completion(eng, progress=None):
-    """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples."""
+    """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples.
+    A free-running engine has no lockstep move: its own loop replays steps until the device's counters say the run is over."""
+    if getattr(eng, "free_running", False):
+        return eng.play_to_completion(progress)
     moves = 0
     while eng.n_alive > 0:
         eng.play_move()
@@ -116,8 +164,20 @@ class SelfPlayEngine:
                  device=None, first_game_index=0, game_index_stride=1, compact_tail=True, row_tiers=None,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
-        """reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, poll_steps=None):
+        """free_running (not in the reference; default off = lockstep moves, today's launches, graphs and games): the games play
+        their moves on the device, inside the search step (csrc/yy_selfplay_move.hip).  A game whose search
+        is complete records its example, draws and plays its move, handles passes and sets up its next root in the same step --
+        or ends, hands its labelled examples to the run's example buffer and lets the run's next game start in its slot --
+        while the other games keep simulating; the host only replays captured steps and, every poll_steps steps (default: four
+        unrolled graphs), enqueues an asynchronous copy of the run's counters, reading the PREVIOUS poll's record.  The games
+        are the lockstep engine's bit for bit (same seed, same game indices: every draw is keyed by (seed, game index, ply)
+        and the evaluator sees a game's rows one by one), given an evaluator whose row results do not depend on the batch;
+        collect() returns them sorted by (game_id, ply).  Evaluation reuse, the opening book and playout cap work as in
+        lockstep; compact_tail / row_tiers do not apply (slots do not move: the compacted evaluator pays for live rows only).
+        play_move() / enqueue_move() raise.  Not with leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" or
+        tree_reuse (ValueError; follow-ups).
+        reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
         declares `row_independent` (the split-f16 evaluator does).  The reference asks the network for every leaf: a node
         without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move order of the same search
         already reached (:385-397), a position the previous move's search evaluated -- and gets the same numbers each time.
@@ -160,6 +220,8 @@ class SelfPlayEngine:
         on when that happens.  It changes which moves a search picks.  Not with leaves_per_step > 1 or aliased boards:
         ValueError."""
         assert board_semantics in ("aliased", "copied")
+        assert rng in ("philox", "numpy")
+        self.free_running = _free_running(free_running, leaves_per_step, board_semantics, reference_quirks, rng, tree_reuse)
         self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
         cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.fast_sims, self.p_full = cap.get("fast_simulations"), cap.get("full_search_probability", 1.0)
@@ -191,8 +253,9 @@ class SelfPlayEngine:
         self.book = _opening_book(opening_book, game, evaluator, self.device)
         if self.book is not None:
             self.ctx.set_book(self.book)
-        self.search = LockstepSearch(self.ctx, evaluator, use_graph=use_graph)
-        self.seed = int(seed)                      # key of the per-game counter streams (csrc/yy_selfplay.hip)
+        # free-running: the steps are FreeRunningSearch's (self.free_search, made with the run's device state by begin_run)
+        self.search = None if self.free_running else LockstepSearch(self.ctx, evaluator, use_graph=use_graph)
+        self.seed = int(seed)                     # key of the per-game counter streams (csrc/yy_selfplay.hip)
         assert rng in ("philox", "numpy")
         self.rng, self.numpy_seeds, self._rs = rng, numpy_seeds, {}
         self.n_alive = 0                           # live games, tracked on the host (no device read needed)
@@ -201,6 +264,16 @@ class SelfPlayEngine:
         # no-op moves (illegal placements), so leave generous room there.
         self.T = self.A + 2 if not self.quirks else 4 * self.A + 8
         dev, G, T = self.device, self.G, self.T
+        self.steps_issued = 0  # free-running: steps put on the stream so far
+        if self.free_running:
+            # the per-slot games, their histories and the finished examples live in the run's device state (engine.SelfPlayRun),
+            # made by begin_run for the run's game count; the host keeps the counters it read last
+            self.use_graph, self.poll_steps = use_graph, poll_steps
+            self.run_state = self.free_search = self._run_open = self._tick = None
+            self._example_capacity = None      # rows of the example buffer; None: num_games * (A + 2), which always fits
+            self.recorded = self.games_started = self.games_finished = self.games_target = self.positions = 0
+            self.out, self.compact_tail, self.rows = [], False, G
+            return
         self.boards = torch.zeros((G, self.R, self.C), dtype=torch.int8, device=dev)
         self.players = torch.ones(G, dtype=torch.int8, device=dev)
         self.ply = torch.zeros(G, dtype=torch.int32, device=dev)
@@ -228,8 +301,15 @@ class SelfPlayEngine:
         self.tiers = sorted({G} | ({m for m in range(1024, G, 1024)} | {m for m in (512, 256) if m < G}
                                    if row_tiers is None else {int(t) for t in row_tiers if 0 < int(t) < G}))
 
+    def _lockstep_only(self, what):
+        """The lockstep move and its per-slot tensors do not exist in a free-running engine: say so, clearly."""
+        if self.free_running:
+            raise RuntimeError(f"free_running=True: the games play their moves on the device, there is no lockstep move "
+                               f"({what}) -- use run() or begin_run() + play_to_completion()")
+
     def _pack_live_games(self):
         """Once per tier change: stable permutation of every per-slot tensor, live games first."""
+        self._lockstep_only("_pack_live_games()")
         perm = torch.argsort((~self.alive).to(torch.int8), stable=True)
         for name in ("boards", "players", "ply", "n_ex", "alive", "game_id", "hist_state", "hist_pi", "hist_player") + (
                 ("hist_ply",) if self.hist_ply is not None else ()):
@@ -237,6 +317,7 @@ class SelfPlayEngine:
 
     # ---- slots
     def _start_games(self, slots):
+        self._lockstep_only("_start_games()")
         n = int(slots.numel())
         if n == 0:
             return
@@ -324,6 +405,7 @@ class SelfPlayEngine:
     def finish_move(self):
         """Waits for the move enqueue_move() put on the engine's stream, reads its one small statistics record (positions
         searched, games finished) and, when games finished, labels their examples and refills their slots."""
+        self._lockstep_only("finish_move()")
         assert self._pending is not None, "finish_move() without enqueue_move()"
         host, event, fin, fin_res, fin_player = self._pending
         self._pending = None
@@ -348,6 +430,7 @@ class SelfPlayEngine:
         per-game counter streams of csrc/yy_selfplay.hip, so a game's noise and moves depend only on (seed, global game index,
         ply).  Between the two calls the host is free to enqueue the moves of other engines on other streams
         (SelfPlayLanes): their kernels fill the compute units this engine's partly empty last round of workgroups leaves idle."""
+        self._lockstep_only("enqueue_move()")
         assert self._pending is None, "enqueue_move() twice without finish_move()"
         with self._on_stream():
             self._enqueue_move()
@@ -452,10 +535,99 @@ class SelfPlayEngine:
 
     def begin_run(self, num_games):
         """Arm the engine for `num_games` more games: the first ones start in the free slots, the others as slots free up."""
+        if self.free_running:
+            return self._begin_free_run(int(num_games))
         with self._on_stream():
             self.games_target = self.games_started + int(num_games)
             free = (~self.alive).nonzero(as_tuple=True)[0]
             self._start_games(free[: int(num_games)])
+
+    # ---- free-running: the games move on the device, the host replays steps and polls the run's counters
+    def _begin_free_run(self, n):
+        """Make (or reuse) the run's device state, sized for n games, and put every slot's first root on the stream."""
+        if self._run_open is not None:
+            raise RuntimeError("begin_run() while a free-running run is in progress: play_to_completion() first")
+        cap = max(1, n * (self.A + 2)) if self._example_capacity is None else int(self._example_capacity)
+        with self._on_stream():
+            if self.run_state is None or (self.run_state.capacity < cap if self._example_capacity is None
+                                          else self.run_state.capacity != cap):
+                if self.run_state is not None:
+                    self.run_state.close()
+                self.run_state = engine.SelfPlayRun(self.ctx, self.seed, self.sims, cap, self.alpha, self.eps, self.thr,
+                                                    self.fast_sims, self.p_full)
+                self.free_search = FreeRunningSearch(self.ctx, self.evaluator, self.run_state, use_graph=self.use_graph)
+            self.run_state.arm(n, self.first_game_index + self.games_started * self.stride, self.stride)
+        self.games_target = self.games_started + n
+        self.n_alive = n
+        self._run_open = n
+
+    def play_to_completion(self, progress=None):
+        """Free-running: replay steps on the engine's stream until the run begin_run() armed is over; returns the examples.
+        Every poll_steps steps the counter copy is enqueued with an event and the PREVIOUS poll's record is read, so the host
+        never waits on the stream it is feeding; the run is over when finished + failed == its games.  Raises YYError when a
+        search failed (the other games' examples stay collectable), when the example buffer overflowed, or when the run is not
+        over after free_running_step_bound() steps."""
+        if not self.free_running:
+            return _play_to_completion(self, progress)
+        while not self._free_tick():
+            if progress:
+                progress(self)
+        return self._free_finish()
+
+    def _free_tick(self):
+        """One batch of poll_steps steps and the poll behind it; reads the previous poll's record.  True: the run is over (or
+        there is none)."""
+        n = self._run_open
+        if not n:
+            return True
+        if not isinstance(self._tick, dict):
+            poll = max(1, int(self.poll_steps) if self.poll_steps else 4 * self.free_search.unroll)
+            self._tick = dict(poll=poll, steps=0, prev=None, cur=None, bound=free_running_step_bound(n, self.G, self.A, self.sims))
+        t, run = self._tick, self.run_state
+        with self._on_stream():
+            self.free_search.issue(t["poll"])
+            t["steps"] += t["poll"]
+            self.steps_issued += t["poll"]
+            t["prev"], t["cur"] = t["cur"], run.poll_counters() + (t["steps"],)
+        if t["prev"] is None:
+            return False
+        event, record, steps_then = t["prev"]
+        event.synchronize()                                # a whole batch of steps is queued behind it
+        c = run.counters(record)
+        if c["finished"] + c["failed"] >= n:
+            return True
+        if steps_then >= t["bound"]:
+            self._run_open, self._tick, self.n_alive = None, None, 0
+            raise YYError(-5, f"free-running self-play: {c['finished'] + c['failed']} of {n} games over after {steps_then} steps "
+                              f"(bound {t['bound']}): something is wrong")
+        return False
+
+    def _free_finish(self):
+        """The run is over: its final counters, its examples; raises for failed searches and an overflowed example buffer."""
+        n, t, run = self._run_open, self._tick, self.run_state
+        self._run_open, self._tick, self.n_alive = None, None, 0
+        if not n:
+            return self.collect()
+        t["cur"][0].synchronize()                          # issued after the poll that showed the end: the final counters
+        c = run.counters(t["cur"][1])
+        self.games_started += n
+        self.positions += c["positions"]
+        self.recorded += c["recorded"]
+        self.games_finished += c["finished"]
+        if c["overflow"]:
+            raise YYError(-3, f"free-running self-play: the example buffer ({run.capacity} rows) is too small: the examples of "
+                              f"{c['overflow']} games did not fit ({c['rows']} rows asked for)")
+        with self._on_stream():
+            self.out.append(run.examples(c["rows"]))
+        if c["failed"]:
+            try:
+                self.ctx.status()                          # clears the sticky per-game flags that the count below reports
+            except YYError:
+                pass
+            raise YYError(YY_E_ARENA, f"free-running self-play: {c['failed']} of {n} games failed (tree arena overflow or "
+                                      f"non-finite evaluator output) and were abandoned, their examples dropped")
+        self.ctx.status()
+        return self.collect()
 
     def run(self, num_games, progress=None):
         """Play `num_games` games to completion; returns the examples (device tensors)."""
@@ -464,6 +636,8 @@ class SelfPlayEngine:
 
     def collect(self):
         out, self.out = self.out, []
+        if out and self.free_running:
+            return sort_examples({k: torch.cat([o[k] for o in out]) for k in out[0]})
         if not out:
             e = torch.empty
             return dict(states=e((0, self.R, self.C), dtype=torch.int8, device=self.device),
@@ -475,6 +649,9 @@ class SelfPlayEngine:
         return dict(states=cat[0], policies=cat[1], values=cat[2], game_id=cat[3], ply=cat[4])
 
     def close(self):
+        if getattr(self, "run_state", None) is not None:
+            self.run_state.close()                 # before the context its kernels read
+            self.run_state = self.free_search = None
         self.ctx.close()
 
 
@@ -514,8 +691,13 @@ class SelfPlayLanes:
                  full_search_probability=1.0, **engine_kwargs):
         """leaves_per_step: every lane's searches are leaf-parallel (SelfPlayEngine leaves_per_step; same defaults, same
         refusals, raised here before the book or any lane is built).  tree_reuse=True (a SelfPlayEngine keyword): likewise.  fast_simulations / full_search_probability: playout-cap
-        randomisation in every lane (SelfPlayEngine's; checked here first).  The other keywords are SelfPlayEngine's."""
+        randomisation in every lane (SelfPlayEngine's; checked here first).  free_running=True (a SelfPlayEngine keyword; checked
+        here first): every lane runs free on its own stream and the host alternates the lanes' batches of graph replays.  The
+        other keywords are SelfPlayEngine's."""
         cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        self.free_running = _free_running(engine_kwargs.get("free_running", False), leaves_per_step,
+                                          engine_kwargs.get("board_semantics", "copied"), engine_kwargs.get("reference_quirks", False),
+                                          engine_kwargs.get("rng", "philox"), engine_kwargs.get("tree_reuse", False))
         _tree_reuse(engine_kwargs.get("tree_reuse", False), leaves_per_step, engine_kwargs.get("board_semantics", "copied"))
         self.leaves_per_step = _leaf_parallel(leaves_per_step, engine_kwargs.get("board_semantics", "copied"),
                                               engine_kwargs.get("reference_quirks", False),
@@ -548,6 +730,31 @@ class SelfPlayLanes:
     recorded = property(lambda self: sum(l.recorded for l in self.lanes))
     games_finished = property(lambda self: sum(l.games_finished for l in self.lanes))
     n_alive = property(lambda self: sum(l.n_alive for l in self.lanes))
+    steps_issued = property(lambda self: sum(l.steps_issued for l in self.lanes))
+
+    def play_to_completion(self, progress=None):
+        """Free-running lanes: every lane's batch of steps and its poll are enqueued in turn, so the lanes' graph replays
+        alternate on their streams; a lane whose run is over drops out.  Then every lane's run is closed: the first error is
+        raised after all lanes have handed over their examples."""
+        if not self.free_running:
+            return _play_to_completion(self, progress)
+        live = list(self.lanes)
+        while live:
+            live = [l for l in live if not l._free_tick()]
+            if progress:
+                progress(self)
+        parts, err = [], None
+        for l in self.lanes:
+            try:
+                parts.append(l._free_finish())
+            except YYError as e:
+                err = err or e
+                parts.append(l.collect())
+        if err is not None:
+            for l, p in zip(self.lanes, parts):
+                l.out.append(p)                            # stay collectable
+            raise err
+        return sort_examples({k: torch.cat([p[k] for p in parts]) for k in parts[0]})
 
     def play_move(self):
         """One lockstep move of every lane: all lanes' moves are enqueued on their streams, then finished in turn."""
@@ -570,7 +777,8 @@ class SelfPlayLanes:
     def collect(self):
         torch.cuda.synchronize(self.device)
         parts = [l.collect() for l in self.lanes]
-        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        ex = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return sort_examples(ex) if self.free_running else ex
 
     def close(self):
         torch.cuda.synchronize(self.device)
@@ -685,8 +893,10 @@ class SelfPlayWorker:
     def __init__(self, game, model_path, num_simulations=800, num_games=1, temperature_threshold=10,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
-        """leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False):
+        """free_running: refused (ValueError).  This class plays ONE game at a time through MCTS, drawing from numpy's global
+        stream: there is no batch whose games could be freed from each other; the mode is SelfPlayEngine's.
+        leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
         board_semantics="copied" and reference_quirks=False, which are not this class's defaults.
         fast_simulations N with full_search_probability P < 1 (not in the reference): playout-cap randomisation -- before every
         search one np.random.random() from the global stream decides between num_simulations (probability P; the move is
@@ -694,6 +904,9 @@ class SelfPlayWorker:
         tree_reuse=True (not in the reference's search): play_game hands the root and the move played to MCTS.reuse_tree, as
         the reference does at self_play.py:192, and the next search continues from that subtree (MCTS tree_reuse); needs
         board_semantics="copied"."""
+        if free_running:
+            raise ValueError("free_running=True: SelfPlayWorker plays one game at a time through MCTS (numpy's global stream): "
+                             "there is no batch to free -- use SelfPlayEngine / SelfPlayManager")
         self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
         self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks)
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
@@ -795,8 +1008,9 @@ class SelfPlayManager:
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
-                 tree_reuse=False):
-        """fast_simulations / full_search_probability: playout-cap randomisation (SelfPlayEngine's; checked here).
+                 tree_reuse=False, free_running=False):
+        """free_running: the rank's games play their moves on the device (SelfPlayEngine free_running; checked here).
+        fast_simulations / full_search_probability: playout-cap randomisation (SelfPlayEngine's; checked here).
         tree_reuse: every search continues from the subtree under the move played (SelfPlayEngine's; checked here).
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference.
@@ -807,6 +1021,7 @@ class SelfPlayManager:
                                               opening_book_stones)
         self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
         self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
+        self.free_running = _free_running(free_running, leaves_per_step, board_semantics, reference_quirks, "philox", tree_reuse)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -848,14 +1063,16 @@ class SelfPlayManager:
                              first_game_index=first, game_index_stride=stride, device=dev,
                              reuse_pass_value=self.evaluation_reuse, reuse_transpositions=self.evaluation_reuse,
                              keep_evaluations=self.evaluation_reuse, **self.playout_cap,
-                             **(dict(tree_reuse=True) if self.tree_reuse else {}))
+                             **(dict(tree_reuse=True) if self.tree_reuse else {}),
+                             **(dict(free_running=True) if self.free_running else {}))
         t0 = time.perf_counter()
         ex = eng.run(mine) if mine > 0 else eng.collect()
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         counters = eng.ctx.status()
         ex = gather_examples(ex, capacity=example_capacity(total, world, eng.T))
-        self.stats = dict(seconds=t1 - t0, positions=eng.positions, games=eng.games_finished, **counters)
+        self.stats = dict(seconds=t1 - t0, positions=eng.positions, games=eng.games_finished, **counters,
+                          **(dict(steps_issued=eng.steps_issued) if self.free_running else {}))
         eng.close()
         return ex
 
@@ -867,8 +1084,8 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     tensors (`states` int8 [N,R,C], `policies` float64 [N,A], `values` float64 [N]; `boards` is an
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
-    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords (tree_reuse among them) are
-    SelfPlayManager's too."""
+    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords (tree_reuse and
+    free_running among them) are SelfPlayManager's too."""
     cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
     games_per_worker = max(1, num_games // num_workers)               # :355 (remainder dropped)
