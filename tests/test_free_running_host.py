@@ -37,8 +37,20 @@ def test_step_bound(pkg):
 
 
 def test_argument_checks_need_no_device(pkg):
-    check = pkg.self_play._free_running
-    assert check(False, leaves_per_step=4, board_semantics="aliased", reference_quirks=True, rng="numpy", tree_reuse=True) is False
+    from yinyang_game_alphazero_amd import options
+
+    def check(free_running, **kw):
+        return options.resolve(free_running=free_running, **kw).free_running
+
+    # off: the free-running rule checks nothing, even when every other option conflicts with it -- what the resolver still
+    # refuses then is the other options' own rules (tree_reuse and leaves_per_step do not go with each other or aliased boards)
+    everything = dict(leaves_per_step=4, board_semantics="aliased", reference_quirks=True, rng="numpy", tree_reuse=True)
+    with pytest.raises(options.OptionConflict) as e:
+        check(False, **everything)
+    assert e.value.option != "free_running" and "free_running" not in str(e.value)
+    assert check(False, leaves_per_step=4, rng="numpy") is False
+    assert check(False, board_semantics="aliased", reference_quirks=True, rng="numpy") is False
+    assert check(False, rng="numpy", tree_reuse=True) is False
     assert check(True) is True
     for kw, word in ((dict(leaves_per_step=2), "leaves_per_step=2"), (dict(board_semantics="aliased"), "aliased"),
                      (dict(reference_quirks=True), "reference_quirks"), (dict(rng="numpy"), "numpy"),

@@ -90,30 +90,32 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+# What each mode hands to the options resolver (the package's options.resolve: the one copy of the rules), one call per tuple.
+# train's self-play always runs on copied boards without the quirks, so --tree-reuse and --free-running do not look at those two
+# flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
+_SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running")
+HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
+          "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
+          "evaluate": [("leaves_per_step", "tree_reuse")]}
+
+
+def _flag(args, name):
+    """An option's name as its flag, with the value it was given."""
+    attr = "simulations" if name == "num_simulations" else name
+    flag, value = "--" + attr.replace("_", "-"), getattr(args, attr)
+    return flag if value is True else f"{flag} {value}"
+
+
 def refused(args):
-    """The flag combinations no search runs with, as a one-line message (None: none), from the parsed flags alone."""
-    if args.mode in ("self-play", "train"):
-        if not 0.0 < args.full_search_probability <= 1.0:
-            return f"train_alphazero.py: --full-search-probability {args.full_search_probability} is outside (0, 1]"
-        if args.fast_simulations is not None and args.fast_simulations < 1:
-            return f"train_alphazero.py: --fast-simulations {args.fast_simulations} is below 1"
-        if args.fast_simulations is not None and args.fast_simulations > args.simulations:
-            return f"train_alphazero.py: --fast-simulations {args.fast_simulations} is above --simulations {args.simulations}"
-    if args.leaves_per_step > 1 and args.mode in ("self-play", "train"):
-        for flag, given in (("--board-semantics aliased", args.board_semantics == "aliased"), ("--reference-quirks", args.reference_quirks)):
-            if given:
-                return f"train_alphazero.py: --leaves-per-step {args.leaves_per_step} searches copied boards without the reference's quirks: not with {flag}"
-    if args.tree_reuse:
-        if args.leaves_per_step > 1:
-            return f"train_alphazero.py: --tree-reuse re-roots the tree for one descent per step: not with --leaves-per-step {args.leaves_per_step}"
-        if args.board_semantics == "aliased" and args.mode == "self-play":
-            return "train_alphazero.py: --tree-reuse needs every node's own board: not with --board-semantics aliased"
-    if args.free_running and args.mode in ("self-play", "train"):
-        for flag, given in ((f"--leaves-per-step {args.leaves_per_step}", args.leaves_per_step > 1),
-                            ("--board-semantics aliased", args.board_semantics == "aliased" and args.mode == "self-play"),
-                            ("--reference-quirks", args.reference_quirks and args.mode == "self-play"), ("--tree-reuse", args.tree_reuse)):
-            if given:
-                return f"train_alphazero.py: --free-running plays copied boards, one descent per step, a fresh root per move: not with {flag}"
+    """The flag combinations no search runs with, as a one-line message (None: none), from the parsed flags alone: the
+    resolver's verdict, its option names rendered as flags."""
+    from yinyang_game_alphazero_amd import options       # imports neither torch nor numpy
+    for names in HANDED[args.mode]:
+        try:
+            options.resolve(**{n: getattr(args, "simulations" if n == "num_simulations" else n) for n in names})
+        except options.OptionConflict as e:
+            others = ", ".join(_flag(args, n) for n in e.conflicts)
+            return f"train_alphazero.py: {_flag(args, e.option)}: {'not with ' + others if others else 'out of range'} ({e})"
     return None
 
 

@@ -19,11 +19,11 @@ import time
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, options
 from .mcts import MCTS
 from .network import BatchedEvaluator, YinYangNeuralNetwork
 from .search import LockstepSearch
-from .self_play import _free_running, _playout_cap, _tree_reuse, generate_self_play_data
+from .self_play import generate_self_play_data
 from .training import run_training_pipeline
 
 
@@ -124,10 +124,8 @@ class Arena:
         opponent's (engine.BatchedMCTS.advance; the reference's two reuse_tree call sites, alphazero.py:346/364), and the
         player's next search tops the kept root up to num_simulations.  Not with literal=True or leaves_per_step > 1."""
         self.game = game
-        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, "aliased" if literal else "copied")
-        self.K = max(1, int(leaves_per_step))
-        if self.K > 1 and literal:
-            raise ValueError("leaves_per_step > 1 needs copied boards: literal=True searches the aliased board")
+        opts = options.resolve(num_simulations, leaves_per_step, "aliased" if literal else "copied", tree_reuse=tree_reuse)
+        self.tree_reuse, self.K = opts.tree_reuse, opts.leaves_per_step
         self.literal = bool(literal)
         self.evaluation_reuse = bool(evaluation_reuse)
         self.reference_scoring = bool(reference_scoring) or self.literal
@@ -323,17 +321,12 @@ class AlphaZero:
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False):
-        """leaves_per_step K > 1 (not in the reference): leaf-parallel searches in the loop's self-play (SelfPlayManager
-        leaves_per_step: evaluation reuse off, no book) and in its arena (Arena leaves_per_step).
-        fast_simulations / full_search_probability: playout-cap randomisation in the loop's self-play (SelfPlayEngine's); the
-        arena always searches num_simulations.
-        tree_reuse: the loop's self-play and its arena continue every search from the subtree under the move played
-        (SelfPlayEngine / Arena tree_reuse); not with leaves_per_step > 1."""
-        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step)
-        # the loop's self-play lets its games move on the device (SelfPlayEngine free_running); the arena is unchanged
-        self.free_running = _free_running(free_running, leaves_per_step, tree_reuse=tree_reuse)
-        self.leaves_per_step = max(1, int(leaves_per_step))
-        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions, for the
+        loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also for its arena, which always searches
+        num_simulations and plays in lockstep."""
+        self.options = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
+                                       full_search_probability=full_search_probability, tree_reuse=tree_reuse,
+                                       free_running=free_running)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold
@@ -363,9 +356,7 @@ class AlphaZero:
                                        temperature_threshold=self.temperature_threshold, nn_mode=self.nn_mode,
                                        num_channels=self.num_channels, num_res_blocks=self.num_res_blocks,
                                        concurrent_games=self.concurrent_games, seed=len(self.history),
-                                       leaves_per_step=self.leaves_per_step, **self.playout_cap,
-                                       **(dict(tree_reuse=True) if self.tree_reuse else {}),
-                                       **(dict(free_running=True) if self.free_running else {}))
+                                       **self.options.keywords())
 
     def train(self):
         # the reference passes num_iterations=1 and ignores --epochs/--batch-size/--lr (alphazero.py:120-127,
@@ -394,7 +385,7 @@ class AlphaZero:
         cur = _load_evaluator(self.game, current_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
-                     leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse).play(mine)
+                     leaves_per_step=self.options.leaves_per_step, tree_reuse=self.options.tree_reuse).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)

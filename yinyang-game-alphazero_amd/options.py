@@ -1,0 +1,121 @@
+"""The search options of the self-play layer and the ONE place that says which of them combine.  Imports neither torch nor
+numpy: train_alphazero.py asks for the verdict before it pays for either.  Every entry point calls `resolve` once with the
+inputs it has and hands `SearchOptions.keywords()` on.  A new option is one field, one rule in `resolve`, one forwarded keyword."""
+from dataclasses import dataclass
+
+
+class OptionConflict(ValueError):
+    """A refused combination: `option` names the option that refuses, `conflicts` those it does not go with (none: out of range)."""
+
+    def __init__(self, message, option, conflicts=()):
+        super().__init__(message)
+        self.option, self.conflicts = option, tuple(conflicts)
+
+
+@dataclass(frozen=True)
+class SearchOptions:
+    """The resolved options.  None is in the reference; every default is its search and the engine's launches and games without it.
+
+    leaves_per_step K > 1: every search is leaf-parallel (engine.BatchedMCTS leaves_per_step): K descents per game and step
+    with virtual visits, their leaves evaluated in one launch of up to K rows per game, ceil(num_simulations / K) steps per
+    move -- for runs with few concurrent games, where a step costs the same whatever it carries.  The move around the search is
+    unchanged (pass handling, root noise, the example record, the draws): it reads the root, and the root holds num_simulations
+    visits at any K.  The None defaults of the evaluation-reuse options then mean OFF and no book is built: the leaf-parallel
+    selection (k_mcts_multi) looks nothing up -- no kept pass value, no evaluation cache, no book -- and the tree context
+    refuses the combination at create.  Asking for one of them explicitly, for aliased boards or for reference_quirks together
+    with K > 1 is refused.  It changes which moves a search picks.
+
+    fast_simulations N with full_search_probability P < 1: playout-cap randomisation.  Every move draws one uniform per game
+    from the game's own counter stream (yy_selfplay_draw_budgets: keyed by seed, global game index and ply, so not by slot,
+    batch or rank; SelfPlayWorker: one np.random.random() from the global stream): with probability P the game searches
+    num_simulations, else N, in the same lockstep search (per-game budgets on the device, include/yy_engine.h
+    yy_mcts_set_sim_budgets; the host issues the steps of num_simulations and reads no draw).  Root noise, pi, the temperature
+    rule, the move draw and the z labels are unchanged; only the moves searched in full are recorded as examples (their `ply`
+    is the game's ply).  Off -- N None or P == 1 -- draws nothing.  N outside 1 .. num_simulations or P outside (0, 1] is
+    refused.
+
+    tree_reuse: after the move draw every game's tree is re-rooted at the move played (engine.BatchedMCTS.advance; -1 = keep
+    nothing for the games that did not search or that ended; SelfPlayWorker: MCTS.reuse_tree, as the reference calls it at
+    self_play.py:192), and the next search continues from that subtree and tops its root up to the move's budget --
+    num_simulations, or the playout-cap draw.  The host issues the same steps; a game whose kept root already holds part of its
+    budget asks for fewer evaluator rows.  A kept tree belongs to its slot: when the draining batch is packed (compact_tail)
+    every tree is dropped once, so with tree_reuse a game's transcript depends on when that happens.  It changes which moves a
+    search picks.  The re-rooting kernel works on copied boards and one descent per step (include/yy_engine.h,
+    yy_mcts_advance): refused with leaves_per_step > 1 or aliased boards.
+
+    free_running: the games play their moves on the device, inside the search step (csrc/yy_selfplay_move.hip; DESIGN.md
+    section 3).  A game whose search is complete records its example, draws and plays its move, handles passes and sets up its
+    next root in the same step -- or ends, hands its labelled examples to the run's example buffer and lets the run's next game
+    start in its slot -- while the other games keep simulating; the host only replays captured steps and, every poll_steps
+    steps (default: four unrolled graphs), enqueues an asynchronous copy of the run's counters, reading the PREVIOUS poll's
+    record.  The games are the lockstep engine's bit for bit (same seed, same game indices: every draw is keyed by (seed, game
+    index, ply) and the evaluator sees a game's rows one by one), given an evaluator whose row results do not depend on the
+    batch; collect() returns them sorted by (game_id, ply).  Evaluation reuse, the opening book and playout cap work as in
+    lockstep; compact_tail / row_tiers do not apply (slots do not move: the compacted evaluator pays for live rows only).  The
+    move kernel plays copied boards, one descent per step, the per-game counter streams and a fresh root per move: refused
+    with leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" and tree_reuse (follow-ups; yy_mcts_advance empties
+    the tree of every game it is not told to keep: re-rooting inside the step needs a "leave alone" action first)."""
+    leaves_per_step: int = 1
+    fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
+    full_search_probability: float = 1.0
+    tree_reuse: bool = False
+    free_running: bool = False
+
+    @property
+    def playout_cap(self):
+        """The two playout-cap keywords, {} when it is off."""
+        return {} if self.fast_simulations is None else dict(fast_simulations=self.fast_simulations,
+                                                              full_search_probability=self.full_search_probability)
+
+    def keywords(self):
+        """The keywords to hand to the next layer: leaves_per_step always, the others only when they are on."""
+        on = {k: True for k in ("tree_reuse", "free_running") if getattr(self, k)}
+        return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
+
+
+def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
+            evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
+            free_running=False):
+    """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
+    device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
+    given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
+    counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
+    -- free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name the same option everywhere."""
+    K = max(1, int(leaves_per_step))
+    aliased = board_semantics == "aliased"
+    if free_running:
+        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
+               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
+               (tree_reuse, "tree_reuse", "tree_reuse=True")]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict("free_running=True: the in-step move plays copied boards with one descent per step, the device's "
+                                 f"counter streams and a fresh root per move -- not with {', '.join(b[1] for b in bad)}",
+                                 "free_running", [b[0] for b in bad])
+    if tree_reuse and K > 1:
+        raise OptionConflict(f"tree_reuse=True: the tree is re-rooted for one descent per step only -- not with leaves_per_step={leaves_per_step}",
+                             "tree_reuse", ["leaves_per_step"])
+    if tree_reuse and aliased:
+        raise OptionConflict('tree_reuse=True: a kept subtree needs every node\'s own board -- not with board_semantics="aliased"',
+                             "tree_reuse", ["board_semantics"])
+    P = float(full_search_probability)
+    if not 0.0 < P <= 1.0:
+        raise OptionConflict(f"full_search_probability={full_search_probability}: the share of full searches lies in (0, 1]",
+                             "full_search_probability")
+    fast = None if fast_simulations is None else int(fast_simulations)
+    if fast is not None and fast < 1:
+        raise OptionConflict(f"fast_simulations={fast_simulations}: a fast search runs at least 1 simulation", "fast_simulations")
+    if fast is not None and num_simulations is not None and fast > int(num_simulations):
+        raise OptionConflict(f"fast_simulations={fast_simulations}: a fast search runs no more than num_simulations={num_simulations}",
+                             "fast_simulations", ["num_simulations"])
+    if K > 1:
+        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (reference_quirks, "reference_quirks", "reference_quirks=True"),
+               (any(x is not None and bool(x) for x in evaluation_reuse), "evaluation_reuse",
+                "evaluation reuse (reuse_pass_value / reuse_transpositions / keep_evaluations / evaluation_reuse)"),
+               (opening_book is not None and not (isinstance(opening_book, int) and opening_book <= 0), "opening_book", "an opening book")]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
+                                 f"book -- not with {', '.join(b[1] for b in bad)}", "leaves_per_step", [b[0] for b in bad])
+    cap = fast is not None and P < 1.0
+    return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running))

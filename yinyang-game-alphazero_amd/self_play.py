@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, options
 from ._lib import YY_E_ARENA, YYError
 from .game import YinYangLogic
 from .mcts import MCTS
@@ -38,87 +38,6 @@ def _opening_book(opening_book, game, evaluator, device):
     R, C = game.getBoardSize()
     return (engine.OpeningBook(R, C, evaluator, opening_book, rowcol=bool(getattr(game, "rowcol_rule", False)), device=device)
             if opening_book > 0 else None)
-
-
-def _leaf_parallel(leaves_per_step, board_semantics="copied", reference_quirks=False, evaluation_reuse=(), opening_book=None):
-    """K = leaves_per_step as the tree context takes it (>= 1).  K > 1 searches copied boards, evaluates every leaf and has no
-    book (engine.BatchedMCTS refuses the rest), and is not offered under the literal reproduction of the reference's play
-    (reference_quirks): a combination that asks for one of these EXPLICITLY raises ValueError -- on the host, before anything
-    touches the device.  evaluation_reuse: the reuse options as given (None = the default, which K > 1 resolves to off);
-    opening_book: an engine.OpeningBook or a stone count (None and counts <= 0 mean no book)."""
-    K = max(1, int(leaves_per_step))
-    if K == 1:
-        return K
-    bad = []
-    if board_semantics == "aliased":
-        bad.append('board_semantics="aliased"')
-    if reference_quirks:
-        bad.append("reference_quirks=True")
-    if any(x is not None and bool(x) for x in evaluation_reuse):
-        bad.append("evaluation reuse (reuse_pass_value / reuse_transpositions / keep_evaluations / evaluation_reuse)")
-    if opening_book is not None and not (isinstance(opening_book, int) and opening_book <= 0):
-        bad.append("an opening book")
-    if bad:
-        raise ValueError(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
-                         f"book -- not with {', '.join(bad)}")
-    return K
-
-
-def _tree_reuse(tree_reuse, leaves_per_step=1, board_semantics="copied"):
-    """tree_reuse as the engine takes it.  The re-rooting kernel works on copied boards and one descent per step
-    (include/yy_engine.h, yy_mcts_advance): together with leaves_per_step > 1 or aliased boards it raises ValueError -- on the
-    host, before anything touches the device."""
-    if not tree_reuse:
-        return False
-    if max(1, int(leaves_per_step)) > 1:
-        raise ValueError(f"tree_reuse=True: the tree is re-rooted for one descent per step only -- not with leaves_per_step={leaves_per_step}")
-    if board_semantics == "aliased":
-        raise ValueError('tree_reuse=True: a kept subtree needs every node\'s own board -- not with board_semantics="aliased"')
-    return True
-
-
-def _playout_cap(num_simulations, fast_simulations, full_search_probability):
-    """Playout-cap randomisation as the engine takes it: the keywords to hand on -- {} when it is off (fast_simulations None, or
-    full_search_probability 1: every search is a full one, today's engine), else both values.  Raises ValueError naming the
-    argument for fast_simulations outside 1 .. num_simulations or full_search_probability outside (0, 1] -- on the host, before
-    anything touches the device."""
-    P = float(full_search_probability)
-    if not 0.0 < P <= 1.0:
-        raise ValueError(f"full_search_probability={full_search_probability}: the share of full searches lies in (0, 1]")
-    if fast_simulations is None:
-        return {}
-    fast = int(fast_simulations)
-    if fast < 1:
-        raise ValueError(f"fast_simulations={fast_simulations}: a fast search runs at least 1 simulation")
-    if fast > int(num_simulations):
-        raise ValueError(f"fast_simulations={fast_simulations}: a fast search runs no more than num_simulations={num_simulations}")
-    return {} if P == 1.0 else dict(fast_simulations=fast, full_search_probability=P)
-
-
-def _free_running(free_running, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
-                  tree_reuse=False):
-    """free_running as the engine takes it.  The move kernel (csrc/yy_selfplay_move.hip) plays copied boards, one descent per
-    step, the per-game counter streams and a fresh root per move: every other combination raises ValueError -- on the host,
-    before anything touches the device.  Follow-ups: leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" and
-    tree_reuse (yy_mcts_advance empties the tree of every game it is not told to keep: re-rooting inside the step needs a
-    "leave alone" action first)."""
-    if not free_running:
-        return False
-    bad = []
-    if max(1, int(leaves_per_step)) > 1:
-        bad.append(f"leaves_per_step={leaves_per_step}")
-    if board_semantics == "aliased":
-        bad.append('board_semantics="aliased"')
-    if reference_quirks:
-        bad.append("reference_quirks=True")
-    if rng != "philox":
-        bad.append(f'rng="{rng}"')
-    if tree_reuse:
-        bad.append("tree_reuse=True")
-    if bad:
-        raise ValueError(f"free_running=True: the in-step move plays copied boards with one descent per step, the device's "
-                         f"counter streams and a fresh root per move -- not with {', '.join(bad)}")
-    return True
 
 
 def free_running_step_bound(num_games, slots, actions, num_simulations):
@@ -139,11 +58,9 @@ def sort_examples(ex):
     return {k: v.index_select(0, order) for k, v in ex.items()}
 
 
-def _play_to_completion(eng, progress=None):
-    """play_move() until no game of `eng` (SelfPlayEngine or SelfPlayLanes, armed by begin_run) is alive; returns the examples.
-    A free-running engine has no lockstep move: its own loop replays steps until the device's counters say the run is over."""
-    if getattr(eng, "free_running", False):
-        return eng.play_to_completion(progress)
+def _play_lockstep(eng, progress=None):
+    """play_move() until no game of `eng` (LockstepEngine or lockstep SelfPlayLanes, armed by begin_run) is alive; returns the
+    examples."""
     moves = 0
     while eng.n_alive > 0:
         eng.play_move()
@@ -157,76 +74,40 @@ def _play_to_completion(eng, progress=None):
 
 
 # =============================================================================== batched engine
-class SelfPlayEngine:
+class _Engine:
+    """What the lockstep and the free-running engine share: the options, the geometry, the tree context with its reuse
+    defaults resolved, the book, the counters, and run / collect / close."""
+    free_running = False
+
     def __init__(self, game, evaluator, num_simulations=800, concurrent_games=4096, cpuct=1.0,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, temperature_threshold=10,
                  board_semantics="copied", reference_quirks=False, use_graph=True, seed=0,
-                 device=None, first_game_index=0, game_index_stride=1, compact_tail=True, row_tiers=None,
+                 device=None, first_game_index=0, game_index_stride=1,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
-                 opening_book=None, stream=None, rng="philox", numpy_seeds=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, poll_steps=None):
-        """free_running (not in the reference; default off = lockstep moves, today's launches, graphs and games): the games play
-        their moves on the device, inside the search step (csrc/yy_selfplay_move.hip).  A game whose search
-        is complete records its example, draws and plays its move, handles passes and sets up its next root in the same step --
-        or ends, hands its labelled examples to the run's example buffer and lets the run's next game start in its slot --
-        while the other games keep simulating; the host only replays captured steps and, every poll_steps steps (default: four
-        unrolled graphs), enqueues an asynchronous copy of the run's counters, reading the PREVIOUS poll's record.  The games
-        are the lockstep engine's bit for bit (same seed, same game indices: every draw is keyed by (seed, game index, ply)
-        and the evaluator sees a game's rows one by one), given an evaluator whose row results do not depend on the batch;
-        collect() returns them sorted by (game_id, ply).  Evaluation reuse, the opening book and playout cap work as in
-        lockstep; compact_tail / row_tiers do not apply (slots do not move: the compacted evaluator pays for live rows only).
-        play_move() / enqueue_move() raise.  Not with leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" or
-        tree_reuse (ValueError; follow-ups).
+                 opening_book=None, stream=None, rng="philox", leaves_per_step=1,
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse and the mode (free_running): options.SearchOptions;
+        a refused combination raises ValueError before anything touches the device.
         reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
-        declares `row_independent` (the split-f16 evaluator does).  The reference asks the network for every leaf: a node
-        without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move order of the same search
-        already reached (:385-397), a position the previous move's search evaluated -- and gets the same numbers each time.
-        With these options the search takes them from the tree / from a per-game evaluation cache in HBM instead
-        (YY_FLAG_REUSE_PASS_VALUE, YY_FLAG_REUSE_TRANSPOSITIONS, YY_FLAG_KEEP_EVALUATIONS in include/yy_engine.h).  The games
-        played are the same, move for move; the evaluator sees a fraction of the rows.  The engine owns ONE evaluator for its
-        lifetime, which is what keep_evaluations needs.
+        declares `row_independent` (the split-f16 evaluator does); off at leaves_per_step > 1.  The reference asks the network
+        for every leaf: a node without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move
+        order of the same search already reached (:385-397), a position the previous move's search evaluated -- and gets the
+        same numbers each time.  With these options the search takes them from the tree / from a per-game evaluation cache in
+        HBM instead (YY_FLAG_REUSE_PASS_VALUE, YY_FLAG_REUSE_TRANSPOSITIONS, YY_FLAG_KEEP_EVALUATIONS in include/yy_engine.h).
+        The games played are the same, move for move; the evaluator sees a fraction of the rows.  The engine owns ONE evaluator
+        for its lifetime, which is what keep_evaluations needs.
         opening_book: an engine.OpeningBook built with THIS evaluator, or a stone count N to build one here (every position
         reachable with <= N stones is evaluated once, in large batches, before play; all games start from the empty board, so
         the first plies of every game search the same positions), or None.
-        rng: "philox" (default) = the per-game counter streams of csrc/yy_selfplay.hip, drawn on the device; "numpy" = the
-        REFERENCE's generator and call sequence, per game: a host numpy RandomState(numpy_seeds[game index], default seed +
-        index) draws np.random.dirichlet at the game's first search (ai/mcts.py:305) and np.random.choice for every move
-        (ai/self_play.py:146, 160) exactly where SelfPlayWorker.play_game draws from the global stream after np.random.seed(s) --
-        a batch of games then replays the reference's transcripts move for move (tests: episodes_*.npz).  One host round
-        trip of (pi, legal mask) per move: a parity mode, not the throughput path.
-        leaves_per_step K > 1 (default 1 = the reference's search, today's launches and games): every search of the engine is
-        leaf-parallel (engine.BatchedMCTS leaves_per_step): K descents per game and step with virtual visits, their leaves
-        evaluated in one launch of up to K rows per game, ceil(num_simulations / K) steps per move -- for runs with few
-        concurrent games, where a step costs the same whatever it carries.  The move around the search is unchanged (pass
-        handling, root noise, the example record, the draws): it reads the root, and the root holds num_simulations visits at
-        any K.  The None defaults of the three reuse options then mean OFF and no book is built: the leaf-parallel selection
-        (k_mcts_multi) looks nothing up -- no kept pass value, no evaluation cache, no book -- and the tree context refuses the
-        combination at create.  Asking for one of them explicitly, for aliased boards or for reference_quirks together with
-        K > 1 raises ValueError.  It changes which moves a search picks.
-        fast_simulations N with full_search_probability P < 1 (not in the reference; default None / 1.0 = every search runs
-        num_simulations, today's engine and launches): playout-cap randomisation.  Every move draws one uniform per game from
-        the game's own counter stream (yy_selfplay_draw_budgets: keyed by seed, global game index and ply, so not by slot, batch
-        or rank): with probability P the game searches num_simulations, else N, in the same lockstep search (per-game budgets
-        on the device, include/yy_engine.h yy_mcts_set_sim_budgets; the host issues the steps of num_simulations and reads no
-        draw).  Root noise, pi, the temperature rule, the move draw and the z labels are unchanged; only the moves searched in
-        full are recorded as examples (their `ply` is the game's ply).  N outside 1 .. num_simulations or P outside (0, 1]
-        raises ValueError.
-        tree_reuse (not in the reference's search; default off = every move starts from a fresh root, today's games and
-        launches): after the move draw every game's tree is re-rooted at the move played (engine.BatchedMCTS.advance; -1 = keep
-        nothing for the games that did not search or that ended), and the next search continues from that subtree and tops its
-        root up to the move's budget -- num_simulations, or the playout-cap draw.  The host issues the same steps; a game
-        whose kept root already holds part of its budget asks for fewer evaluator rows.  A kept tree belongs to its slot: when
-        the draining batch is packed (compact_tail) every tree is dropped once, so with tree_reuse a game's transcript depends
-        on when that happens.  It changes which moves a search picks.  Not with leaves_per_step > 1 or aliased boards:
-        ValueError."""
+        rng: "philox" (default) = the per-game counter streams of csrc/yy_selfplay.hip, drawn on the device; "numpy"
+        (LockstepEngine) = the reference's generator."""
         assert board_semantics in ("aliased", "copied")
         assert rng in ("philox", "numpy")
-        self.free_running = _free_running(free_running, leaves_per_step, board_semantics, reference_quirks, rng, tree_reuse)
-        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
-        cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
-        self.fast_sims, self.p_full = cap.get("fast_simulations"), cap.get("full_search_probability", 1.0)
-        self.K = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks,
-                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book)
+        opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
+                               (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
+                               full_search_probability, tree_reuse, self.free_running)
+        self.K, self.tree_reuse = opts.leaves_per_step, opts.tree_reuse
+        self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
         self.R, self.C = game.getBoardSize()
         self.A = self.R * self.C
@@ -238,11 +119,8 @@ class SelfPlayEngine:
         self.quirks = bool(reference_quirks)
         self.rowcol = bool(getattr(game, "rowcol_rule", False))
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.evaluator = evaluator
+        self.evaluator, self.use_graph = evaluator, use_graph
         self.stream = stream                       # HIP stream every launch of this engine goes to (None: the caller's current one)
-        self._pending = None                       # a move enqueued by enqueue_move() and not yet finished
-        self._evals_seen = 0                       # tree-context counter at the end of the last move (rows_hint)
-        self._stats_host = None                    # pinned record of the move's one host read, made at the first move
         auto = self.K == 1 and (not self.aliased) and bool(getattr(evaluator, "row_independent", False))
         self.reuse_pass_value, self.reuse_transpositions, self.keep_evaluations = (
             bool(auto if x is None else x) for x in (reuse_pass_value, reuse_transpositions, keep_evaluations))
@@ -253,27 +131,61 @@ class SelfPlayEngine:
         self.book = _opening_book(opening_book, game, evaluator, self.device)
         if self.book is not None:
             self.ctx.set_book(self.book)
-        # free-running: the steps are FreeRunningSearch's (self.free_search, made with the run's device state by begin_run)
-        self.search = None if self.free_running else LockstepSearch(self.ctx, evaluator, use_graph=use_graph)
         self.seed = int(seed)                     # key of the per-game counter streams (csrc/yy_selfplay.hip)
-        assert rng in ("philox", "numpy")
-        self.rng, self.numpy_seeds, self._rs = rng, numpy_seeds, {}
-        self.n_alive = 0                           # live games, tracked on the host (no device read needed)
+        self.rng = rng
         self.first_game_index, self.stride = int(first_game_index), int(game_index_stride)
         # a game has at most A placements; passes never add examples.  Literal quirk mode can make
         # no-op moves (illegal placements), so leave generous room there.
         self.T = self.A + 2 if not self.quirks else 4 * self.A + 8
-        dev, G, T = self.device, self.G, self.T
+        self.n_alive = 0       # live games, tracked on the host (no device read needed)
+        self.positions = 0
+        self.recorded = 0      # examples recorded so far (== positions without playout cap)
+        self.games_started = self.games_finished = self.games_target = 0
         self.steps_issued = 0  # free-running: steps put on the stream so far
-        if self.free_running:
-            # the per-slot games, their histories and the finished examples live in the run's device state (engine.SelfPlayRun),
-            # made by begin_run for the run's game count; the host keeps the counters it read last
-            self.use_graph, self.poll_steps = use_graph, poll_steps
-            self.run_state = self.free_search = self._run_open = self._tick = None
-            self._example_capacity = None      # rows of the example buffer; None: num_games * (A + 2), which always fits
-            self.recorded = self.games_started = self.games_finished = self.games_target = self.positions = 0
-            self.out, self.compact_tail, self.rows = [], False, G
-            return
+        self.out = []          # finished examples: dicts of device tensors (states, policies, values, game_id, ply)
+
+    def _on_stream(self):
+        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+
+    def run(self, num_games, progress=None):
+        """Play `num_games` games to completion; returns the examples (device tensors)."""
+        self.begin_run(num_games)
+        return self.play_to_completion(progress)
+
+    def collect(self):
+        """The examples finished since the last collect(); a free-running engine's sorted by (game_id, ply)."""
+        out, self.out = self.out, []
+        if not out:
+            e = torch.empty
+            return dict(states=e((0, self.R, self.C), dtype=torch.int8, device=self.device),
+                        policies=e((0, self.A), dtype=torch.float32, device=self.device),
+                        values=e((0,), dtype=torch.float32, device=self.device),
+                        game_id=e((0,), dtype=torch.int64, device=self.device),
+                        ply=e((0,), dtype=torch.int64, device=self.device))
+        ex = {k: torch.cat([o[k] for o in out]) for k in out[0]}
+        return sort_examples(ex) if self.free_running else ex
+
+    def close(self):
+        self.ctx.close()
+
+
+class LockstepEngine(_Engine):
+    """G games advance in lockstep: one search and one move of every live game per play_move(), finished games replaced in
+    their slot (the module docstring)."""
+
+    def __init__(self, *args, compact_tail=True, row_tiers=None, numpy_seeds=None, **kwargs):
+        """The other arguments are _Engine's.  rng="numpy" = the REFERENCE's generator and call sequence, per game: a host numpy RandomState(numpy_seeds[game index],
+        default seed + index) draws np.random.dirichlet at the game's first search (ai/mcts.py:305) and np.random.choice for
+        every move (ai/self_play.py:146, 160) exactly where SelfPlayWorker.play_game draws from the global stream after
+        np.random.seed(s) -- a batch of games then replays the reference's transcripts move for move (tests: episodes_*.npz).
+        One host round trip of (pi, legal mask) per move: a parity mode, not the throughput path."""
+        super().__init__(*args, **kwargs)
+        self.search = LockstepSearch(self.ctx, self.evaluator, use_graph=self.use_graph)
+        self.numpy_seeds, self._rs = numpy_seeds, {}
+        self._pending = None                       # a move enqueued by enqueue_move() and not yet finished
+        self._evals_seen = 0                       # tree-context counter at the end of the last move (rows_hint)
+        self._stats_host = None                    # pinned record of the move's one host read, made at the first move
+        dev, G, T = self.device, self.G, self.T
         self.boards = torch.zeros((G, self.R, self.C), dtype=torch.int8, device=dev)
         self.players = torch.ones(G, dtype=torch.int8, device=dev)
         self.ply = torch.zeros(G, dtype=torch.int32, device=dev)
@@ -285,12 +197,6 @@ class SelfPlayEngine:
         self.hist_player = torch.zeros((G, T), dtype=torch.int8, device=dev)
         # playout cap: the examples of a game are its fully searched moves only, so an example's index is not its ply
         self.hist_ply = torch.zeros((G, T), dtype=torch.int64, device=dev) if self.fast_sims is not None else None
-        self.recorded = 0      # examples recorded so far (== positions without playout cap)
-        self.out = []          # finished examples: tuples of device tensors
-        self.games_started = 0
-        self.games_finished = 0
-        self.games_target = 0
-        self.positions = 0
         self._ar = torch.arange(G, device=dev)
         self._ones = torch.ones(G, dtype=torch.int8, device=dev)
         # draining batch: once no new game will start, live games are packed to the front and only the leaf rows of the first
@@ -301,15 +207,8 @@ class SelfPlayEngine:
         self.tiers = sorted({G} | ({m for m in range(1024, G, 1024)} | {m for m in (512, 256) if m < G}
                                    if row_tiers is None else {int(t) for t in row_tiers if 0 < int(t) < G}))
 
-    def _lockstep_only(self, what):
-        """The lockstep move and its per-slot tensors do not exist in a free-running engine: say so, clearly."""
-        if self.free_running:
-            raise RuntimeError(f"free_running=True: the games play their moves on the device, there is no lockstep move "
-                               f"({what}) -- use run() or begin_run() + play_to_completion()")
-
     def _pack_live_games(self):
         """Once per tier change: stable permutation of every per-slot tensor, live games first."""
-        self._lockstep_only("_pack_live_games()")
         perm = torch.argsort((~self.alive).to(torch.int8), stable=True)
         for name in ("boards", "players", "ply", "n_ex", "alive", "game_id", "hist_state", "hist_pi", "hist_player") + (
                 ("hist_ply",) if self.hist_ply is not None else ()):
@@ -317,7 +216,6 @@ class SelfPlayEngine:
 
     # ---- slots
     def _start_games(self, slots):
-        self._lockstep_only("_start_games()")
         n = int(slots.numel())
         if n == 0:
             return
@@ -352,7 +250,8 @@ class SelfPlayEngine:
         gid = self.game_id[idx][:, None].expand(-1, self.T)
         plyi = (torch.arange(self.T, device=self.device)[None, :].expand(idx.numel(), -1) if self.hist_ply is None
                 else self.hist_ply[idx])
-        self.out.append((states[sel], self.hist_pi[idx][sel], z[sel].to(torch.float32), gid[sel], plyi[sel]))
+        self.out.append(dict(states=states[sel], policies=self.hist_pi[idx][sel], values=z[sel].to(torch.float32),
+                             game_id=gid[sel], ply=plyi[sel]))
         self.games_finished += int(idx.numel())
         self.n_alive -= int(idx.numel())
         self.alive[idx] = False
@@ -394,9 +293,6 @@ class SelfPlayEngine:
         action[idx] = torch.from_numpy(out).to(self.device)
         return action
 
-    def _on_stream(self):
-        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
-
     def play_move(self):
         """One lockstep move of every live game: enqueue_move() + finish_move()."""
         self.enqueue_move()
@@ -405,7 +301,6 @@ class SelfPlayEngine:
     def finish_move(self):
         """Waits for the move enqueue_move() put on the engine's stream, reads its one small statistics record (positions
         searched, games finished) and, when games finished, labels their examples and refills their slots."""
-        self._lockstep_only("finish_move()")
         assert self._pending is not None, "finish_move() without enqueue_move()"
         host, event, fin, fin_res, fin_player = self._pending
         self._pending = None
@@ -430,7 +325,6 @@ class SelfPlayEngine:
         per-game counter streams of csrc/yy_selfplay.hip, so a game's noise and moves depend only on (seed, global game index,
         ply).  Between the two calls the host is free to enqueue the moves of other engines on other streams
         (SelfPlayLanes): their kernels fill the compute units this engine's partly empty last round of workgroups leaves idle."""
-        self._lockstep_only("enqueue_move()")
         assert self._pending is None, "enqueue_move() twice without finish_move()"
         with self._on_stream():
             self._enqueue_move()
@@ -535,16 +429,37 @@ class SelfPlayEngine:
 
     def begin_run(self, num_games):
         """Arm the engine for `num_games` more games: the first ones start in the free slots, the others as slots free up."""
-        if self.free_running:
-            return self._begin_free_run(int(num_games))
         with self._on_stream():
             self.games_target = self.games_started + int(num_games)
             free = (~self.alive).nonzero(as_tuple=True)[0]
             self._start_games(free[: int(num_games)])
 
-    # ---- free-running: the games move on the device, the host replays steps and polls the run's counters
-    def _begin_free_run(self, n):
-        """Make (or reuse) the run's device state, sized for n games, and put every slot's first root on the stream."""
+    play_to_completion = _play_lockstep
+
+
+class FreeRunningEngine(_Engine):
+    """The games play their moves on the device, inside the search step (options.SearchOptions free_running); the host replays
+    steps and polls the counters of the run's device state (engine.SelfPlayRun, made by begin_run for the run's game count)."""
+    free_running = True
+
+    def __init__(self, *args, poll_steps=None, compact_tail=None, row_tiers=None, numpy_seeds=None, **kwargs):
+        """poll_steps: steps between two polls of the run's counters (default: four unrolled graphs).  compact_tail, row_tiers and
+        numpy_seeds are the lockstep engine's and do not apply; the other arguments are _Engine's."""
+        super().__init__(*args, **kwargs)
+        self.poll_steps = poll_steps
+        # the steps are FreeRunningSearch's, made with the run's device state by begin_run
+        self.run_state = self.free_search = self._run_open = self._tick = None
+        self._example_capacity = None      # rows of the example buffer; None: num_games * (A + 2), which always fits
+
+    def play_move(self, *args):
+        raise RuntimeError("free_running=True: the games play their moves on the device, there is no lockstep move "
+                           "(play_move / enqueue_move / finish_move) -- use run() or begin_run() + play_to_completion()")
+
+    enqueue_move = finish_move = play_move
+
+    def begin_run(self, num_games):
+        """Make (or reuse) the run's device state, sized for num_games games, and put every slot's first root on the stream."""
+        n = int(num_games)
         if self._run_open is not None:
             raise RuntimeError("begin_run() while a free-running run is in progress: play_to_completion() first")
         cap = max(1, n * (self.A + 2)) if self._example_capacity is None else int(self._example_capacity)
@@ -562,19 +477,17 @@ class SelfPlayEngine:
         self._run_open = n
 
     def play_to_completion(self, progress=None):
-        """Free-running: replay steps on the engine's stream until the run begin_run() armed is over; returns the examples.
-        Every poll_steps steps the counter copy is enqueued with an event and the PREVIOUS poll's record is read, so the host
-        never waits on the stream it is feeding; the run is over when finished + failed == its games.  Raises YYError when a
-        search failed (the other games' examples stay collectable), when the example buffer overflowed, or when the run is not
-        over after free_running_step_bound() steps."""
-        if not self.free_running:
-            return _play_to_completion(self, progress)
-        while not self._free_tick():
+        """Replay steps on the engine's stream until the run begin_run() armed is over; returns the examples.  Every poll_steps
+        steps the counter copy is enqueued with an event and the PREVIOUS poll's record is read, so the host never waits on the
+        stream it is feeding; the run is over when finished + failed == its games.  Raises YYError when a search failed (the
+        other games' examples stay collectable), when the example buffer overflowed, or when the run is not over after
+        free_running_step_bound() steps."""
+        while not self.tick():
             if progress:
                 progress(self)
-        return self._free_finish()
+        return self.finish()
 
-    def _free_tick(self):
+    def tick(self):
         """One batch of poll_steps steps and the poll behind it; reads the previous poll's record.  True: the run is over (or
         there is none)."""
         n = self._run_open
@@ -602,7 +515,7 @@ class SelfPlayEngine:
                               f"(bound {t['bound']}): something is wrong")
         return False
 
-    def _free_finish(self):
+    def finish(self):
         """The run is over: its final counters, its examples; raises for failed searches and an overflowed example buffer."""
         n, t, run = self._run_open, self._tick, self.run_state
         self._run_open, self._tick, self.n_alive = None, None, 0
@@ -629,30 +542,17 @@ class SelfPlayEngine:
         self.ctx.status()
         return self.collect()
 
-    def run(self, num_games, progress=None):
-        """Play `num_games` games to completion; returns the examples (device tensors)."""
-        self.begin_run(num_games)
-        return _play_to_completion(self, progress)
-
-    def collect(self):
-        out, self.out = self.out, []
-        if out and self.free_running:
-            return sort_examples({k: torch.cat([o[k] for o in out]) for k in out[0]})
-        if not out:
-            e = torch.empty
-            return dict(states=e((0, self.R, self.C), dtype=torch.int8, device=self.device),
-                        policies=e((0, self.A), dtype=torch.float32, device=self.device),
-                        values=e((0,), dtype=torch.float32, device=self.device),
-                        game_id=e((0,), dtype=torch.int64, device=self.device),
-                        ply=e((0,), dtype=torch.int64, device=self.device))
-        cat = [torch.cat([o[i] for o in out]) for i in range(5)]
-        return dict(states=cat[0], policies=cat[1], values=cat[2], game_id=cat[3], ply=cat[4])
-
     def close(self):
-        if getattr(self, "run_state", None) is not None:
+        if self.run_state is not None:
             self.run_state.close()                 # before the context its kernels read
             self.run_state = self.free_search = None
-        self.ctx.close()
+        super().close()
+
+
+def SelfPlayEngine(game, evaluator, *args, free_running=False, **kwargs):
+    """The engine of one batch of games on one GPU: FreeRunningEngine with free_running=True, else LockstepEngine; the other
+    arguments are the class's."""
+    return (FreeRunningEngine if free_running else LockstepEngine)(game, evaluator, *args, **kwargs)
 
 
 class _LaneCounters:
@@ -687,22 +587,19 @@ class SelfPlayLanes:
     Lane k of K plays the games first_game_index + (k + j*K) * game_index_stride, j = 0, 1, ..."""
 
     def __init__(self, game, evaluator, num_simulations=800, concurrent_games=4096, lanes=2, seed=0, device=None,
-                 first_game_index=0, game_index_stride=1, opening_book=None, leaves_per_step=1, fast_simulations=None,
-                 full_search_probability=1.0, **engine_kwargs):
-        """leaves_per_step: every lane's searches are leaf-parallel (SelfPlayEngine leaves_per_step; same defaults, same
-        refusals, raised here before the book or any lane is built).  tree_reuse=True (a SelfPlayEngine keyword): likewise.  fast_simulations / full_search_probability: playout-cap
-        randomisation in every lane (SelfPlayEngine's; checked here first).  free_running=True (a SelfPlayEngine keyword; checked
-        here first): every lane runs free on its own stream and the host alternates the lanes' batches of graph replays.  The
-        other keywords are SelfPlayEngine's."""
-        cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
-        self.free_running = _free_running(engine_kwargs.get("free_running", False), leaves_per_step,
-                                          engine_kwargs.get("board_semantics", "copied"), engine_kwargs.get("reference_quirks", False),
-                                          engine_kwargs.get("rng", "philox"), engine_kwargs.get("tree_reuse", False))
-        _tree_reuse(engine_kwargs.get("tree_reuse", False), leaves_per_step, engine_kwargs.get("board_semantics", "copied"))
-        self.leaves_per_step = _leaf_parallel(leaves_per_step, engine_kwargs.get("board_semantics", "copied"),
-                                              engine_kwargs.get("reference_quirks", False),
-                                              [engine_kwargs.get(k) for k in ("reuse_pass_value", "reuse_transpositions", "keep_evaluations")],
-                                              opening_book)
+                 first_game_index=0, game_index_stride=1, opening_book=None, board_semantics="copied", reference_quirks=False,
+                 reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, **engine_kwargs):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions, in every
+        lane; resolved here once, before the book or any lane is built.  Free-running lanes each run on their own stream and
+        the host alternates their batches of graph replays.  The other keywords are SelfPlayEngine's."""
+        opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
+                               (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
+                               full_search_probability, tree_reuse, free_running)
+        self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
+        engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
+                             reuse_pass_value=reuse_pass_value, reuse_transpositions=reuse_transpositions,
+                             keep_evaluations=keep_evaluations, **opts.keywords())
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         K = max(1, min(int(lanes), int(concurrent_games)))
         self.game, self.evaluator, self.sims = game, evaluator, int(num_simulations)
@@ -718,7 +615,7 @@ class SelfPlayLanes:
                 self.lanes.append(SelfPlayEngine(game, evaluator, num_simulations=num_simulations, concurrent_games=g_k, seed=seed,
                                                  device=self.device, first_game_index=first_game_index + k * game_index_stride,
                                                  game_index_stride=K * game_index_stride, opening_book=self.book, stream=st,
-                                                 leaves_per_step=self.leaves_per_step, **cap, **engine_kwargs))
+                                                 **engine_kwargs))
         torch.cuda.synchronize(self.device)      # evaluator weights / the book were written on the caller's stream
         ln = self.lanes[0]
         self.G = sum(l.G for l in self.lanes)
@@ -737,16 +634,16 @@ class SelfPlayLanes:
         alternate on their streams; a lane whose run is over drops out.  Then every lane's run is closed: the first error is
         raised after all lanes have handed over their examples."""
         if not self.free_running:
-            return _play_to_completion(self, progress)
+            return _play_lockstep(self, progress)
         live = list(self.lanes)
         while live:
-            live = [l for l in live if not l._free_tick()]
+            live = [l for l in live if not l.tick()]
             if progress:
                 progress(self)
         parts, err = [], None
         for l in self.lanes:
             try:
-                parts.append(l._free_finish())
+                parts.append(l.finish())
             except YYError as e:
                 err = err or e
                 parts.append(l.collect())
@@ -772,7 +669,7 @@ class SelfPlayLanes:
         K = len(self.lanes)
         for k, l in enumerate(self.lanes):
             l.begin_run(shard_games(int(num_games), k, K)[0])
-        return _play_to_completion(self, progress)
+        return self.play_to_completion(progress)
 
     def collect(self):
         torch.cuda.synchronize(self.device)
@@ -894,22 +791,16 @@ class SelfPlayWorker:
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False):
-        """free_running: refused (ValueError).  This class plays ONE game at a time through MCTS, drawing from numpy's global
-        stream: there is no batch whose games could be freed from each other; the mode is SelfPlayEngine's.
-        leaves_per_step K > 1 (not in the reference): leaf-parallel searches (MCTS leaves_per_step); needs
-        board_semantics="copied" and reference_quirks=False, which are not this class's defaults.
-        fast_simulations N with full_search_probability P < 1 (not in the reference): playout-cap randomisation -- before every
-        search one np.random.random() from the global stream decides between num_simulations (probability P; the move is
-        recorded) and N simulations (not recorded).  Off (the defaults) draws nothing.
-        tree_reuse=True (not in the reference's search): play_game hands the root and the move played to MCTS.reuse_tree, as
-        the reference does at self_play.py:192, and the next search continues from that subtree (MCTS tree_reuse); needs
-        board_semantics="copied"."""
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse: options.SearchOptions, through MCTS; K > 1 and
+        tree_reuse need board_semantics="copied", K > 1 also reference_quirks=False, which are not this class's defaults.
+        free_running: refused (ValueError).  This class plays ONE game at a time through MCTS, drawing from numpy's global
+        stream: there is no batch whose games could be freed from each other; the mode is SelfPlayEngine's."""
         if free_running:
             raise ValueError("free_running=True: SelfPlayWorker plays one game at a time through MCTS (numpy's global stream): "
                              "there is no batch to free -- use SelfPlayEngine / SelfPlayManager")
-        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
-        self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks)
-        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+        opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, fast_simulations=fast_simulations,
+                               full_search_probability=full_search_probability, tree_reuse=tree_reuse)
+        self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
         self.temperature_threshold = temperature_threshold
@@ -1009,19 +900,13 @@ class SelfPlayManager:
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False):
-        """free_running: the rank's games play their moves on the device (SelfPlayEngine free_running; checked here).
-        fast_simulations / full_search_probability: playout-cap randomisation (SelfPlayEngine's; checked here).
-        tree_reuse: every search continues from the subtree under the move played (SelfPlayEngine's; checked here).
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions.
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
-        per-game evaluation cache, SelfPlayEngine); False = the network is asked for every leaf like the reference.
-        leaves_per_step K > 1: leaf-parallel searches (SelfPlayEngine leaves_per_step); evaluation_reuse=None then means off and
-        opening_book_stones=None no book; evaluation_reuse=True, a book, aliased boards or reference_quirks with it raise
-        ValueError here."""
-        self.leaves_per_step = _leaf_parallel(leaves_per_step, board_semantics, reference_quirks, (evaluation_reuse,),
-                                              opening_book_stones)
-        self.playout_cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
-        self.tree_reuse = _tree_reuse(tree_reuse, leaves_per_step, board_semantics)
-        self.free_running = _free_running(free_running, leaves_per_step, board_semantics, reference_quirks, "philox", tree_reuse)
+        per-game evaluation cache, SelfPlayEngine; off at leaves_per_step > 1, where opening_book_stones=None also means no
+        book); False = the network is asked for every leaf like the reference."""
+        self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
+                                       (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
+                                       tree_reuse, free_running)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -1050,21 +935,19 @@ class SelfPlayManager:
         evaluator = BatchedEvaluator(net, self.nn_mode)
         book = self.opening_book_stones
         if book is None:
-            auto = (self.leaves_per_step == 1 and self.evaluation_reuse is not False and self.board_semantics == "copied" and mine >= 1024
+            auto = (self.options.leaves_per_step == 1 and self.evaluation_reuse is not False and self.board_semantics == "copied" and mine >= 1024
                     and self.game.getActionSize() <= 64 and getattr(evaluator, "row_independent", False))
             book = 8 if auto else 0
         slots = max(1, min(self.concurrent_games, mine))
         eng = SelfPlayLanes(self.game, evaluator, num_simulations=self.num_simulations, opening_book=int(book),
-                            lanes=self.lanes if self.lanes else (2 if slots >= 512 else 1), leaves_per_step=self.leaves_per_step,
+                            lanes=self.lanes if self.lanes else (2 if slots >= 512 else 1),
                              concurrent_games=slots, cpuct=self.cpuct,
                              dirichlet_alpha=self.dirichlet_alpha, dirichlet_epsilon=self.dirichlet_epsilon,
                              temperature_threshold=self.temperature_threshold, board_semantics=self.board_semantics,
                              reference_quirks=self.reference_quirks, seed=1000 + self.seed,   # key of the per-game streams: the same on every rank
                              first_game_index=first, game_index_stride=stride, device=dev,
                              reuse_pass_value=self.evaluation_reuse, reuse_transpositions=self.evaluation_reuse,
-                             keep_evaluations=self.evaluation_reuse, **self.playout_cap,
-                             **(dict(tree_reuse=True) if self.tree_reuse else {}),
-                             **(dict(free_running=True) if self.free_running else {}))
+                             keep_evaluations=self.evaluation_reuse, **self.options.keywords())
         t0 = time.perf_counter()
         ex = eng.run(mine) if mine > 0 else eng.collect()
         torch.cuda.synchronize(dev)
@@ -1072,7 +955,7 @@ class SelfPlayManager:
         counters = eng.ctx.status()
         ex = gather_examples(ex, capacity=example_capacity(total, world, eng.T))
         self.stats = dict(seconds=t1 - t0, positions=eng.positions, games=eng.games_finished, **counters,
-                          **(dict(steps_issued=eng.steps_issued) if self.free_running else {}))
+                          **(dict(steps_issued=eng.steps_issued) if self.options.free_running else {}))
         eng.close()
         return ex
 
@@ -1084,13 +967,14 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     tensors (`states` int8 [N,R,C], `policies` float64 [N,A], `values` float64 [N]; `boards` is an
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
-    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's; the other keywords (tree_reuse and
-    free_running among them) are SelfPlayManager's too."""
-    cap = _playout_cap(num_simulations, fast_simulations, full_search_probability)
+    leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
+    the other keywords (tree_reuse and free_running among them) are SelfPlayManager's too."""
+    opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
+                           full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
     games_per_worker = max(1, num_games // num_workers)               # :355 (remainder dropped)
     manager = SelfPlayManager(game, model_path, num_workers=num_workers, games_per_worker=games_per_worker,
-                              num_simulations=num_simulations, leaves_per_step=leaves_per_step, **cap, **engine_kwargs)
+                              num_simulations=num_simulations, **opts.keywords(), **engine_kwargs)
     ex = manager.generate_games_parallel()
     filename = publish_examples_file(ex, output_dir, reference_format)
     generate_self_play_data.last_stats = manager.stats
