@@ -71,6 +71,23 @@ extern "C" {
                               then positions that cannot recur (no more stones than the root).  REQUIRES that every
                               search of the context uses the same evaluator: call yy_mcts_cache_clear when it changes. */
 
+#define YY_FLAG_EVAL_SYMMETRY 32u /* symmetry-randomised evaluation (not in the reference; copied boards only: create refuses it
+                              with YY_FLAG_ALIASED).  Every position (black, white) is shown to the evaluator under a board symmetry
+                              s = sym(symmetry_seed, black, white) drawn from the project's Philox streams: a pure function of
+                              the seed and the position -- not of slot, game, ply, simulation, batch or rank -- so the evaluation
+                              cache, the book and "a row's result does not depend on its batch" stay true.  Keying: Philox4x32-10
+                              with the key symmetry_seed ^ 0x59595F53594D5F34 (the domain tag: every other stream keys with its
+                              seed itself), the NW 64-bit word pairs chained: block i has the counter (black[i] lo, black[i] hi,
+                              white[i] lo, white[i] hi) ^ the output of block i - 1 (zero for i = 0); s = the top 3 (square
+                              boards) or 2 bits of the last block's first word.  Square boards, s in 0 .. 7: np.rot90(board,
+                              s & 3), then np.fliplr when s & 4; other boards, s in 0 .. 3: np.flipud when s & 1, np.fliplr when
+                              s & 2.  The row written for the position (yy_mcts_begin, select, step) is planes(T_s(board)), all
+                              five planes encoded from the transformed board; the prior of action a is policy[T_s(a)], T_s(a) =
+                              where cell a lands; the value is used as is.  Noise, the NaN rule, edge order, cache keys and every
+                              read-out stay in the original frame; the cache and the book hold rows as the evaluator returned
+                              them and are read through the same map (a book must be built with yy_encode_planes_sym and the
+                              same seed).  Flag clear: every kernel does what it did without it. */
+
 typedef void *yy_stream_t;
 
 const char *yy_last_error(void);
@@ -98,6 +115,12 @@ int yy_rules_game_ended(const int8_t *boards, const int8_t *players, int G, int 
 /* YinYangNeuralNetwork.board_to_input(board)  (ai/neural_network.py:156-196):
  * out float32 [G,5,R,C] = [empty, black, white, row fill, column fill]. */
 int yy_encode_planes(const int8_t *boards, int G, int R, int C, float *out, yy_stream_t stream);
+
+/* Symmetry-randomised evaluation (YY_FLAG_EVAL_SYMMETRY): yy_encode_planes of every board under the symmetry drawn for it
+ * from `seed` -- the row a context created with that symmetry_seed writes for the position (for the book's builder) -- and
+ * the drawn symmetry itself, out int8 [G] (0 .. 7 on square boards, 0 .. 3 on others). */
+int yy_encode_planes_sym(const int8_t *boards, int G, int R, int C, uint64_t seed, float *out, yy_stream_t stream);
+int yy_eval_symmetry(const int8_t *boards, int G, int R, int C, uint64_t seed, int8_t *out, yy_stream_t stream);
 
 /* Native packed form of the same rules: one game per lane on bitboards.
  * black/white: uint64 [NW][G] (word-major SoA, NW = ceil(R*C/64), bit a = cell a);
@@ -132,6 +155,7 @@ typedef struct yy_mcts_config {
     int32_t leaves_per_step;   /* K: descents per game per step (leaf parallelism with virtual visits); 0 and 1 = one,
                                   the reference's search.  1 < K <= 64 needs copied boards and no YY_FLAG_REUSE_* /
                                   YY_FLAG_KEEP_EVALUATIONS (create returns YY_E_UNSUPPORTED) and no book.  See below. */
+    uint64_t symmetry_seed;    /* YY_FLAG_EVAL_SYMMETRY: the seed of the symmetry draw; ignored without the flag */
 } yy_mcts_config;
 
 /* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after

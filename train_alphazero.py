@@ -7,7 +7,8 @@
 
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
---dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability.  `--mode train` runs
+--dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability, --tree-reuse, --free-running,
+--evaluation-symmetry, --symmetry-seed.  `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
 """
@@ -87,13 +88,20 @@ def parse_args(argv=None):
                    help="self-play and train: the games play their moves on the device, inside the search step, each as soon as its "
                         "own search is complete, instead of in lockstep (default off; the same games; not with --leaves-per-step "
                         "> 1, --board-semantics aliased, --reference-quirks or --tree-reuse)")
+    p.add_argument("--evaluation-symmetry", choices=["off", "random"], default="off",
+                   help="self-play and train: random = every position is shown to the network under a board symmetry drawn for it "
+                        "(a pure function of --symmetry-seed and the position) and the policy is mapped back (default off; changes "
+                        "which moves are picked; not with --board-semantics aliased or --reference-quirks)")
+    p.add_argument("--symmetry-seed", type=int, default=None,
+                   help="seed of the symmetry draw of --evaluation-symmetry random (default: the engine's seed)")
     return p.parse_args(argv)
 
 
 # What each mode hands to the options resolver (the package's options.resolve: the one copy of the rules), one call per tuple.
 # train's self-play always runs on copied boards without the quirks, so --tree-reuse and --free-running do not look at those two
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
-_SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running")
+_SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
+           "evaluation_symmetry")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse")]}
@@ -158,7 +166,8 @@ def main(argv=None):
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
                            lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
                            fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
-                           tree_reuse=args.tree_reuse, free_running=args.free_running)
+                           tree_reuse=args.tree_reuse, free_running=args.free_running,
+                           evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -187,7 +196,8 @@ def main(argv=None):
                                        lanes=args.lanes or None, leaves_per_step=args.leaves_per_step,
                                        fast_simulations=args.fast_simulations,
                                        full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse,
-                                       free_running=args.free_running)
+                                       free_running=args.free_running, evaluation_symmetry=args.evaluation_symmetry,
+                                       symmetry_seed=args.symmetry_seed)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

@@ -16,6 +16,7 @@ FLAG_ALIASED = 2
 FLAG_REUSE_PASS_VALUE = 4
 FLAG_REUSE_TRANSPOSITIONS = 8
 FLAG_KEEP_EVALUATIONS = 16
+FLAG_EVAL_SYMMETRY = 32
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -30,7 +31,7 @@ class YYError(RuntimeError):
 class MctsConfig(C.Structure):
     _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_sims", C.c_int32),
                 ("cpuct", C.c_float), ("flags", C.c_uint32), ("edges_per_game", C.c_int64),
-                ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32)]
+                ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32), ("symmetry_seed", C.c_uint64)]
 
 
 class SelfPlayConfig(C.Structure):
@@ -70,6 +71,8 @@ _SIGS = {
     "yy_rules_step": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp],
     "yy_rules_game_ended": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp],
     "yy_encode_planes": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "yy_encode_planes_sym": [_vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, _vp],
+    "yy_eval_symmetry": [_vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, _vp],
     "yy_rules_mask_terminal_bb": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp],
     "yy_pack_boards": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "yy_unpack_boards": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],

@@ -320,13 +320,16 @@ class AlphaZero:
                  num_simulations=800, num_epochs=10, temperature_threshold=10, update_threshold=0.6, num_workers=1,
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
-                 full_search_probability=1.0, tree_reuse=False, free_running=False):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions, for the
-        loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also for its arena, which always searches
-        num_simulations and plays in lockstep."""
+                 full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
+                 symmetry_seed=None):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry /
+        symmetry_seed: options.SearchOptions, for the loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also
+        for its arena, which always searches num_simulations, plays in lockstep and shows every position to the network in
+        its one orientation (evaluation_symmetry is a self-play option)."""
         self.options = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                                        full_search_probability=full_search_probability, tree_reuse=tree_reuse,
-                                       free_running=free_running)
+                                       free_running=free_running, evaluation_symmetry=evaluation_symmetry,
+                                       symmetry_seed=symmetry_seed)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold

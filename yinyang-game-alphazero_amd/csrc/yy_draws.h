@@ -1,7 +1,8 @@
 // yy_draws.h -- the random draws of the episode loop, one copy: the counter streams and the three draws built on them.  The
 // batch kernels of yy_selfplay.hip (k_root_noise, k_sample_actions, k_draw_budgets) and the in-step move kernel of
 // yy_selfplay_move.hip apply these very functions, so a game's noise, moves and budgets do not depend on which of them drew.
-// Every draw is a pure function of (seed, global game index, ply, purpose, element) through Philox4x32-10 (see yy_selfplay.hip).
+// Every draw is a pure function of (seed, global game index, ply, purpose, element) through Philox4x32-10 (see yy_selfplay.hip);
+// the evaluation symmetry of a position (draw_symmetry, used by the tree kernels through yy_tree.h) one of (seed, position).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,6 +171,24 @@ __device__ __forceinline__ int pick_action(uint64_t seed, int64_t gid, int ply, 
 __device__ __forceinline__ bool draw_full_search(uint64_t seed, int64_t gid, int ply, double p_full) {
     const U4 r = draw(seed, gid, ply, 3, 0u);
     return u01(r.x, r.y) < p_full;
+}
+
+// symmetry-randomised evaluation: the symmetry a POSITION is evaluated under, a pure function of (seed, black, white) -- not
+// of game, ply, slot or batch.  The four counter words of every block are taken by the position, so the domain tag sits in the
+// key: seed ^ SYM_TAG, where every other stream keys with the seed itself.  The NW word pairs are chained: block i has the
+// counter (black[i] lo, black[i] hi, white[i] lo, white[i] hi) ^ the output of block i - 1 (zero for i = 0).  The draw is
+// the top bits of the last block's first word: uniform over `group` = 8 (square boards) or 4 elements.
+#define YY_SYM_TAG 0x59595F53594D5F34ull   // "YY_SYM_4": purposes 0 .. 3 are the streams above
+__host__ __device__ __forceinline__ int symmetry_group(int R, int C) { return R == C ? 8 : 4; }
+__device__ __forceinline__ int draw_symmetry(uint64_t seed, const uint64_t *black, const uint64_t *white, int nw, int group) {
+    const uint64_t key = seed ^ YY_SYM_TAG;
+    U4 h = {0u, 0u, 0u, 0u};
+    for (int i = 0; i < nw; i++) {
+        const U4 c = {h.x ^ (uint32_t)black[i], h.y ^ (uint32_t)(black[i] >> 32), h.z ^ (uint32_t)white[i],
+                      h.w ^ (uint32_t)(white[i] >> 32)};
+        h = philox(c, (uint32_t)key, (uint32_t)(key >> 32));
+    }
+    return (int)(h.x >> (group == 8 ? 29 : 30));
 }
 
 }   // namespace sp

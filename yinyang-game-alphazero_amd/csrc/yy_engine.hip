@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 104
+#define YY_VERSION 105
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -190,6 +190,18 @@ __global__ void __launch_bounds__(64) k_encode(const int8_t *boards, int G, YYGe
     write_planes<NW>(out + (size_t)g * 5 * geo.A, geo, black, white);
 }
 
+// k_encode under symmetry-randomised evaluation: the row the tree kernels write for this position (write_eval_planes) and / or
+// the symmetry it was drawn (either output may be null)
+template <int NW>
+__global__ void __launch_bounds__(64) k_encode_sym(const int8_t *boards, int G, YYGeo geo, uint64_t seed, float *out,
+                                                   int8_t *sym_out) {
+    const int g = blockIdx.x;
+    BB<NW> black, white;
+    board_to_bb<NW>(boards + (size_t)g * geo.A, geo.A, black, white);
+    if (sym_out && lane_id() == 0) sym_out[g] = (int8_t)sym_of<NW>(geo, seed, black, white);
+    if (out) write_eval_planes<NW>(out + (size_t)g * 5 * geo.A, geo, 1u, seed, black, white);
+}
+
 template <int NW>
 __global__ void __launch_bounds__(64) k_pack(const int8_t *boards, int G, YYGeo geo, uint64_t *black, uint64_t *white) {
     const int g = blockIdx.x;
@@ -298,6 +310,25 @@ extern "C" int yy_encode_planes(const int8_t *boards, int G, int R, int C, float
     DISPATCH_NW(geo.NW, k_encode<NW><<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(boards, G, geo, out));
     HIP_TRY(hipGetLastError());
     return YY_OK;
+}
+
+static int encode_sym(const int8_t *boards, int G, int R, int C, uint64_t seed, float *out, int8_t *sym_out, yy_stream_t s) {
+    if (G == 0) return YY_OK;
+    if (int e = check_geo(G, R, C)) return e;
+    if (!boards || (!out && !sym_out)) return set_err(YY_E_INVALID, "null pointer%s%s");
+    YYGeo geo;
+    yy_make_geo(&geo, R, C, 0);
+    DISPATCH_NW(geo.NW, k_encode_sym<NW><<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(boards, G, geo, seed, out, sym_out));
+    HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
+extern "C" int yy_encode_planes_sym(const int8_t *boards, int G, int R, int C, uint64_t seed, float *out, yy_stream_t s) {
+    return encode_sym(boards, G, R, C, seed, out, nullptr, s);
+}
+
+extern "C" int yy_eval_symmetry(const int8_t *boards, int G, int R, int C, uint64_t seed, int8_t *out, yy_stream_t s) {
+    return encode_sym(boards, G, R, C, seed, nullptr, out, s);
 }
 
 extern "C" int yy_pack_boards(const int8_t *boards, int G, int R, int C, uint64_t *black, uint64_t *white,
@@ -577,11 +608,23 @@ __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, con
         }
         int base = n_edges;
         bool bad = false;   // a NaN prior (python: `score > best` is never true for it, select_child returns None and the game raises)
+        // symmetry-randomised evaluation: prow (the evaluator's, a cache's or the book's row) is in the frame of the position
+        // under its drawn symmetry, where action `cell` sits at sym_cell(s, cell); everything below stays in the original frame
+        int s = 0;
+        if (d.sym) {                                                            // wave-uniform
+            BB<NW> lb, lw;
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                lb.w[i] = rfl64(rec->board[i]);
+                lw.w[i] = rfl64(rec->board[NW + i]);
+            }
+            s = sym_of<NW>(d.geo, d.sym_seed, lb, lw);
+        }
 #pragma unroll
         for (int j = 0; j < NW; j++) {
             const int cell = j * 64 + lane;
             if ((mask.w[j] >> lane) & 1) {
-                float p = prow[cell];
+                float p = prow[d.sym ? sym_cell(d.geo, s, cell) : cell];
                 bad |= (p != p);
                 if (mix) {                                                      // mcts.py:310-312
                     const float kp = __fmul_rn(keep, p);
@@ -782,7 +825,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
         int slot;
         const int src = leaf_lookup<NW>(d, st, g, black, white, slot);
-        if (src == SRC_NONE) write_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, black, white);
+        if (src == SRC_NONE) write_eval_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, d.sym, d.sym_seed, black, white);
         leaf_store<NW>(&st->leaf, black, white, mask, lplayer, term, tv);
         if (lane == 0) {
             st->leaf_src = src;
@@ -971,7 +1014,7 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
             bool term;
             float tv;
             leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
-            write_planes<NW>(planes + ((size_t)g * K + j) * 5 * d.geo.A, d.geo, black, white);
+            write_eval_planes<NW>(planes + ((size_t)g * K + j) * 5 * d.geo.A, d.geo, d.sym, d.sym_seed, black, white);
             leaf_store<NW>(rec, black, white, mask, lplayer, term, tv);
         }
         if (lane == 0) {
@@ -1256,6 +1299,8 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     if (cfg->max_sims < 1) return set_err(YY_E_INVALID, "max_sims < 1%s%s");
     if ((cfg->flags & YY_FLAG_REUSE_PASS_VALUE) && (cfg->flags & YY_FLAG_ALIASED))
         return set_err(YY_E_INVALID, "YY_FLAG_REUSE_PASS_VALUE needs copied boards: with the aliased board a node's position changes between visits%s%s");
+    if ((cfg->flags & YY_FLAG_EVAL_SYMMETRY) && (cfg->flags & YY_FLAG_ALIASED))
+        return set_err(YY_E_UNSUPPORTED, "YY_FLAG_EVAL_SYMMETRY needs copied boards (YY_FLAG_ALIASED reproduces the reference, which has no such option)%s%s");
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
     if (cfg->leaves_per_step > 1) {
@@ -1276,7 +1321,9 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.reuse = (cfg->flags & YY_FLAG_REUSE_PASS_VALUE) ? 1u : 0u;
     d.ec_keep = (cfg->flags & YY_FLAG_KEEP_EVALUATIONS) ? 1u : 0u;
     d.cpuct = cfg->cpuct;
-    m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
+    d.sym = (cfg->flags & YY_FLAG_EVAL_SYMMETRY) ? 1u : 0u;
+    d.sym_seed = d.sym ? cfg->symmetry_seed : 0ull;
+    m.K =cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
     yy_make_geo(&d.geo, cfg->R, cfg->C, cfg->flags & YY_FLAG_ROWCOL);

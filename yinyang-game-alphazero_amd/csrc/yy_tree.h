@@ -8,6 +8,7 @@
 
 #include "../../include/yy_engine.h"
 #include "yy_bitboard.h"
+#include "yy_draws.h"
 
 // ------------------------------------------------------------------------------------ helpers
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -96,6 +97,62 @@ __device__ __forceinline__ void write_planes(float *out, const YYGeo &geo, BB<NW
             out[4 * A + cell] = geo.colfill[colk];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------ symmetry-randomised evaluation
+// Board symmetries by number s.  Square boards, s in 0 .. 7: np.rot90(board, s & 3) (counter-clockwise), then np.fliplr when
+// s & 4.  Other boards, s in 0 .. 3: np.flipud when s & 1, np.fliplr when s & 2.  sym_apply maps a cell forwards (where it
+// lands on the transformed board) or backwards (the cell of the original board that lands here).
+__device__ __forceinline__ int sym_apply(const YYGeo &geo, const int s, const int cell, const bool inverse) {
+    const int R = geo.R, C = geo.C;
+    int r = cell / C, c = cell - r * C;
+    if (R != C) {                                  // two commuting flips: the map is its own inverse
+        if (s & 1) r = R - 1 - r;
+        if (s & 2) c = C - 1 - c;
+    } else {
+        const int n1 = C - 1;
+        int k = s & 3;
+        if (inverse) {                             // undo the flip, then turn the remaining 4 - k quarters
+            if (s & 4) c = n1 - c;
+            k = (4 - k) & 3;
+        }
+        const int r0 = r, c0 = c;                  // one quarter turn: (r, c) -> (n - 1 - c, r)
+        r = (k == 0) ? r0 : (k == 1) ? n1 - c0 : (k == 2) ? n1 - r0 : c0;
+        c = (k == 0) ? c0 : (k == 1) ? r0 : (k == 2) ? n1 - c0 : n1 - r0;
+        if (!inverse && (s & 4)) c = n1 - c;
+    }
+    return r * C + c;
+}
+// where cell `cell` lands under symmetry s: the entry of the transformed frame's policy row that is this action's prior
+__device__ __forceinline__ int sym_cell(const YYGeo &geo, const int s, const int cell) { return sym_apply(geo, s, cell, false); }
+
+// the symmetry the position (black, white) is evaluated under (yy_draws.h): wave-uniform
+template <int NW> __device__ __forceinline__ int sym_of(const YYGeo &geo, const uint64_t seed, BB<NW> black, BB<NW> white) {
+    return sp::draw_symmetry(seed, black.w, white.w, NW, sp::symmetry_group(geo.R, geo.C));
+}
+
+// wave-cooperative: the position under symmetry s.  Lane = destination cell; it tests the bit of the cell that lands there, and
+// one ballot per word and colour rebuilds the uniform words.  Every lane of the wavefront must call it.
+template <int NW> __device__ __forceinline__ void bb_symmetry(const YYGeo &geo, BB<NW> &black, BB<NW> &white, const int s) {
+    BB<NW> nb, nw;
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const int cell = j * 64 + lane_id();
+        const bool on = cell < geo.A;
+        const int src = on ? sym_apply(geo, s, cell, true) : 0;
+        nb.w[j] = __ballot(on && bb_test(black, src));
+        nw.w[j] = __ballot(on && bb_test(white, src));
+    }
+    black = nb;
+    white = nw;
+}
+
+// the evaluator row of a position: its planes, with `sym` those of the position under its drawn symmetry
+template <int NW>
+__device__ __forceinline__ void write_eval_planes(float *out, const YYGeo &geo, const uint32_t sym, const uint64_t seed,
+                                                  BB<NW> black, BB<NW> white) {
+    if (sym) bb_symmetry<NW>(geo, black, white, sym_of<NW>(geo, seed, black, white));   // wave-uniform branch
+    write_planes<NW>(out, geo, black, white);
 }
 
 // ------------------------------------------------------------------------------------ rules, one copy
@@ -201,6 +258,10 @@ struct MctsDev {
     GameState *state;
     float *sqrt_tab;
     int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
+    // symmetry-randomised evaluation (YY_FLAG_EVAL_SYMMETRY): a position's row is written under sym_of(position) and its policy
+    // row read through sym_cell; 0: off, every kernel does what it did without it
+    uint32_t sym;
+    uint64_t sym_seed;
 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
@@ -315,7 +376,7 @@ __device__ __forceinline__ void root_setup(const MctsDev &d, GameState *st, Leaf
             leaf_rules<NW>(d.geo, gb, black, white, player, mask, term, tv);
             leaf_store<NW>(rec, black, white, mask, player, term, tv);
         }
-        write_planes<NW>(planes_row, d.geo, black, white);
+        write_eval_planes<NW>(planes_row, d.geo, d.sym, d.sym_seed, black, white);
     }
 }
 

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FLAG_ALIASED, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -72,15 +72,45 @@ def game_ended(boards, players, rowcol=False, with_counts=False):
     return (out, counts) if with_counts else out
 
 
-def encode_planes(boards, out=None):
-    """board_to_input for a batch (neural_network.py:156-196): float32 [G,5,R,C]."""
+def _u64(seed):
+    return ct.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def symmetry_key(mode, seed):
+    """(mode, seed) of symmetry-randomised evaluation as contexts and books compare it: ("off", None), or ("random", seed
+    as the device sees it).  ValueError for another mode."""
+    if mode not in ("off", "random"):
+        raise ValueError(f'evaluation_symmetry={mode!r}: "off" or "random"')
+    return ("off", None) if mode == "off" else ("random", int(0 if seed is None else seed) & (2 ** 64 - 1))
+
+
+def encode_planes(boards, out=None, symmetry_seed=None):
+    """board_to_input for a batch (neural_network.py:156-196): float32 [G,5,R,C].  symmetry_seed (not None): every board is
+    encoded under the symmetry drawn for it from that seed (evaluation_symmetry below): the evaluator row a
+    BatchedMCTS(evaluation_symmetry="random", symmetry_seed=...) writes for the position."""
     G, R, Cc = boards.shape
     _need(boards, torch.int8, name="boards")
     if out is None:
         out = torch.empty((G, 5, R, Cc), dtype=torch.float32, device=boards.device)
     _need(out, torch.float32, (G, 5, R, Cc), "out")
     with torch.cuda.device(boards.device):
-        check(lib().yy_encode_planes(_p(boards), G, R, Cc, _p(out), _stream()))
+        if symmetry_seed is None:
+            check(lib().yy_encode_planes(_p(boards), G, R, Cc, _p(out), _stream()))
+        else:
+            check(lib().yy_encode_planes_sym(_p(boards), G, R, Cc, _u64(symmetry_seed), _p(out), _stream()))
+    return out
+
+
+def evaluation_symmetry(boards, seed):
+    """The board symmetry every position of int8 [G,R,C] is evaluated under with evaluation_symmetry="random" and this
+    symmetry seed: int8 [G], a pure function of (seed, position) from the Philox streams (include/yy_engine.h,
+    YY_FLAG_EVAL_SYMMETRY).  Square boards, s in 0 .. 7: np.rot90(board, s & 3), then np.fliplr when s & 4; other boards,
+    s in 0 .. 3: np.flipud when s & 1, np.fliplr when s & 2."""
+    G, R, Cc = boards.shape
+    _need(boards, torch.int8, name="boards")
+    out = torch.empty(G, dtype=torch.int8, device=boards.device)
+    with torch.cuda.device(boards.device):
+        check(lib().yy_eval_symmetry(_p(boards), G, R, Cc, _u64(seed), _p(out), _stream()))
     return out
 
 
@@ -469,9 +499,14 @@ class OpeningBook:
     there before asking the evaluator (include/yy_engine.h: yy_mcts_set_book): all games start from the empty board, so the
     first plies of thousands of games walk the same positions.  The evaluator must be the one the searches use, and a
     deterministic function of the row (BatchedEvaluator.row_independent); the results of a search are then unchanged.
-    max_positions bounds the table: enumeration stops before the stone count that would exceed it (max_stones is lowered)."""
+    max_positions bounds the table: enumeration stops before the stone count that would exceed it (max_stones is lowered).
+    evaluation_symmetry / symmetry_seed: the rows are those of the contexts that will read the book -- with "random" every
+    position is shown to the evaluator under its drawn symmetry and the row stored as returned; the book remembers
+    (mode, seed) as `symmetry`, and a context of another (mode, seed) refuses it (BatchedMCTS.set_book)."""
 
-    def __init__(self, R, C, evaluator, max_stones, rowcol=False, batch=4096, device=None, max_positions=8_000_000):
+    def __init__(self, R, C, evaluator, max_stones, rowcol=False, batch=4096, device=None, max_positions=8_000_000,
+                 evaluation_symmetry="off", symmetry_seed=None):
+        self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.R, self.C, self.A, self.max_stones = int(R), int(C), int(R) * int(C), int(max_stones)
         nw = (self.A + 63) // 64
@@ -509,7 +544,7 @@ class OpeningBook:
         pol = torch.empty((self.n, self.A), dtype=torch.float32, device=dev)
         val = torch.empty(self.n, dtype=torch.float32, device=dev)
         for lo in range(0, self.n, batch):                                              # the evaluations: n / batch launches
-            p, v = evaluator(encode_planes(boards[lo:lo + batch].contiguous()))
+            p, v = evaluator(encode_planes(boards[lo:lo + batch].contiguous(), symmetry_seed=self.symmetry[1]))
             pol[lo:lo + batch], val[lo:lo + batch] = p, v
         self.cap = 64
         while self.cap < 6 * self.n:                   # load <= 1/6: next to no probe run reaches the 8-step window
@@ -539,8 +574,12 @@ class BatchedMCTS:
 
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
-                 keep_evaluations=False, leaves_per_step=1):
-        """reuse_pass_value (copied boards only): a childless non-terminal node keeps the value of its first
+                 keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None):
+        """evaluation_symmetry="random" (copied boards only; default "off": every launch is what it is without the option):
+        every position is shown to the evaluator under a board symmetry drawn from (symmetry_seed, position) and its policy
+        row mapped back (YY_FLAG_EVAL_SYMMETRY, include/yy_engine.h; evaluation_symmetry() above gives the draw).  symmetry_seed
+        None = 0.
+        reuse_pass_value (copied boards only): a childless non-terminal node keeps the value of its first
         evaluation instead of being evaluated again on every visit (YY_FLAG_REUSE_PASS_VALUE, include/yy_engine.h);
         needs a deterministic evaluator whose row results do not depend on the rest of the batch.
         reuse_transpositions: a leaf whose position was already evaluated in this search takes the cached policy row and
@@ -559,11 +598,13 @@ class BatchedMCTS:
         self.keep_evaluations = bool(keep_evaluations)
         self.K = max(1, int(leaves_per_step))
         self.rows = self.G * self.K            # evaluator rows of a step
+        self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
-                         | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0),
-                         int(edges_per_game), int(nodes_per_game), int(leaves_per_step))
+                         | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0)
+                         | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0),
+                         int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0)
         h = ct.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_create(ct.byref(cfg), ct.byref(h)))
@@ -714,9 +755,13 @@ class BatchedMCTS:
 
     def set_book(self, book):
         """Shallow leaves are looked up in `book` (OpeningBook, or None to unset) before the evaluator is asked; the context
-        keeps a reference so that the table outlives its use."""
+        keeps a reference so that the table outlives its use.  A book built under another (evaluation_symmetry, symmetry_seed)
+        holds rows of another frame: ValueError."""
         if book is not None and (book.R, book.C) != (self.R, self.C):
             raise _lib.YYError(-1, "the book was built for another board size")
+        if book is not None and getattr(book, "symmetry", ("off", None)) != self.symmetry:
+            raise ValueError(f"the book was built with (evaluation_symmetry, symmetry_seed) = {getattr(book, 'symmetry', ('off', None))}, "
+                             f"this context evaluates with {self.symmetry}: its rows are in another frame")
         with torch.cuda.device(self.device):
             if book is None:
                 check(lib().yy_mcts_set_book(self._h, None, None, None, None, 0, 0))

@@ -135,8 +135,11 @@ class _HostPredictEvaluator:
 class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
-                 board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False):
-        """board_semantics: "aliased" = literal reference (the search mutates the caller's board);
+                 board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
+                 evaluation_symmetry="off", symmetry_seed=None):
+        """evaluation_symmetry="random" (not in the reference; needs board_semantics="copied"): every position is shown to the
+        network under a board symmetry drawn from (symmetry_seed, position) and the policy mapped back (engine.BatchedMCTS).
+        board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
         evaluation_reuse (not in the reference; default off = its evaluator call sequence): a position is evaluated once per
         search (pass values with copied boards + the evaluation cache, include/yy_engine.h YY_FLAG_REUSE_*); same results, fewer
@@ -155,6 +158,9 @@ class MCTS:
         if tree_reuse and (board_semantics == "aliased" or max(1, int(leaves_per_step)) > 1):
             raise ValueError('tree_reuse=True needs board_semantics="copied" and leaves_per_step == 1')
         self.tree_reuse = bool(tree_reuse)
+        if evaluation_symmetry != "off" and board_semantics == "aliased":
+            raise ValueError('evaluation_symmetry="random" needs board_semantics="copied"')
+        self.symmetry = engine.symmetry_key(evaluation_symmetry, symmetry_seed)
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
         self.num_threads = max(1, num_threads)
@@ -179,7 +185,8 @@ class MCTS:
                                      aliased=(self.board_semantics == "aliased"), rowcol=self.rowcol,
                                      device=self.device,
                                      reuse_pass_value=self.evaluation_reuse and self.board_semantics == "copied",
-                                     reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step)
+                                     reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
+                                     evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1])
             self._ctx[G] = ctx
         return ctx
 

@@ -54,12 +54,22 @@ class SearchOptions:
     lockstep; compact_tail / row_tiers do not apply (slots do not move: the compacted evaluator pays for live rows only).  The
     move kernel plays copied boards, one descent per step, the per-game counter streams and a fresh root per move: refused
     with leaves_per_step > 1, aliased boards, reference_quirks, rng="numpy" and tree_reuse (follow-ups; yy_mcts_advance empties
-    the tree of every game it is not told to keep: re-rooting inside the step needs a "leave alone" action first)."""
+    the tree of every game it is not told to keep: re-rooting inside the step needs a "leave alone" action first).
+
+    evaluation_symmetry "random": every position is shown to the evaluator under a board symmetry drawn for it (the dihedral
+    group of a square board, the two flips of another) and its policy row is mapped back; the value is used as is.  The draw
+    is a pure function of (symmetry_seed, position) from the Philox streams (include/yy_engine.h, YY_FLAG_EVAL_SYMMETRY) --
+    not of slot, game, ply, simulation, batch or rank -- so evaluation reuse, the opening book (built through the same map and
+    tied to the seed), lockstep against free-running and every other option work as without it.  symmetry_seed None = the
+    engine's seed.  It changes which moves a search picks, unless the evaluator is exactly equivariant.  The reference has no
+    such option: refused with aliased boards, reference_quirks and rng="numpy", which exist for transcript parity with it."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
     tree_reuse: bool = False
     free_running: bool = False
+    evaluation_symmetry: str = "off"
+    symmetry_seed: int = None               # None: the engine's seed
 
     @property
     def playout_cap(self):
@@ -70,19 +80,32 @@ class SearchOptions:
     def keywords(self):
         """The keywords to hand to the next layer: leaves_per_step always, the others only when they are on."""
         on = {k: True for k in ("tree_reuse", "free_running") if getattr(self, k)}
+        if self.evaluation_symmetry != "off":
+            on.update(evaluation_symmetry=self.evaluation_symmetry, symmetry_seed=self.symmetry_seed)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
-            free_running=False):
+            free_running=False, evaluation_symmetry="off", symmetry_seed=None):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name the same option everywhere."""
+    -- evaluation_symmetry, free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name the same
+    option everywhere."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
+    if evaluation_symmetry not in ("off", "random"):
+        raise OptionConflict(f'evaluation_symmetry={evaluation_symmetry!r}: "off" or "random"', "evaluation_symmetry")
+    if evaluation_symmetry != "off":
+        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (reference_quirks, "reference_quirks", "reference_quirks=True"),
+               (rng != "philox", "rng", f'rng="{rng}"')]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f'evaluation_symmetry="{evaluation_symmetry}": the reference has no such option, so it does not go with '
+                                 f"what exists for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
+                                 "evaluation_symmetry", [b[0] for b in bad])
     if free_running:
         bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
                (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
@@ -118,4 +141,6 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             raise OptionConflict(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
                                  f"book -- not with {', '.join(b[1] for b in bad)}", "leaves_per_step", [b[0] for b in bad])
     cap = fast is not None and P < 1.0
-    return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running))
+    sym = evaluation_symmetry != "off"
+    return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
+                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed))

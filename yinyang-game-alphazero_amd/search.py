@@ -1,4 +1,5 @@
 """Graph-replayed driver of engine.BatchedMCTS.run_search: what SelfPlayEngine, Arena and MCTS (above 8 simulations) search with."""
+import gc
 import os
 
 import torch
@@ -68,10 +69,22 @@ class LockstepSearch:
             self._book_version, self._graph_evaluator = self.ctx.book_version, self.evaluator
 
     def _captured(self, rows, steps):
+        """`steps` steps captured into one graph.  Python's cycle collector is kept out of the capture: it runs when it pleases,
+        and a dropped engine that sits in a reference cycle (a caller that wrapped one of its methods, say) takes its captured
+        graphs and its device buffers with it only then -- destroying a graph or freeing device memory is not allowed while a
+        stream is capturing, and a destructor has no way to report the failure.  So automatic collection is off until the capture
+        has ended; what it would have collected waits for the next collection outside.  (No gc.collect() in front: a full
+        collection per capture cost the default bench line 2 %.)"""
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(steps):
-                self._sim_step(rows)
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph):
+                for _ in range(steps):
+                    self._sim_step(rows)
+        finally:
+            if was_enabled:
+                gc.enable()
         return graph
 
     def _capture(self, gkey, rows, n):

@@ -31,12 +31,14 @@ from .search import FreeRunningSearch, LockstepSearch
 DRAW = 1e-4
 
 
-def _opening_book(opening_book, game, evaluator, device):
-    """An engine.OpeningBook as it is; a stone count N -> the book of every position with <= N stones, None for N <= 0."""
+def _opening_book(opening_book, game, evaluator, device, symmetry=("off", None)):
+    """An engine.OpeningBook as it is; a stone count N -> the book of every position with <= N stones, None for N <= 0, built
+    under `symmetry` = (evaluation_symmetry, symmetry_seed) of the contexts that will read it."""
     if not isinstance(opening_book, int):
         return opening_book
     R, C = game.getBoardSize()
-    return (engine.OpeningBook(R, C, evaluator, opening_book, rowcol=bool(getattr(game, "rowcol_rule", False)), device=device)
+    return (engine.OpeningBook(R, C, evaluator, opening_book, rowcol=bool(getattr(game, "rowcol_rule", False)), device=device,
+                               evaluation_symmetry=symmetry[0], symmetry_seed=symmetry[1])
             if opening_book > 0 else None)
 
 
@@ -85,9 +87,11 @@ class _Engine:
                  device=None, first_game_index=0, game_index_stride=1,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse and the mode (free_running): options.SearchOptions;
-        a refused combination raises ValueError before anything touches the device.
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
+                 symmetry_seed=None):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: `seed`)
+        and the mode (free_running): options.SearchOptions; a refused combination raises ValueError before anything touches the
+        device.  An opening_book built under another (evaluation_symmetry, symmetry_seed) is refused (ValueError).
         reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
         declares `row_independent` (the split-f16 evaluator does); off at leaves_per_step > 1.  The reference asks the network
         for every leaf: a node without legal moves again on every visit (ai/mcts.py:93-95, 371-397), a position another move
@@ -105,8 +109,9 @@ class _Engine:
         assert rng in ("philox", "numpy")
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
-                               full_search_probability, tree_reuse, self.free_running)
+                               full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed)
         self.K, self.tree_reuse = opts.leaves_per_step, opts.tree_reuse
+        self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
         self.R, self.C = game.getBoardSize()
@@ -127,8 +132,9 @@ class _Engine:
         self.ctx = engine.BatchedMCTS(self.G, self.R, self.C, self.sims, cpuct=cpuct, aliased=self.aliased,
                                       rowcol=self.rowcol, device=self.device, reuse_pass_value=self.reuse_pass_value,
                                       reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations,
-                                      leaves_per_step=self.K)
-        self.book = _opening_book(opening_book, game, evaluator, self.device)
+                                      leaves_per_step=self.K, evaluation_symmetry=self.symmetry[0],
+                                      symmetry_seed=self.symmetry[1])
+        self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
         self.seed = int(seed)                     # key of the per-game counter streams (csrc/yy_selfplay.hip)
@@ -589,21 +595,24 @@ class SelfPlayLanes:
     def __init__(self, game, evaluator, num_simulations=800, concurrent_games=4096, lanes=2, seed=0, device=None,
                  first_game_index=0, game_index_stride=1, opening_book=None, board_semantics="copied", reference_quirks=False,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, **engine_kwargs):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions, in every
-        lane; resolved here once, before the book or any lane is built.  Free-running lanes each run on their own stream and
-        the host alternates their batches of graph replays.  The other keywords are SelfPlayEngine's."""
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
+                 symmetry_seed=None, **engine_kwargs):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
+        (None: `seed`, the same in every lane): options.SearchOptions, in every lane; resolved here once, before the book or any
+        lane is built.  Free-running lanes each run on their own stream and the host alternates their batches of graph replays.
+        The other keywords are SelfPlayEngine's."""
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
-                               full_search_probability, tree_reuse, free_running)
+                               full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
+        symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
                              reuse_pass_value=reuse_pass_value, reuse_transpositions=reuse_transpositions,
                              keep_evaluations=keep_evaluations, **opts.keywords())
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         K = max(1, min(int(lanes), int(concurrent_games)))
         self.game, self.evaluator, self.sims = game, evaluator, int(num_simulations)
-        self.book = _opening_book(opening_book, game, evaluator, self.device)      # one book, shared read-only by every lane
+        self.book = _opening_book(opening_book, game, evaluator, self.device, symmetry)      # one book, shared read-only by every lane
         self.lanes = []
         for k in range(K):
             g_k = concurrent_games // K + (1 if k < concurrent_games % K else 0)
@@ -790,16 +799,19 @@ class SelfPlayWorker:
     def __init__(self, game, model_path, num_simulations=800, num_games=1, temperature_threshold=10,
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
-                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse: options.SearchOptions, through MCTS; K > 1 and
-        tree_reuse need board_semantics="copied", K > 1 also reference_quirks=False, which are not this class's defaults.
+                 fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
+                 evaluation_symmetry="off", symmetry_seed=None):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
+        class has no seed of its own): options.SearchOptions, through MCTS; K > 1, tree_reuse and evaluation_symmetry need
+        board_semantics="copied", K > 1 and evaluation_symmetry also reference_quirks=False, which are not this class's defaults.
         free_running: refused (ValueError).  This class plays ONE game at a time through MCTS, drawing from numpy's global
         stream: there is no batch whose games could be freed from each other; the mode is SelfPlayEngine's."""
         if free_running:
             raise ValueError("free_running=True: SelfPlayWorker plays one game at a time through MCTS (numpy's global stream): "
                              "there is no batch to free -- use SelfPlayEngine / SelfPlayManager")
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, fast_simulations=fast_simulations,
-                               full_search_probability=full_search_probability, tree_reuse=tree_reuse)
+                               full_search_probability=full_search_probability, tree_reuse=tree_reuse,
+                               evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed)
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -817,7 +829,8 @@ class SelfPlayWorker:
         self.mcts = MCTS(game, neural_net, num_simulations=num_simulations, cpuct=cpuct,
                          dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                          num_threads=num_parallel, board_semantics=board_semantics, device=device,
-                         leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse)
+                         leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse,
+                         evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed)
 
     def play_game(self):
         game, examples = self.game, []
@@ -899,14 +912,15 @@ class SelfPlayManager:
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
-                 tree_reuse=False, free_running=False):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running: options.SearchOptions.
+                 tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None):
+        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
+        (None: the engine's seed, 1000 + seed, on every rank): options.SearchOptions.
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine; off at leaves_per_step > 1, where opening_book_stones=None also means no
         book); False = the network is asked for every leaf like the reference."""
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
-                                       tree_reuse, free_running)
+                                       tree_reuse, free_running, evaluation_symmetry, symmetry_seed)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
