@@ -88,6 +88,21 @@ extern "C" {
                               them and are read through the same map (a book must be built with yy_encode_planes_sym and the
                               same seed).  Flag clear: every kernel does what it did without it. */
 
+#define YY_FLAG_FORCED_PLAYOUTS 64u /* forced playouts with policy target pruning at the search root (Wu, "Accelerating Self-Play
+                              Learning in Go", section 3.2; not in the reference).  k = yy_mcts_config.forced_playouts, positive
+                              and finite (else YY_E_INVALID), fixed at creation.  Copied boards and leaves_per_step <= 1 only: create
+                              returns YY_E_UNSUPPORTED with YY_FLAG_ALIASED or K > 1.  Forcing, at depth 0 of every descent: with S
+                              the sum of the root's child visits that its PUCT uses (root visits, one less on a root kept by
+                              yy_mcts_advance), P the edge's stored prior (the noised one at a noised root) and N its visits, an
+                              edge is forced iff N >= 1 and f64(N)*f64(N) < (k*f64(P))*f64(S); the descent takes the forced edge of
+                              the lowest action, else the PUCT choice.  Below the root, expansion and backup are untouched.
+                              Pruning: yy_mcts_root_policy and the move of yy_mcts_step_selfplay compute pi from counts N': c* =
+                              the most visited edge (lowest action on ties) keeps N; every other edge with N > 0 gives back, one
+                              visit at a time and at most n_f = min{m >= 0: f64(m)*f64(m) >= (k*f64(P))*f64(S)} of them, every
+                              visit without which its PUCT score (N' - 1 in the exploration term, W / N unchanged) stays below
+                              c*'s score at the final S; N' == 1 becomes 0.  yy_mcts_root_counts returns the raw visits.
+                              Flag clear: every kernel does what it did without it. */
+
 typedef void *yy_stream_t;
 
 const char *yy_last_error(void);
@@ -156,6 +171,7 @@ typedef struct yy_mcts_config {
                                   the reference's search.  1 < K <= 64 needs copied boards and no YY_FLAG_REUSE_* /
                                   YY_FLAG_KEEP_EVALUATIONS (create returns YY_E_UNSUPPORTED) and no book.  See below. */
     uint64_t symmetry_seed;    /* YY_FLAG_EVAL_SYMMETRY: the seed of the symmetry draw; ignored without the flag */
+    double forced_playouts;    /* YY_FLAG_FORCED_PLAYOUTS: k (KataGo: 2.0); ignored without the flag */
 } yy_mcts_config;
 
 /* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after
@@ -266,6 +282,9 @@ int yy_mcts_get_boards(yy_mcts *ctx, int8_t *boards, yy_stream_t stream);
  * or the last yy_mcts_reset_counters.  Returns YY_E_ARENA if any game overflowed. */
 int yy_mcts_status(yy_mcts *ctx, int32_t *n_overflow, uint64_t *counters);
 int yy_mcts_reset_counters(yy_mcts *ctx, yy_stream_t stream);
+/* sync. YY_FLAG_FORCED_PLAYOUTS: the root descents, over all games, that took a forced edge since create or the last
+ * yy_mcts_reset_counters (host out; 0 without the flag). */
+int yy_mcts_forced_descents(yy_mcts *ctx, uint64_t *out);
 /* Shared book of pre-evaluated positions.  Every self-play game starts from the empty board, so the searches of the first plies
  * of ALL games walk the same few hundred thousand positions (8x8: 770 232 positions with <= 8 stones are reachable).  The
  * caller enumerates them, evaluates them once in large batches with the SAME evaluator the searches use, and hands the table

@@ -8,7 +8,7 @@
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
 --dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability, --tree-reuse, --free-running,
---evaluation-symmetry, --symmetry-seed.  `--mode train` runs
+--evaluation-symmetry, --symmetry-seed, --forced-playouts.  `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
 """
@@ -94,6 +94,11 @@ def parse_args(argv=None):
                         "which moves are picked; not with --board-semantics aliased or --reference-quirks)")
     p.add_argument("--symmetry-seed", type=int, default=None,
                    help="seed of the symmetry draw of --evaluation-symmetry random (default: the engine's seed)")
+    p.add_argument("--forced-playouts", type=float, default=None, metavar="K",
+                   help="self-play and train: forced playouts with policy target pruning at the search root -- a visited root child "
+                        "is visited again while N*N < K*P*S, and the recorded policy is computed from the pruned counts (KataGo: 2; "
+                        "default off; changes which moves are picked; not with --leaves-per-step > 1, --board-semantics aliased or "
+                        "--reference-quirks)")
     return p.parse_args(argv)
 
 
@@ -101,7 +106,7 @@ def parse_args(argv=None):
 # train's self-play always runs on copied boards without the quirks, so --tree-reuse and --free-running do not look at those two
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
-           "evaluation_symmetry")
+           "evaluation_symmetry", "forced_playouts")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse")]}
@@ -167,7 +172,8 @@ def main(argv=None):
                            lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
                            fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
                            tree_reuse=args.tree_reuse, free_running=args.free_running,
-                           evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed)
+                           evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
+                           forced_playouts=args.forced_playouts)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -197,7 +203,7 @@ def main(argv=None):
                                        fast_simulations=args.fast_simulations,
                                        full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse,
                                        free_running=args.free_running, evaluation_symmetry=args.evaluation_symmetry,
-                                       symmetry_seed=args.symmetry_seed)
+                                       symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

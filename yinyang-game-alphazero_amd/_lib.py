@@ -17,6 +17,7 @@ FLAG_REUSE_PASS_VALUE = 4
 FLAG_REUSE_TRANSPOSITIONS = 8
 FLAG_KEEP_EVALUATIONS = 16
 FLAG_EVAL_SYMMETRY = 32
+FLAG_FORCED_PLAYOUTS = 64
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -31,7 +32,8 @@ class YYError(RuntimeError):
 class MctsConfig(C.Structure):
     _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_sims", C.c_int32),
                 ("cpuct", C.c_float), ("flags", C.c_uint32), ("edges_per_game", C.c_int64),
-                ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32), ("symmetry_seed", C.c_uint64)]
+                ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32), ("symmetry_seed", C.c_uint64),
+                ("forced_playouts", C.c_double)]
 
 
 class SelfPlayConfig(C.Structure):
@@ -93,6 +95,7 @@ _SIGS = {
     "yy_mcts_get_boards": [_vp, _vp, _vp],
     "yy_mcts_status": [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)],
     "yy_mcts_reset_counters": [_vp, _vp],
+    "yy_mcts_forced_descents": [_vp, C.POINTER(C.c_uint64)],
     "yy_mcts_cache_clear": [_vp, _vp],
     "yy_book_insert": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, _vp],
     "yy_mcts_set_book": [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int],

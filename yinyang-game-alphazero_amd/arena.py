@@ -321,15 +321,15 @@ class AlphaZero:
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
-                 symmetry_seed=None):
+                 symmetry_seed=None, forced_playouts=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry /
-        symmetry_seed: options.SearchOptions, for the loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also
+        symmetry_seed, forced_playouts: options.SearchOptions, for the loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also
         for its arena, which always searches num_simulations, plays in lockstep and shows every position to the network in
-        its one orientation (evaluation_symmetry is a self-play option)."""
+        its one orientation and without forced playouts (evaluation_symmetry and forced_playouts are self-play options)."""
         self.options = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                                        full_search_probability=full_search_probability, tree_reuse=tree_reuse,
                                        free_running=free_running, evaluation_symmetry=evaluation_symmetry,
-                                       symmetry_seed=symmetry_seed)
+                                       symmetry_seed=symmetry_seed, forced_playouts=forced_playouts)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold

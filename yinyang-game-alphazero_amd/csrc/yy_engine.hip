@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 105
+#define YY_VERSION 106
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -87,11 +87,6 @@ __device__ __forceinline__ uint32_t wave_uadd(uint32_t v) {
     YY_DPP_STEP(uadd32, 0u, v, 0x142, 0xa);
     YY_DPP_STEP(uadd32, 0u, v, 0x143, 0xc);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// float -> unsigned key with the same order (all non-NaN keys are > 0)
-__device__ __forceinline__ uint32_t f32_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // ------------------------------------------------------------------------- stateless kernels
@@ -500,16 +495,9 @@ __device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *s
 // with the reference exists once, here.
 #define BEST_NONE 0x7FFFFFFF
 
-// Order-preserving key of one child's PUCT score (mcts.py:120-133), float32 order of SURVEY 8a/a12.  K = 1 passes the edge's
-// N and W, K > 1 the counts with this step's virtual visits (do_select_multi).
-__device__ __forceinline__ uint32_t child_key(float cpuct, float sq, float P, int n, float w) {
-    const float t1 = __fmul_rn(cpuct, P);
-    const float t2 = __fmul_rn(t1, sq);
-    const float u = __fdiv_rn(t2, (float)(1 + n));
-    const float q = (n > 0) ? __fdiv_rn(w, (float)n) : 0.0f;
-    const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);   // + 0.0f: -0.0 compares equal to +0.0 (mcts.py:133)
-    return f32_key(ucb);
-}
+// child_key, the order-preserving key of one child's PUCT score (mcts.py:120-133), lives in yy_tree.h: the root distribution
+// prunes forced playouts with it.  K = 1 passes the edge's N and W, K > 1 the counts with this step's virtual visits
+// (do_select_multi).
 
 // Wave arg-max over the k children of a node: every lane brings the best key `bk` of its own children and that child's index
 // `bi` (BEST_NONE: none).  Returns the child with the largest key, the lowest index among ties = the lowest action
@@ -755,6 +743,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
 
     int node = 0, depth = 0, parent = -1, action = -1, kind;
     uint64_t c_levels = 0, c_scan = 0;
+    int c_forced = 0;   // wave-uniform: this descent took a forced edge (stored with the counters below)
     for (;;) {
         const uint4 hdr = nodes[node];
         const uint32_t hy = rfl(hdr.y);
@@ -780,18 +769,42 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         } else {
             S = s_carry;
         }
-        const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
-        uint32_t bk = 0, bw = 0, bn = 0;
-        int bi = BEST_NONE;
-        for (int j = lane; j < k; j += 64) {
-            const uint4 e = edges[first + j];
-            const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e.x), (int)e.y, __uint_as_float(e.z));
-            if (key > bk) { bk = key; bi = j; bw = e.w; bn = e.y; }               // strict >: lowest j of a lane
+        // forced playouts: at the root a visited edge that is still owed visits (edge_forced, yy_tree.h) is taken before any
+        // score is looked at, the lowest action first.  Wave-uniform branch; below the root only `depth == 0` is tested, at the
+        // root without the option one float64 compare more
+        int best = BEST_NONE;
+        if (depth == 0 && d.forced > 0.0) {
+            for (int j0 = 0; j0 < k && best == BEST_NONE; j0 += 64) {
+                const int j = j0 + lane;
+                bool f = false;
+                if (j < k) {
+                    const uint4 e = edges[first + j];
+                    f = edge_forced(d.forced, __uint_as_float(e.x), (int)e.y, S);
+                }
+                const uint64_t fm = __ballot(f);
+                if (fm) best = j0 + (int)__ffsll((unsigned long long)fm) - 1;
+            }
+            c_forced += (best != BEST_NONE);
         }
-        const int best = best_child(bk, bi, k);
-        if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }  // no selectable child
-        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
-        s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
+        uint32_t w;
+        if (best != BEST_NONE) {
+            const uint4 e = edges[first + best];
+            w = rfl(e.w);
+            s_carry = (int)rfl(e.y) - 1;
+        } else {
+            const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
+            uint32_t bk = 0, bw = 0, bn = 0;
+            int bi = BEST_NONE;
+            for (int j = lane; j < k; j += 64) {
+                const uint4 e = edges[first + j];
+                const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e.x), (int)e.y, __uint_as_float(e.z));
+                if (key > bk) { bk = key; bi = j; bw = e.w; bn = e.y; }               // strict >: lowest j of a lane
+            }
+            best = best_child(bk, bi, k);
+            if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }  // no selectable child
+            w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
+            s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
+        }
         if (lane == 0) path[depth] = first + best;
         depth++;
         c_levels++;
@@ -843,6 +856,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         if (need) st->ctr[0] += 1;
         if (kind == K_TERMINAL) st->ctr[4] += 1;
         if (kind == K_REUSE) st->ctr[6] += 1;
+        if (c_forced) st->forced += 1;
         if (needs_eval) needs_eval[g] = need;
     }
 }
@@ -1290,6 +1304,13 @@ __global__ void k_reset_counters(MctsDev d) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     for (int i = 0; i < 8; i++) d.state[g].ctr[i] = 0;
+    d.state[g].forced = 0;
+}
+
+__global__ void k_forced_sum(MctsDev d, uint64_t *out) {
+    uint64_t acc = 0;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x) acc += d.state[g].forced;
+    if (acc) atomicAdd((unsigned long long *)out, (unsigned long long)acc);
 }
 
 // ---------------------------------------------------------------------------------- host API
@@ -1301,6 +1322,14 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         return set_err(YY_E_INVALID, "YY_FLAG_REUSE_PASS_VALUE needs copied boards: with the aliased board a node's position changes between visits%s%s");
     if ((cfg->flags & YY_FLAG_EVAL_SYMMETRY) && (cfg->flags & YY_FLAG_ALIASED))
         return set_err(YY_E_UNSUPPORTED, "YY_FLAG_EVAL_SYMMETRY needs copied boards (YY_FLAG_ALIASED reproduces the reference, which has no such option)%s%s");
+    if (cfg->flags & YY_FLAG_FORCED_PLAYOUTS) {
+        if (cfg->flags & YY_FLAG_ALIASED)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_FORCED_PLAYOUTS needs copied boards (YY_FLAG_ALIASED reproduces the reference, which has no such option)%s%s");
+        if (cfg->leaves_per_step > 1)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_FORCED_PLAYOUTS: leaves_per_step > 1 is not supported (the forcing test is part of the one-descent selection)%s%s");
+        if (!(cfg->forced_playouts > 0.0 && cfg->forced_playouts < (double)INFINITY))
+            return set_err(YY_E_INVALID, "YY_FLAG_FORCED_PLAYOUTS: forced_playouts must be positive and finite%s%s");
+    }
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
     if (cfg->leaves_per_step > 1) {
@@ -1323,7 +1352,8 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.cpuct = cfg->cpuct;
     d.sym = (cfg->flags & YY_FLAG_EVAL_SYMMETRY) ? 1u : 0u;
     d.sym_seed = d.sym ? cfg->symmetry_seed : 0ull;
-    m.K =cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
+    d.forced = (cfg->flags & YY_FLAG_FORCED_PLAYOUTS) ? cfg->forced_playouts : 0.0;
+    m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
     yy_make_geo(&d.geo, cfg->R, cfg->C, cfg->flags & YY_FLAG_ROWCOL);
@@ -1541,6 +1571,16 @@ extern "C" int yy_mcts_status(yy_mcts *c, int32_t *n_overflow, uint64_t *counter
     }
     if (n_overflow) *n_overflow = (int32_t)h[8];
     if (h[8]) return set_err(YY_E_ARENA, "tree arena overflow or non-finite evaluator output in at least one game since the last status call%s%s");
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_forced_descents(yy_mcts *c, uint64_t *out) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(c->scratch, 0, sizeof(uint64_t)));
+    hipLaunchKernelGGL(k_forced_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, c->scratch, sizeof(uint64_t), hipMemcpyDeviceToHost));
     return YY_OK;
 }
 

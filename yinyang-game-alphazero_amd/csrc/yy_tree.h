@@ -225,6 +225,7 @@ struct GameState {
     int32_t budget;         // K = 1: simulations of this game's current search (root_setup); at root_N == budget selection stops
     LeafRec leaf;           // K = 1: the pending leaf
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
+    uint64_t forced;        // forced playouts: root descents that took a forced edge, since create / yy_mcts_reset_counters
 };
 
 // A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
@@ -262,6 +263,9 @@ struct MctsDev {
     // row read through sym_cell; 0: off, every kernel does what it did without it
     uint32_t sym;
     uint64_t sym_seed;
+    // forced playouts with policy target pruning (YY_FLAG_FORCED_PLAYOUTS): k of yy_mcts_config.forced_playouts; 0.0: off, every
+    // kernel does what it did without it.  K = 1 and copied boards only (yy_mcts_create)
+    double forced;
 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
@@ -380,22 +384,103 @@ __device__ __forceinline__ void root_setup(const MctsDev &d, GameState *st, Leaf
     }
 }
 
+// ------------------------------------------------------------------------------------ the edge score, one copy
+// float -> unsigned key with the same order (all non-NaN keys are > 0)
+__device__ __forceinline__ uint32_t f32_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Order-preserving key of one child's PUCT score (mcts.py:120-133), float32 order of SURVEY 8a/a12: the exploration term with
+// `nu` visits, the mean value over `nq`.  Selection scores an edge with nu == nq (child_key); policy target pruning asks what
+// the edge would have scored with fewer visits and its real mean value.
+__device__ __forceinline__ uint32_t child_key_at(float cpuct, float sq, float P, int nu, int nq, float w) {
+    const float t1 = __fmul_rn(cpuct, P);
+    const float t2 = __fmul_rn(t1, sq);
+    const float u = __fdiv_rn(t2, (float)(1 + nu));
+    const float q = (nq > 0) ? __fdiv_rn(w, (float)nq) : 0.0f;
+    const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);   // + 0.0f: -0.0 compares equal to +0.0 (mcts.py:133)
+    return f32_key(ucb);
+}
+__device__ __forceinline__ uint32_t child_key(float cpuct, float sq, float P, int n, float w) {
+    return child_key_at(cpuct, sq, P, n, n, w);
+}
+
+// ------------------------------------------------------------------------------------ forced playouts (YY_FLAG_FORCED_PLAYOUTS)
+// k * P(c) * S in float64, in this order: the square of the visits a root edge of stored prior P is owed once the root's
+// children hold S visits.  An edge is forced while it has been visited and N * N is below the bound.
+__device__ __forceinline__ double forced_bound(const double k, const float P, const int S) {
+    return __dmul_rn(__dmul_rn(k, (double)P), (double)S);
+}
+__device__ __forceinline__ bool edge_forced(const double k, const float P, const int n, const int S) {
+    return n >= 1 && __dmul_rn((double)n, (double)n) < forced_bound(k, P, S);
+}
+
+// Policy target pruning: the counts cn[i] of this lane's root edges (edge i*64 + lane; 0 past the k-th) become the pruned
+// counts N'.  c* = the most visited edge, the lowest index on ties, keeps its count; every other visited edge gives back, one
+// at a time and at most n_f = min{m >= 0: m*m >= k*P*S} of them, the visits without which it would still score below c* (its
+// mean value held), and an edge left with one visit is left with none.
+template <int NW>
+__device__ __forceinline__ void prune_forced(const MctsDev &d, const uint4 *edges, const int first, const int k, const int S,
+                                             int (&cn)[NW]) {
+    int mx = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) mx = max(mx, cn[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+    if (mx == 0) return;                                                        // wave-uniform: no edge was visited
+    int star = -1;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const uint64_t m = __ballot(i * 64 + lane_id() < k && cn[i] == mx);
+        if (star < 0 && m) star = i * 64 + (int)__ffsll((unsigned long long)m) - 1;
+    }
+    const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];
+    const uint4 es = edges[first + star];
+    const uint32_t kstar = child_key(d.cpuct, sq, __uint_as_float(rfl(es.x)), (int)rfl(es.y), __uint_as_float(rfl(es.z)));
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int j = i * 64 + lane_id();
+        if (j >= k || j == star || cn[i] == 0) continue;
+        const uint4 e = edges[first + j];
+        const float P = __uint_as_float(e.x), w = __uint_as_float(e.z);
+        const int n = cn[i];
+        const double bound = forced_bound(d.forced, P, S);
+        int np = n;
+        for (int m = 0; np >= 1 && __dmul_rn((double)m, (double)m) < bound; m++) {   // m < n_f
+            if (child_key_at(d.cpuct, sq, P, np - 1, n, w) < kstar) np -= 1;
+            else break;
+        }
+        cn[i] = (np == 1) ? 0 : np;
+    }
+}
+
 // Node.get_children_distribution (mcts.py:183-215) of game g's root for T == 1 and T == 0 into pi[0 .. A) (float64; global
-// memory or LDS).  Every thread of the one-wavefront block calls it.
+// memory or LDS), with forced playouts on the pruned counts.  Every thread of the one-wavefront block calls it.
 template <int NW> __device__ __forceinline__ void root_distribution(const MctsDev &d, const int g, const int tzero, double *pi) {
     const int A = d.geo.A;
     const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
     const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
     const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
     const bool act = rfl((int)d.state[g].active) != 0;
+    int cn[NW];                                                                 // k <= A <= 64 * NW: edge i*64 + lane
     int sum = 0, mx = 0;
-    if (act)
-        for (int j = lane_id(); j < k; j += 64) {
-            int n = (int)edges[first + j].y;
-            sum += n;
-            mx = max(mx, n);
-        }
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int j = i * 64 + lane_id();
+        cn[i] = (act && j < k) ? (int)edges[first + j].y : 0;
+        sum += cn[i];
+    }
     sum = wave_sum(sum);
+    if (d.forced > 0.0 && act) {                                                // wave-uniform; S = the children's visits
+        prune_forced<NW>(d, edges, first, k, sum, cn);
+        sum = 0;
+#pragma unroll
+        for (int i = 0; i < NW; i++) sum += cn[i];
+        sum = wave_sum(sum);
+    }
+#pragma unroll
+    for (int i = 0; i < NW; i++) mx = max(mx, cn[i]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
     double fill;
@@ -404,7 +489,8 @@ template <int NW> __device__ __forceinline__ void root_distribution(const MctsDe
         // counts == max over ALL A actions (zeros included when max == 0), mcts.py:200-203
         if (mx == 0) nbest = A;
         else {
-            for (int j = lane_id(); j < k; j += 64) nbest += ((int)edges[first + j].y == mx);
+#pragma unroll
+            for (int i = 0; i < NW; i++) nbest += (i * 64 + lane_id() < k && cn[i] == mx);
             nbest = wave_sum(nbest);
         }
         fill = (mx == 0) ? 1.0 / (double)A : 0.0;
@@ -414,10 +500,14 @@ template <int NW> __device__ __forceinline__ void root_distribution(const MctsDe
     for (int a = lane_id(); a < A; a += 64) pi[a] = act ? fill : 0.0;
     __syncthreads();
     if (!act) return;
-    if (tzero ? (mx > 0) : (sum > 0))
-        for (int j = lane_id(); j < k; j += 64) {
-            const uint4 e = edges[first + j];
-            const int a = (int)(e.w >> 24), n = (int)e.y;
-            pi[a] = tzero ? ((n == mx) ? 1.0 / (double)nbest : 0.0) : (double)n / (double)sum;
+    if (tzero ? (mx > 0) : (sum > 0)) {
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            const int j = i * 64 + lane_id();
+            if (j < k) {
+                const int a = (int)(edges[first + j].w >> 24), n = cn[i];
+                pi[a] = tzero ? ((n == mx) ? 1.0 / (double)nbest : 0.0) : (double)n / (double)sum;
+            }
         }
+    }
 }

@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from .options import forced_k
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -574,8 +575,12 @@ class BatchedMCTS:
 
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
-                 keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None):
-        """evaluation_symmetry="random" (copied boards only; default "off": every launch is what it is without the option):
+                 keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
+        """forced_playouts=k > 0 (copied boards and leaves_per_step == 1 only; None / 0 = off: every launch is what it is without
+        the option; KataGo: 2): forced playouts with policy target pruning at the root (YY_FLAG_FORCED_PLAYOUTS, include/yy_engine.h).
+        A visited root child is visited again while N * N < k * P * S, and root_policy() is computed from the pruned counts;
+        root_counts() stays raw.  Fixed at creation (captured steps hold the context's device view by value).
+        evaluation_symmetry="random" (copied boards only; default "off": every launch is what it is without the option):
         every position is shown to the evaluator under a board symmetry drawn from (symmetry_seed, position) and its policy
         row mapped back (YY_FLAG_EVAL_SYMMETRY, include/yy_engine.h; evaluation_symmetry() above gives the draw).  symmetry_seed
         None = 0.
@@ -599,12 +604,15 @@ class BatchedMCTS:
         self.K = max(1, int(leaves_per_step))
         self.rows = self.G * self.K            # evaluator rows of a step
         self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
+        self.forced_playouts = forced_k(forced_playouts)
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
                          | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0)
-                         | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0),
-                         int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0)
+                         | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0)
+                         | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0),
+                         int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
+                         self.forced_playouts)
         h = ct.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_create(ct.byref(cfg), ct.byref(h)))
@@ -731,6 +739,13 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_root_policy(self._h, int(bool(temperature_zero)), _p(pi), _stream()))
         return pi
+
+    def forced_descents(self):
+        """sync; forced_playouts: the root descents, over all games, that took a forced edge since create / reset_counters()."""
+        n = ct.c_uint64(0)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_forced_descents(self._h, ct.byref(n)))
+        return int(n.value)
 
     def root_stats(self):
         visits = torch.empty(self.G, dtype=torch.int32, device=self.device)

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, options
 from .game import YinYangLogic
 from .network import BatchedEvaluator
 from .search import LockstepSearch
@@ -136,8 +136,11 @@ class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
-                 evaluation_symmetry="off", symmetry_seed=None):
-        """evaluation_symmetry="random" (not in the reference; needs board_semantics="copied"): every position is shown to the
+                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
+        """forced_playouts=k > 0 (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; None / 0 = off):
+        forced playouts with policy target pruning at the root (engine.BatchedMCTS); the distribution search() returns is the
+        pruned one.  The device prunes for temperature 0 and 1 only: a search with any other temperature raises ValueError.
+        evaluation_symmetry="random" (not in the reference; needs board_semantics="copied"): every position is shown to the
         network under a board symmetry drawn from (symmetry_seed, position) and the policy mapped back (engine.BatchedMCTS).
         board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
@@ -161,6 +164,9 @@ class MCTS:
         if evaluation_symmetry != "off" and board_semantics == "aliased":
             raise ValueError('evaluation_symmetry="random" needs board_semantics="copied"')
         self.symmetry = engine.symmetry_key(evaluation_symmetry, symmetry_seed)
+        self.forced_playouts = options.forced_k(forced_playouts)
+        if self.forced_playouts:                                # the resolver's refusals: aliased boards, leaves_per_step > 1
+            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts)
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
         self.num_threads = max(1, num_threads)
@@ -186,7 +192,8 @@ class MCTS:
                                      device=self.device,
                                      reuse_pass_value=self.evaluation_reuse and self.board_semantics == "copied",
                                      reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
-                                     evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1])
+                                     evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
+                                     forced_playouts=self.forced_playouts)
             self._ctx[G] = ctx
         return ctx
 
@@ -227,6 +234,9 @@ class MCTS:
         if self.temperature in (0, 1.0):
             pi = ctx.root_policy(temperature_zero=(self.temperature == 0))
         else:
+            if self.forced_playouts:
+                raise ValueError(f"forced_playouts={self.forced_playouts}: the pruned distribution exists for temperature 0 and 1 "
+                                 f"(root_policy), not for temperature={self.temperature}")
             c = ctx.root_counts().cpu().numpy()
             pi = torch.from_numpy(np.stack([children_distribution(r, self.temperature) for r in c])).to(boards.device)
         return pi, ctx

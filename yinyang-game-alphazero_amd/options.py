@@ -62,7 +62,18 @@ class SearchOptions:
     not of slot, game, ply, simulation, batch or rank -- so evaluation reuse, the opening book (built through the same map and
     tied to the seed), lockstep against free-running and every other option work as without it.  symmetry_seed None = the
     engine's seed.  It changes which moves a search picks, unless the evaluator is exactly equivariant.  The reference has no
-    such option: refused with aliased boards, reference_quirks and rng="numpy", which exist for transcript parity with it."""
+    such option: refused with aliased boards, reference_quirks and rng="numpy", which exist for transcript parity with it.
+
+    forced_playouts k > 0 (KataGo: 2): forced playouts with policy target pruning at the search root (Wu, "Accelerating Self-Play
+    Learning in Go", section 3.2; include/yy_engine.h YY_FLAG_FORCED_PLAYOUTS).  At the root a child that
+    has been visited is visited again, before any score is looked at, while N * N < k * P * S (P its stored, noised prior, S the
+    visits of the root's children), so a child that noise or a low prior makes interesting is judged on more than a handful of
+    visits; pi -- the recorded example, the distribution the move is drawn from, root_policy() -- is then computed from counts
+    from which every visit is taken back that the search would not have spent on the child by its score alone, and a child
+    left with one visit is left with none.  Root visit counts (root_counts) stay raw.  Fast and full searches of the playout
+    cap alike (KataGo switches it off in fast searches: a follow-up).  It changes which moves a search picks.  The forcing
+    test is part of the one-descent selection on copied boards, and the reference has no such option: refused with
+    leaves_per_step > 1, aliased boards, reference_quirks and rng="numpy"."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -70,6 +81,7 @@ class SearchOptions:
     free_running: bool = False
     evaluation_symmetry: str = "off"
     symmetry_seed: int = None               # None: the engine's seed
+    forced_playouts: float = 0.0            # 0.0: off
 
     @property
     def playout_cap(self):
@@ -82,18 +94,34 @@ class SearchOptions:
         on = {k: True for k in ("tree_reuse", "free_running") if getattr(self, k)}
         if self.evaluation_symmetry != "off":
             on.update(evaluation_symmetry=self.evaluation_symmetry, symmetry_seed=self.symmetry_seed)
+        if self.forced_playouts:
+            on.update(forced_playouts=self.forced_playouts)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
+
+
+def forced_k(forced_playouts):
+    """forced_playouts as the device takes it: 0.0 for None / 0 (off), else the positive finite float.  OptionConflict for
+    anything else."""
+    if forced_playouts is None:
+        return 0.0
+    try:
+        k = float(forced_playouts)
+    except (TypeError, ValueError):
+        k = -1.0
+    if not 0.0 <= k < float("inf"):
+        raise OptionConflict(f"forced_playouts={forced_playouts!r}: a finite number >= 0 (0 / None: off; KataGo uses 2)", "forced_playouts")
+    return k
 
 
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
-            free_running=False, evaluation_symmetry="off", symmetry_seed=None):
+            free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- evaluation_symmetry, free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name the same
-    option everywhere."""
+    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name
+    the same option everywhere.  forced_playouts: None and 0 = off."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
     if evaluation_symmetry not in ("off", "random"):
@@ -106,6 +134,15 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             raise OptionConflict(f'evaluation_symmetry="{evaluation_symmetry}": the reference has no such option, so it does not go with '
                                  f"what exists for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
                                  "evaluation_symmetry", [b[0] for b in bad])
+    forced = forced_k(forced_playouts)
+    if forced:
+        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
+               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f"forced_playouts={forced_playouts}: the forcing test is part of the one-descent selection on copied "
+                                 f"boards, and the reference has no such option -- not with {', '.join(b[1] for b in bad)}",
+                                 "forced_playouts", [b[0] for b in bad])
     if free_running:
         bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
                (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
@@ -143,4 +180,4 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     cap = fast is not None and P < 1.0
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
-                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed))
+                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced)
