@@ -103,6 +103,25 @@ extern "C" {
                               c*'s score at the final S; N' == 1 becomes 0.  yy_mcts_root_counts returns the raw visits.
                               Flag clear: every kernel does what it did without it. */
 
+#define YY_FLAG_FPU_REDUCTION 128u /* first-play urgency reduction in the PUCT selection (KataGo / Lc0 practice; not in the
+                              reference, which scores an unvisited child with q = 0).  r = yy_mcts_config.fpu_reduction at every
+                              node below the root, r = yy_mcts_config.fpu_reduction_root at the root (depth 0 of a descent); r
+                              positive and finite, the root's finite and >= 0 (else YY_E_INVALID), fixed at creation.  Every
+                              board semantics, every leaves_per_step, every other flag.  At the node a descent selects from, with
+                              N and W of each child as its score reads them (leaves_per_step > 1: N + v and W less the virtual
+                              visits), over the children with N > 0:
+                                SN = sum of N                                          (integer)
+                                SW = f32(f64(sum of (int64)(f64(W) * 2^32)) * 2^-32)   (each term truncated toward zero)
+                                SP = f32(f64(sum of (uint64)(f64(P) * 2^40)) * 2^-40)  (P the stored prior: the noised one at a
+                                                                                        noised root; each term truncated)
+                              so that the sums do not depend on the order of the children.  A child with N == 0 is scored with
+                                q_fpu = f32( f32(SW / SN) - f32( r * f32(sqrt(SP)) ) )
+                              in place of 0 -- the division, the square root, the product and the difference each the correctly
+                              rounded float32 one, in this order -- and with q_fpu = 0 when SN == 0.  Its exploration term, the
+                              `+ 0.0f` and the score of every visited child are unchanged.  The estimate of the node's value is
+                              the mean over its visited children on purpose: it is in the units and the sign convention of the
+                              W / N it stands in for.  Flag clear: every kernel does what it did without it. */
+
 typedef void *yy_stream_t;
 
 const char *yy_last_error(void);
@@ -172,6 +191,8 @@ typedef struct yy_mcts_config {
                                   YY_FLAG_KEEP_EVALUATIONS (create returns YY_E_UNSUPPORTED) and no book.  See below. */
     uint64_t symmetry_seed;    /* YY_FLAG_EVAL_SYMMETRY: the seed of the symmetry draw; ignored without the flag */
     double forced_playouts;    /* YY_FLAG_FORCED_PLAYOUTS: k (KataGo: 2.0); ignored without the flag */
+    float fpu_reduction;       /* YY_FLAG_FPU_REDUCTION: r below the root (KataGo: 0.2); ignored without the flag */
+    float fpu_reduction_root;  /* YY_FLAG_FPU_REDUCTION: r at the root (KataGo: 0 at a noised root); ignored without the flag */
 } yy_mcts_config;
 
 /* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after

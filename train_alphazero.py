@@ -8,7 +8,7 @@
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
 --dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability, --tree-reuse, --free-running,
---evaluation-symmetry, --symmetry-seed, --forced-playouts.  `--mode train` runs
+--evaluation-symmetry, --symmetry-seed, --forced-playouts, --fpu-reduction, --fpu-reduction-root.  `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
 """
@@ -99,6 +99,12 @@ def parse_args(argv=None):
                         "is visited again while N*N < K*P*S, and the recorded policy is computed from the pruned counts (KataGo: 2; "
                         "default off; changes which moves are picked; not with --leaves-per-step > 1, --board-semantics aliased or "
                         "--reference-quirks)")
+    p.add_argument("--fpu-reduction", type=float, default=None, metavar="R",
+                   help="self-play, train (self-play and arena) and evaluate: first-play urgency reduction -- a child that has not been "
+                        "visited is scored with the mean value of its visited siblings less R * sqrt(their share of the prior) "
+                        "instead of 0 (KataGo: 0.2; default off; changes which moves are picked; not with --reference-quirks)")
+    p.add_argument("--fpu-reduction-root", type=float, default=None, metavar="R",
+                   help="the R of --fpu-reduction at the search root (default: the same R; KataGo uses 0 at a noised root)")
     return p.parse_args(argv)
 
 
@@ -106,10 +112,10 @@ def parse_args(argv=None):
 # train's self-play always runs on copied boards without the quirks, so --tree-reuse and --free-running do not look at those two
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
-           "evaluation_symmetry", "forced_playouts")
+           "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
-          "evaluate": [("leaves_per_step", "tree_reuse")]}
+          "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root")]}
 
 
 def _flag(args, name):
@@ -173,7 +179,8 @@ def main(argv=None):
                            fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
                            tree_reuse=args.tree_reuse, free_running=args.free_running,
                            evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
-                           forced_playouts=args.forced_playouts)
+                           forced_playouts=args.forced_playouts, fpu_reduction=args.fpu_reduction,
+                           fpu_reduction_root=args.fpu_reduction_root)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -186,7 +193,8 @@ def main(argv=None):
             sys.exit(f"Model file not found: {model_path}")
         res = pkg.evaluate_vs_random(game, model_path, num_games=10, num_simulations=args.simulations, nn_mode=args.nn,
                                      num_channels=args.channels, num_res_blocks=args.blocks,
-                                     leaves_per_step=args.leaves_per_step, tree_reuse=args.tree_reuse)
+                                     leaves_per_step=args.leaves_per_step, tree_reuse=args.tree_reuse,
+                                     fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root)
         print(json.dumps(res))
         return
     if not os.path.exists(model_path):           # same contract as the reference (train_alphazero.py:107-109)
@@ -203,7 +211,8 @@ def main(argv=None):
                                        fast_simulations=args.fast_simulations,
                                        full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse,
                                        free_running=args.free_running, evaluation_symmetry=args.evaluation_symmetry,
-                                       symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts)
+                                       symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts,
+                                       fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

@@ -18,6 +18,7 @@ FLAG_REUSE_TRANSPOSITIONS = 8
 FLAG_KEEP_EVALUATIONS = 16
 FLAG_EVAL_SYMMETRY = 32
 FLAG_FORCED_PLAYOUTS = 64
+FLAG_FPU_REDUCTION = 128
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -33,7 +34,7 @@ class MctsConfig(C.Structure):
     _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_sims", C.c_int32),
                 ("cpuct", C.c_float), ("flags", C.c_uint32), ("edges_per_game", C.c_int64),
                 ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32), ("symmetry_seed", C.c_uint64),
-                ("forced_playouts", C.c_double)]
+                ("forced_playouts", C.c_double), ("fpu_reduction", C.c_float), ("fpu_reduction_root", C.c_float)]
 
 
 class SelfPlayConfig(C.Structure):

@@ -105,8 +105,11 @@ class Arena:
     between two fixed networks is deterministic, as the reference's is."""
 
     def __init__(self, game, player_a, player_b, num_simulations=800, cpuct=1.0, device=None, seed=0,
-                 reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1, tree_reuse=False):
-        """evaluation_reuse: inside one search a position is evaluated once (pass values, other move orders) when both players
+                 reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1, tree_reuse=False,
+                 fpu_reduction=None, fpu_reduction_root=None):
+        """fpu_reduction r > 0 with fpu_reduction_root (None: r): first-play urgency reduction in every search of the match, both
+        players' (options.SearchOptions; None / 0 = off, the reference's q = 0 for an unvisited child).
+        evaluation_reuse: inside one search a position is evaluated once (pass values, other move orders) when both players
         are row-independent compacting evaluators (the float32-accurate BatchedEvaluator); the moves are the same.
         reference_scoring=True reproduces the reference's attribution literally (alphazero.py:206-218): the value of
         getGameEnded for the player who would move NEXT is read as "+1 = first player won, -1 = second player won".
@@ -124,8 +127,10 @@ class Arena:
         opponent's (engine.BatchedMCTS.advance; the reference's two reuse_tree call sites, alphazero.py:346/364), and the
         player's next search tops the kept root up to num_simulations.  Not with literal=True or leaves_per_step > 1."""
         self.game = game
-        opts = options.resolve(num_simulations, leaves_per_step, "aliased" if literal else "copied", tree_reuse=tree_reuse)
+        opts = options.resolve(num_simulations, leaves_per_step, "aliased" if literal else "copied", tree_reuse=tree_reuse,
+                               fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root)
         self.tree_reuse, self.K = opts.tree_reuse, opts.leaves_per_step
+        self.fpu = dict(fpu_reduction=opts.fpu_reduction, fpu_reduction_root=opts.fpu_reduction_root) if opts.fpu_reduction else {}
         self.literal = bool(literal)
         self.evaluation_reuse = bool(evaluation_reuse)
         self.reference_scoring = bool(reference_scoring) or self.literal
@@ -157,7 +162,7 @@ class Arena:
                  and self.K == 1)
         ctx = engine.BatchedMCTS(G, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
                                  aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse,
-                                 leaves_per_step=self.K)
+                                 leaves_per_step=self.K, **self.fpu)
         own = []           # tree_reuse: (the player moves as A, its evaluator's search on its own context)
         try:
             search = LockstepSearch(ctx, dual, use_graph=dense)     # routed mode: the row sets change every move
@@ -166,7 +171,8 @@ class Arena:
                     for par in (0, 1):                               # games par, par + 2, ...: the player has one colour in all of them
                         n = len(range(par, G, 2))
                         if who != "random" and n > 0:
-                            c = engine.BatchedMCTS(n, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev)
+                            c = engine.BatchedMCTS(n, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
+                                                       **self.fpu)
                             own.append((is_a, par, LockstepSearch(c, ev, use_graph=dense)))
             result = torch.zeros(G, dtype=torch.int8, device=dev)   # +1 black won, -1 white won, 2 draw
             ended_at = torch.zeros(G, dtype=torch.float64, device=dev)
@@ -270,8 +276,10 @@ class RandomPlayer:
 class AlphaZeroPlayer:
     """alphazero.py:272-365: network + MCTS behind `play(board, player) -> action` (-1 = no move)."""
 
-    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1, tree_reuse=False):
-        """tree_reuse: play() re-roots the search tree at the move chosen and notify() at the opponent's reply (MCTS tree_reuse),
+    def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1, tree_reuse=False,
+                 fpu_reduction=None, fpu_reduction_root=None):
+        """fpu_reduction / fpu_reduction_root: first-play urgency reduction in the player's searches (MCTS).
+        tree_reuse: play() re-roots the search tree at the move chosen and notify() at the opponent's reply (MCTS tree_reuse),
         so that the next play() continues from the kept subtree."""
         self.game = game
         self.tree_reuse = bool(tree_reuse)
@@ -282,7 +290,7 @@ class AlphaZeroPlayer:
         self.neural_net = net.to(dev).eval()
         self.mcts = MCTS(game, self.neural_net, num_simulations=num_simulations, num_threads=num_threads,
                          board_semantics="copied", device=dev, leaves_per_step=leaves_per_step,
-                         tree_reuse=tree_reuse)
+                         tree_reuse=tree_reuse, fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root)
         self.root = None
 
     def reset(self):
@@ -321,15 +329,17 @@ class AlphaZero:
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None):
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry /
-        symmetry_seed, forced_playouts: options.SearchOptions, for the loop's self-play (SelfPlayManager); leaves_per_step and tree_reuse also
+        symmetry_seed, forced_playouts, fpu_reduction / fpu_reduction_root: options.SearchOptions, for the loop's self-play
+        (SelfPlayManager); leaves_per_step, tree_reuse and fpu_reduction (a playing-strength parameter) also
         for its arena, which always searches num_simulations, plays in lockstep and shows every position to the network in
         its one orientation and without forced playouts (evaluation_symmetry and forced_playouts are self-play options)."""
         self.options = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                                        full_search_probability=full_search_probability, tree_reuse=tree_reuse,
                                        free_running=free_running, evaluation_symmetry=evaluation_symmetry,
-                                       symmetry_seed=symmetry_seed, forced_playouts=forced_playouts)
+                                       symmetry_seed=symmetry_seed, forced_playouts=forced_playouts,
+                                       fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold
@@ -388,7 +398,8 @@ class AlphaZero:
         cur = _load_evaluator(self.game, current_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
-                     leaves_per_step=self.options.leaves_per_step, tree_reuse=self.options.tree_reuse).play(mine)
+                     leaves_per_step=self.options.leaves_per_step, tree_reuse=self.options.tree_reuse,
+                     fpu_reduction=self.options.fpu_reduction, fpu_reduction_root=self.options.fpu_reduction_root).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)
@@ -431,11 +442,14 @@ class AlphaZero:
 
 
 def evaluate_vs_random(game, model_path, num_games=10, num_simulations=800, nn_mode="auto", device=None,
-                       num_channels=128, num_res_blocks=10, leaves_per_step=1, tree_reuse=False):
+                       num_channels=128, num_res_blocks=10, leaves_per_step=1, tree_reuse=False,
+                       fpu_reduction=None, fpu_reduction_root=None):
     """`--mode evaluate` (train_alphazero.py:124-243): the model against RandomPlayer, alternating colours.  leaves_per_step:
-    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search).  tree_reuse: Arena's."""
+    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search).  tree_reuse, fpu_reduction / fpu_reduction_root:
+    Arena's."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     ev = _load_evaluator(game, model_path, dev, nn_mode, num_channels, num_res_blocks)
-    res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse).play(num_games)
+    res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse,
+                fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root).play(num_games)
     return dict(alphazero_wins=res["a_wins"], random_wins=res["b_wins"], draws=res["draws"],
                 win_rate=res["a_wins"] / num_games)

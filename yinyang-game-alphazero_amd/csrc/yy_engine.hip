@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 106
+#define YY_VERSION 107
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -87,6 +87,21 @@ __device__ __forceinline__ uint32_t wave_uadd(uint32_t v) {
     YY_DPP_STEP(uadd32, 0u, v, 0x142, 0xa);
     YY_DPP_STEP(uadd32, 0u, v, 0x143, 0xc);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// The same scan on 64-bit integers (sums modulo 2^64, so two's-complement values add as well): both halves move by the same
+// DPP control, the add carries between them.
+#define YY_DPP_STEP64(v, ctrl, rmask)                                                                                     \
+    v += ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), ctrl, rmask, 0xf, false) << 32) | \
+         (uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, ctrl, rmask, 0xf, false)
+__device__ __forceinline__ uint64_t wave_uadd64(uint64_t v) {
+    YY_DPP_STEP64(v, 0x111, 0xf);
+    YY_DPP_STEP64(v, 0x112, 0xf);
+    YY_DPP_STEP64(v, 0x114, 0xf);
+    YY_DPP_STEP64(v, 0x118, 0xf);
+    YY_DPP_STEP64(v, 0x142, 0xa);
+    YY_DPP_STEP64(v, 0x143, 0xc);
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
 }
 
 // ------------------------------------------------------------------------- stateless kernels
@@ -499,6 +514,37 @@ __device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *s
 // prunes forced playouts with it.  K = 1 passes the edge's N and W, K > 1 the counts with this step's virtual visits
 // (do_select_multi).
 
+// First-play urgency (YY_FLAG_FPU_REDUCTION, include/yy_engine.h): the q an unvisited child of a node is scored with.  Every
+// lane adds its own children (the counts and W that child_key is given: with the virtual visits at K > 1) to a FpuPart; the
+// sums are integers -- W in units of 2^-32, truncated toward zero, P in units of 2^-40 -- so that they do not depend on which
+// lane holds which child.  fpu_value reduces them over the wave, and only when some child is unvisited and some is visited.
+struct FpuPart {
+    uint32_t n = 0;      // sum of N over the children with N > 0
+    int64_t w = 0;       // sum of (int64)(f64(W) * 2^32) over them
+    uint64_t p = 0;      // sum of (uint64)(f64(P) * 2^40) over them
+    bool unvisited = false;
+    __device__ __forceinline__ void add(const float P, const int N, const float W) {
+        if (N > 0) {
+            n += (uint32_t)N;
+            w += (int64_t)__dmul_rn((double)W, 4294967296.0);
+            p += (uint64_t)__dmul_rn((double)P, 1099511627776.0);
+        } else {
+            unvisited = true;
+        }
+    }
+};
+// q_fpu = f32( f32(SW / SN) - f32(r * f32(sqrt(SP))) ); 0 when no child is visited (or none is unvisited: nobody reads it)
+__device__ __forceinline__ float fpu_value(const FpuPart &a, const float r) {
+    if (!__ballot(a.unvisited)) return 0.0f;
+    const uint32_t SN = wave_uadd(a.n);
+    if (SN == 0u) return 0.0f;
+    const int64_t sw = (int64_t)wave_uadd64((uint64_t)a.w);
+    const uint64_t sp = wave_uadd64(a.p);
+    const float SW = (float)__dmul_rn((double)sw, 0x1p-32);
+    const float SP = (float)__dmul_rn((double)sp, 0x1p-40);
+    return __fsub_rn(__fdiv_rn(SW, (float)SN), __fmul_rn(r, __fsqrt_rn(SP)));
+}
+
 // Wave arg-max over the k children of a node: every lane brings the best key `bk` of its own children and that child's index
 // `bi` (BEST_NONE: none).  Returns the child with the largest key, the lowest index among ties = the lowest action
 // (mcts.py:133), or BEST_NONE when no child is selectable (every key 0: NaN scores).
@@ -793,11 +839,22 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             s_carry = (int)rfl(e.y) - 1;
         } else {
             const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
+            // first-play urgency: one more pass over the node's edges for the sums behind the q of its unvisited children
+            // (copied and aliased boards alike).  Wave-uniform branch; without the option q0 stays the reference's 0
+            float q0 = 0.0f;
+            if (d.fpu > 0.0f) {
+                FpuPart fp;
+                for (int j = lane; j < k; j += 64) {
+                    const uint4 e = edges[first + j];
+                    fp.add(__uint_as_float(e.x), (int)e.y, __uint_as_float(e.z));
+                }
+                q0 = fpu_value(fp, depth == 0 ? d.fpu_root : d.fpu);
+            }
             uint32_t bk = 0, bw = 0, bn = 0;
             int bi = BEST_NONE;
             for (int j = lane; j < k; j += 64) {
                 const uint4 e = edges[first + j];
-                const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e.x), (int)e.y, __uint_as_float(e.z));
+                const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e.x), (int)e.y, __uint_as_float(e.z), q0);
                 if (key > bk) { bk = key; bi = j; bw = e.w; bn = e.y; }               // strict >: lowest j of a lane
             }
             best = best_child(bk, bi, k);
@@ -990,6 +1047,19 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
             }
             const int S = (int)wave_uadd(part);                    // sum of the children's N + v (mcts.py:112)
             const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];
+            // first-play urgency on the counts the children are scored with: N + v, and W less the virtual visits
+            float q0 = 0.0f;
+            if (d.fpu > 0.0f) {                                    // wave-uniform
+                FpuPart fp;
+#pragma unroll
+                for (int t = 0; t < NW; t++) {
+                    if (t * 64 + lane < k) {
+                        const float W = __uint_as_float(e[t].z);
+                        fp.add(__uint_as_float(e[t].x), (int)e[t].y + v[t], (v[t] > 0) ? __fsub_rn(W, (float)v[t]) : W);
+                    }
+                }
+                q0 = fpu_value(fp, depth == 0 ? d.fpu_root : d.fpu);
+            }
             uint32_t bk = 0, bw = 0;
             int bi = BEST_NONE;
 #pragma unroll
@@ -998,7 +1068,7 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
                 if (jj < k) {
                     const float W = __uint_as_float(e[t].z);
                     const float w = (v[t] > 0) ? __fsub_rn(W, (float)v[t]) : W;
-                    const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e[t].x), (int)e[t].y + v[t], w);
+                    const uint32_t key = child_key(d.cpuct, sq, __uint_as_float(e[t].x), (int)e[t].y + v[t], w, q0);
                     if (key > bk) { bk = key; bi = jj; bw = e[t].w; }
                 }
             }
@@ -1330,6 +1400,12 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         if (!(cfg->forced_playouts > 0.0 && cfg->forced_playouts < (double)INFINITY))
             return set_err(YY_E_INVALID, "YY_FLAG_FORCED_PLAYOUTS: forced_playouts must be positive and finite%s%s");
     }
+    if (cfg->flags & YY_FLAG_FPU_REDUCTION) {
+        if (!(cfg->fpu_reduction > 0.0f && cfg->fpu_reduction < INFINITY))
+            return set_err(YY_E_INVALID, "YY_FLAG_FPU_REDUCTION: fpu_reduction must be positive and finite%s%s");
+        if (!(cfg->fpu_reduction_root >= 0.0f && cfg->fpu_reduction_root < INFINITY))
+            return set_err(YY_E_INVALID, "YY_FLAG_FPU_REDUCTION: fpu_reduction_root must be finite and >= 0%s%s");
+    }
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
     if (cfg->leaves_per_step > 1) {
@@ -1353,6 +1429,8 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.sym = (cfg->flags & YY_FLAG_EVAL_SYMMETRY) ? 1u : 0u;
     d.sym_seed = d.sym ? cfg->symmetry_seed : 0ull;
     d.forced = (cfg->flags & YY_FLAG_FORCED_PLAYOUTS) ? cfg->forced_playouts : 0.0;
+    d.fpu = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction : 0.0f;
+    d.fpu_root = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction_root : 0.0f;
     m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);

@@ -266,6 +266,9 @@ struct MctsDev {
     // forced playouts with policy target pruning (YY_FLAG_FORCED_PLAYOUTS): k of yy_mcts_config.forced_playouts; 0.0: off, every
     // kernel does what it did without it.  K = 1 and copied boards only (yy_mcts_create)
     double forced;
+    // first-play urgency reduction (YY_FLAG_FPU_REDUCTION): r below the root and r at the root; fpu == 0: off, every kernel
+    // does what it did without it (an unvisited child scores q = 0)
+    float fpu, fpu_root;
 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
@@ -393,17 +396,18 @@ __device__ __forceinline__ uint32_t f32_key(float f) {
 
 // Order-preserving key of one child's PUCT score (mcts.py:120-133), float32 order of SURVEY 8a/a12: the exploration term with
 // `nu` visits, the mean value over `nq`.  Selection scores an edge with nu == nq (child_key); policy target pruning asks what
-// the edge would have scored with fewer visits and its real mean value.
-__device__ __forceinline__ uint32_t child_key_at(float cpuct, float sq, float P, int nu, int nq, float w) {
+// the edge would have scored with fewer visits and its real mean value.  q0: the value an unvisited child (nq == 0) is scored
+// with -- 0 in the reference, the node's first-play urgency with YY_FLAG_FPU_REDUCTION (fpu_value, yy_engine.hip).
+__device__ __forceinline__ uint32_t child_key_at(float cpuct, float sq, float P, int nu, int nq, float w, float q0 = 0.0f) {
     const float t1 = __fmul_rn(cpuct, P);
     const float t2 = __fmul_rn(t1, sq);
     const float u = __fdiv_rn(t2, (float)(1 + nu));
-    const float q = (nq > 0) ? __fdiv_rn(w, (float)nq) : 0.0f;
+    const float q = (nq > 0) ? __fdiv_rn(w, (float)nq) : q0;
     const float ucb = __fadd_rn(__fadd_rn(q, u), 0.0f);   // + 0.0f: -0.0 compares equal to +0.0 (mcts.py:133)
     return f32_key(ucb);
 }
-__device__ __forceinline__ uint32_t child_key(float cpuct, float sq, float P, int n, float w) {
-    return child_key_at(cpuct, sq, P, n, n, w);
+__device__ __forceinline__ uint32_t child_key(float cpuct, float sq, float P, int n, float w, float q0 = 0.0f) {
+    return child_key_at(cpuct, sq, P, n, n, w, q0);
 }
 
 // ------------------------------------------------------------------------------------ forced playouts (YY_FLAG_FORCED_PLAYOUTS)
@@ -447,6 +451,8 @@ __device__ __forceinline__ void prune_forced(const MctsDev &d, const uint4 *edge
         const int n = cn[i];
         const double bound = forced_bound(d.forced, P, S);
         int np = n;
+        // first-play urgency does not enter here: only visited edges are scored (nq == n >= 1), as edge_forced only looks at
+        // visited edges, so forcing and pruning are the same with and without YY_FLAG_FPU_REDUCTION
         for (int m = 0; np >= 1 && __dmul_rn((double)m, (double)m) < bound; m++) {   // m < n_f
             if (child_key_at(d.cpuct, sq, P, np - 1, n, w) < kstar) np -= 1;
             else break;

@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .options import forced_k
-from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from .options import forced_k, fpu_r
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -575,8 +575,13 @@ class BatchedMCTS:
 
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
-                 keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
-        """forced_playouts=k > 0 (copied boards and leaves_per_step == 1 only; None / 0 = off: every launch is what it is without
+                 keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
+                 fpu_reduction=None, fpu_reduction_root=None):
+        """fpu_reduction=r > 0 (None / 0 = off: every launch is what it is without the option; KataGo: 0.2), fpu_reduction_root
+        (None: r; KataGo: 0 at a noised root): first-play urgency reduction (YY_FLAG_FPU_REDUCTION, include/yy_engine.h).  A child
+        that has not been visited is scored with the mean value of its visited siblings less r * sqrt(their share of the prior)
+        instead of q = 0; the root uses fpu_reduction_root.  Every board semantics and leaves_per_step.  Fixed at creation.
+        forced_playouts=k > 0 (copied boards and leaves_per_step == 1 only; None / 0 = off: every launch is what it is without
         the option; KataGo: 2): forced playouts with policy target pruning at the root (YY_FLAG_FORCED_PLAYOUTS, include/yy_engine.h).
         A visited root child is visited again while N * N < k * P * S, and root_policy() is computed from the pruned counts;
         root_counts() stays raw.  Fixed at creation (captured steps hold the context's device view by value).
@@ -605,14 +610,16 @@ class BatchedMCTS:
         self.rows = self.G * self.K            # evaluator rows of a step
         self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
         self.forced_playouts = forced_k(forced_playouts)
+        self.fpu_reduction, self.fpu_reduction_root = fpu_r(fpu_reduction, fpu_reduction_root)
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
                          | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0)
                          | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0)
-                         | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0),
+                         | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0)
+                         | (FLAG_FPU_REDUCTION if self.fpu_reduction else 0),
                          int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
-                         self.forced_playouts)
+                         self.forced_playouts, self.fpu_reduction, self.fpu_reduction_root)
         h = ct.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_create(ct.byref(cfg), ct.byref(h)))

@@ -136,8 +136,11 @@ class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
-                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
-        """forced_playouts=k > 0 (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; None / 0 = off):
+                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
+        """fpu_reduction=r > 0 with fpu_reduction_root (None: r) (not in the reference; None / 0 = off): first-play urgency
+        reduction -- an unvisited child is scored with the mean value of its visited siblings less r * sqrt(their share of the
+        prior) instead of q = 0 (engine.BatchedMCTS); both board semantics, every leaves_per_step.
+        forced_playouts=k > 0 (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; None / 0 = off):
         forced playouts with policy target pruning at the root (engine.BatchedMCTS); the distribution search() returns is the
         pruned one.  The device prunes for temperature 0 and 1 only: a search with any other temperature raises ValueError.
         evaluation_symmetry="random" (not in the reference; needs board_semantics="copied"): every position is shown to the
@@ -167,6 +170,7 @@ class MCTS:
         self.forced_playouts = options.forced_k(forced_playouts)
         if self.forced_playouts:                                # the resolver's refusals: aliased boards, leaves_per_step > 1
             options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts)
+        self.fpu_reduction, self.fpu_reduction_root = options.fpu_r(fpu_reduction, fpu_reduction_root)
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
         self.num_threads = max(1, num_threads)
@@ -193,7 +197,8 @@ class MCTS:
                                      reuse_pass_value=self.evaluation_reuse and self.board_semantics == "copied",
                                      reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
                                      evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
-                                     forced_playouts=self.forced_playouts)
+                                     forced_playouts=self.forced_playouts, fpu_reduction=self.fpu_reduction,
+                                     fpu_reduction_root=self.fpu_reduction_root)
             self._ctx[G] = ctx
         return ctx
 

@@ -73,7 +73,20 @@ class SearchOptions:
     left with one visit is left with none.  Root visit counts (root_counts) stay raw.  Fast and full searches of the playout
     cap alike (KataGo switches it off in fast searches: a follow-up).  It changes which moves a search picks.  The forcing
     test is part of the one-descent selection on copied boards, and the reference has no such option: refused with
-    leaves_per_step > 1, aliased boards, reference_quirks and rng="numpy"."""
+    leaves_per_step > 1, aliased boards, reference_quirks and rng="numpy".
+
+    fpu_reduction r > 0 (KataGo: 0.2) with fpu_reduction_root (None: r; KataGo: 0 at a noised root): first-play urgency reduction
+    in the PUCT selection (include/yy_engine.h YY_FLAG_FPU_REDUCTION).  The reference scores a child that
+    has not been visited with q = 0, which is optimistic where the side to move is losing and pessimistic where it is winning.
+    With the option such a child is scored with the mean value of its visited siblings less r * sqrt(the visited siblings' share
+    of the prior): q_fpu = f32(f32(SW / SN) - f32(r * f32(sqrt(SP)))), the sums in fixed point so that they do not depend on the
+    order of the children; q = 0 as before while no sibling is visited.  The root uses fpu_reduction_root (0: the siblings' mean
+    itself), every node below it fpu_reduction.  Visited children, the exploration term, forced playouts and the pruned policy
+    target are untouched.  It is a playing-strength parameter, so the arena and the evaluation matches take it as well as
+    self-play; it goes with every leaves_per_step, both board semantics, the playout cap, tree reuse, free-running, evaluation
+    symmetry, forced playouts, evaluation reuse and the book (which hold evaluator outputs only).  It changes which moves a
+    search picks.  The reference has no such option: refused with reference_quirks and rng="numpy", which exist for transcript
+    parity with it."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -82,6 +95,8 @@ class SearchOptions:
     evaluation_symmetry: str = "off"
     symmetry_seed: int = None               # None: the engine's seed
     forced_playouts: float = 0.0            # 0.0: off
+    fpu_reduction: float = 0.0              # 0.0: off
+    fpu_reduction_root: float = 0.0         # resolved: fpu_reduction where it was not given; 0.0 when the option is off
 
     @property
     def playout_cap(self):
@@ -96,6 +111,8 @@ class SearchOptions:
             on.update(evaluation_symmetry=self.evaluation_symmetry, symmetry_seed=self.symmetry_seed)
         if self.forced_playouts:
             on.update(forced_playouts=self.forced_playouts)
+        if self.fpu_reduction:
+            on.update(fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
@@ -113,15 +130,39 @@ def forced_k(forced_playouts):
     return k
 
 
+def fpu_r(fpu_reduction, fpu_reduction_root=None):
+    """(r, r_root) as the device takes them: (0.0, 0.0) for fpu_reduction None / 0 (off), else the positive finite r and the
+    root's finite r_root >= 0 (None: r).  OptionConflict naming fpu_reduction for anything else, a root value without the option
+    included."""
+    def num(x):
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            return -1.0
+
+    r = 0.0 if fpu_reduction is None else num(fpu_reduction)
+    if not 0.0 <= r < float("inf"):
+        raise OptionConflict(f"fpu_reduction={fpu_reduction!r}: a finite number >= 0 (0 / None: off; KataGo uses 0.2)", "fpu_reduction")
+    root = (r if fpu_reduction_root is None else num(fpu_reduction_root))
+    if not 0.0 <= root < float("inf"):
+        raise OptionConflict(f"fpu_reduction_root={fpu_reduction_root!r}: a finite number >= 0 (None: fpu_reduction; KataGo uses 0 "
+                             "at a noised root)", "fpu_reduction")
+    if not r and root:
+        raise OptionConflict(f"fpu_reduction_root={fpu_reduction_root!r} without fpu_reduction: the root's value belongs to the "
+                             "option, and fpu_reduction 0 / None switches it off", "fpu_reduction")
+    return r, root
+
+
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
-            free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
+            free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
+            fpu_reduction=None, fpu_reduction_root=None):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step -- so two broken rules name
-    the same option everywhere.  forced_playouts: None and 0 = off."""
+    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction -- so two
+    broken rules name the same option everywhere.  forced_playouts, fpu_reduction: None and 0 = off."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
     if evaluation_symmetry not in ("off", "random"):
@@ -177,7 +218,15 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
         if bad:
             raise OptionConflict(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
                                  f"book -- not with {', '.join(b[1] for b in bad)}", "leaves_per_step", [b[0] for b in bad])
+    fpu, fpu_root = fpu_r(fpu_reduction, fpu_reduction_root)
+    if fpu:
+        bad = [(reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f"fpu_reduction={fpu_reduction}: the reference has no such option, so it does not go with what exists "
+                                 f"for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
+                                 "fpu_reduction", [b[0] for b in bad])
     cap = fast is not None and P < 1.0
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
-                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced)
+                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root)

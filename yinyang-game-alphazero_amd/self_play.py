@@ -88,9 +88,10 @@ class _Engine:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None):
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: `seed`),
-        forced_playouts (the recorded pi and the move draw use the pruned counts; fast and full searches alike)
+        forced_playouts (the recorded pi and the move draw use the pruned counts; fast and full searches alike),
+        fpu_reduction / fpu_reduction_root (first-play urgency reduction in every search, fast and full alike)
         and the mode (free_running): options.SearchOptions; a refused combination raises ValueError before anything touches the
         device.  An opening_book built under another (evaluation_symmetry, symmetry_seed) is refused (ValueError).
         reuse_pass_value / reuse_transpositions / keep_evaluations: None = on when the boards are copied and the evaluator
@@ -111,8 +112,9 @@ class _Engine:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts)
+                               forced_playouts, fpu_reduction, fpu_reduction_root)
         self.K, self.tree_reuse, self.forced_playouts = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts
+        self.fpu_reduction, self.fpu_reduction_root = opts.fpu_reduction, opts.fpu_reduction_root
         self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
@@ -135,7 +137,8 @@ class _Engine:
                                       rowcol=self.rowcol, device=self.device, reuse_pass_value=self.reuse_pass_value,
                                       reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations,
                                       leaves_per_step=self.K, evaluation_symmetry=self.symmetry[0],
-                                      symmetry_seed=self.symmetry[1], forced_playouts=self.forced_playouts)
+                                      symmetry_seed=self.symmetry[1], forced_playouts=self.forced_playouts,
+                                      fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
         self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
@@ -598,15 +601,15 @@ class SelfPlayLanes:
                  first_game_index=0, game_index_stride=1, opening_book=None, board_semantics="copied", reference_quirks=False,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None, **engine_kwargs):
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, **engine_kwargs):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
-        (None: `seed`, the same in every lane), forced_playouts: options.SearchOptions, in every lane; resolved here once, before the book or any
+        (None: `seed`, the same in every lane), forced_playouts, fpu_reduction / fpu_reduction_root: options.SearchOptions, in every lane; resolved here once, before the book or any
         lane is built.  Free-running lanes each run on their own stream and the host alternates their batches of graph replays.
         The other keywords are SelfPlayEngine's."""
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts)
+                               forced_playouts, fpu_reduction, fpu_reduction_root)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -803,9 +806,10 @@ class SelfPlayWorker:
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
-                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
+                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
-        class has no seed of its own), forced_playouts: options.SearchOptions, through MCTS; K > 1, tree_reuse, evaluation_symmetry
+        class has no seed of its own), forced_playouts, fpu_reduction / fpu_reduction_root (needs reference_quirks=False):
+        options.SearchOptions, through MCTS; K > 1, tree_reuse, evaluation_symmetry
         and forced_playouts need board_semantics="copied", K > 1, evaluation_symmetry and forced_playouts also
         reference_quirks=False, which are not this class's defaults.
         free_running: refused (ValueError).  This class plays ONE game at a time through MCTS, drawing from numpy's global
@@ -816,7 +820,8 @@ class SelfPlayWorker:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, fast_simulations=fast_simulations,
                                full_search_probability=full_search_probability, tree_reuse=tree_reuse,
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
-                               forced_playouts=forced_playouts)
+                               forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
+                               fpu_reduction_root=fpu_reduction_root)
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -836,7 +841,8 @@ class SelfPlayWorker:
                          num_threads=num_parallel, board_semantics=board_semantics, device=device,
                          leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse,
                          evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
-                         forced_playouts=opts.forced_playouts)
+                         forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
+                         fpu_reduction_root=opts.fpu_reduction_root)
 
     def play_game(self):
         game, examples = self.game, []
@@ -918,15 +924,18 @@ class SelfPlayManager:
                  mcts_parallel=1, concurrent_games=4096, board_semantics="copied", reference_quirks=False,
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
-                 tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None):
+                 tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
+                 fpu_reduction=None, fpu_reduction_root=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
-        (None: the engine's seed, 1000 + seed, on every rank), forced_playouts: options.SearchOptions.
+        (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root:
+        options.SearchOptions.
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine; off at leaves_per_step > 1, where opening_book_stones=None also means no
         book); False = the network is asked for every leaf like the reference."""
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
-                                       tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts)
+                                       tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
+                                       fpu_reduction, fpu_reduction_root)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -988,7 +997,7 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
-    the other keywords (tree_reuse, free_running and forced_playouts among them) are SelfPlayManager's too."""
+    the other keywords (tree_reuse, free_running, forced_playouts and fpu_reduction / fpu_reduction_root among them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
