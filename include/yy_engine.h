@@ -322,6 +322,31 @@ int yy_mcts_set_book(yy_mcts *ctx, const uint32_t *meta, const uint64_t *keys, c
 /* Forget every cached evaluation (YY_FLAG_REUSE_TRANSPOSITIONS / YY_FLAG_KEEP_EVALUATIONS): to be called when the evaluator
  * (the network) changes between two searches of one context.  Async on `stream`. */
 int yy_mcts_cache_clear(yy_mcts *ctx, yy_stream_t stream);
+/* Shared evaluation table: the dynamic form of the book.  The games of ONE context fill it while they play: every fresh
+ * evaluator row of a non-root leaf is inserted (next to the game's own cache), and a leaf whose position any game of the
+ * context had evaluated in an EARLIER launch takes the stored policy row and value instead of an evaluator row
+ * (counters[7], and hits in yy_mcts_shared_counters).  Lookup order: book, the game's own cache, the shared table.
+ *   meta u32 [slots] (zeroed by the caller; 0 = never used, else the step stamp of the launch that inserted the entry),
+ *   keys u64 [slots, 2*NW], value f32 [slots], policy f32 [slots, A], slots a power of two in 64 .. 2^30,
+ *   stamp u32 [1] in device memory: the step stamp.  The context advances it by one thread in a launch of its own in front
+ *   of every tree-step launch (only while a table is set) and keeps it non-zero; the tree kernel reads it once per wave.
+ * An entry that carries the current stamp is passed over by lookups -- its key and row may still be in flight in another
+ * workgroup -- so everything a lookup trusts was written by a launch that completed earlier on the same stream: the kernel
+ * boundary publishes, and the slot claim (one atomicCAS, as in yy_book_insert) is the only atomic.  Insert-only: no
+ * eviction, no overwrite; a full probe window drops the insert (counted); two games inserting one position in one launch
+ * take two slots.  The arrays stay owned by the caller and must outlive the context (or be unset with meta = NULL); ONE
+ * table belongs to ONE context on ONE stream, and holds the outputs of one evaluator under one symmetry setting.  Set it
+ * with no select pending and before the first step is captured.  YY_E_UNSUPPORTED for YY_FLAG_ALIASED and
+ * leaves_per_step > 1.  yy_mcts_shared_evaluations_clear zeroes the meta of the context's table (async on `stream`): the table
+ * is empty again.  Like the setter it needs a context with no select or root expansion pending (YY_E_STATE otherwise): a
+ * pending leaf may name a slot, and an emptied slot could be claimed and rewritten in the launch that reads it.  A context
+ * armed by yy_selfplay_run_arm stays pending.
+ * yy_mcts_shared_counters (sync; host out [3]): leaves served, rows inserted, inserts dropped, over all games since create
+ * or the last yy_mcts_reset_counters. */
+int yy_mcts_set_shared_evaluations(yy_mcts *ctx, uint32_t *meta, uint64_t *keys, float *value, float *policy, int64_t slots,
+                                   uint32_t *stamp);
+int yy_mcts_shared_evaluations_clear(yy_mcts *ctx, yy_stream_t stream);
+int yy_mcts_shared_counters(yy_mcts *ctx, uint64_t *out);
 
 /* ------------------------------------------------------------------ evaluator epilogue
  * Batched leaf evaluator fast path (the reference evaluates one board per call:

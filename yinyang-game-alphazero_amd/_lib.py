@@ -100,6 +100,9 @@ _SIGS = {
     "yy_mcts_cache_clear": [_vp, _vp],
     "yy_book_insert": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, _vp],
     "yy_mcts_set_book": [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int],
+    "yy_mcts_set_shared_evaluations": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp],
+    "yy_mcts_shared_evaluations_clear": [_vp, _vp],
+    "yy_mcts_shared_counters": [_vp, C.POINTER(C.c_uint64)],
     "yy_nn_bias_act_bf16": [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp],
     "yy_nn_tower_bf16": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_nn_tower_heads_bf16": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],

@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 107
+#define YY_VERSION 108
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -431,21 +431,25 @@ template <int NW> __device__ __forceinline__ PosTable cache_of(const MctsDev &d,
     return PosTable{d.ec.meta + o, d.ec.key + o * 2 * NW, d.ec.val + o, d.ec.pol + o * d.geo.A, d.ec.mask};
 }
 
-// Where a leaf's evaluation comes from (GameState.leaf_src): the evaluator, slot s of the game's cache, slot s of the book
+// Where a leaf's evaluation comes from (GameState.leaf_src): the evaluator, slot s of the game's cache, slot s of the book,
+// slot s of the shared evaluation table (a cache has at most 2^26 slots per game, the shared table at most 2^30)
 #define SRC_NONE (-1)
+#define SRC_SHARED 0x40000000
 __device__ __forceinline__ int src_cache(uint32_t s) { return (int)s; }
 __device__ __forceinline__ int src_book(uint32_t s) { return -2 - (int)s; }
+__device__ __forceinline__ int src_shared(uint32_t s) { return (int)s | SRC_SHARED; }
 
 // Evaluation cache: the evaluator is a function of the position alone (the planes encode the board, not the side to move),
 // so a position it has already seen -- another move order inside this search, a pass node visited again, with
 // YY_FLAG_KEEP_EVALUATIONS an earlier search of the same game, or one of the book -- needs no evaluator row: the stored
 // policy row and value ARE this leaf's evaluation.  Returns the leaf_src of the position (black, white); on SRC_NONE with a
-// cache, `slot` is where cache_store puts the fresh evaluation (else -1).
+// cache, `slot` is where cache_store puts the fresh evaluation (else -1).  The order is book, the game's own cache, the shared
+// table; `stamp` is the step stamp of this launch (shared table only).
 template <int NW>
 __device__ __forceinline__ int leaf_lookup(const MctsDev &d, const GameState *st, const int g, BB<NW> black, BB<NW> white,
-                                           int &slot) {
+                                           int &slot, const uint32_t stamp) {
     slot = -1;
-    if (!d.ec.meta && !d.bk.meta) return SRC_NONE;
+    if (!d.ec.meta && !d.bk.meta && !d.sh.meta) return SRC_NONE;
     const uint64_t h = bb_hash<NW>(black.w, white.w);
     // the shared book: positions of the first plies evaluated once for ALL games before play; read-only
     if (d.bk.meta && pos_stones<NW>(black, white) <= d.bk_stones) {
@@ -455,21 +459,36 @@ __device__ __forceinline__ int leaf_lookup(const MctsDev &d, const GameState *st
         });
         if (at >= 0) return src_book((uint32_t)at);
     }
-    if (!d.ec.meta) return SRC_NONE;
-    const PosTable t = cache_of<NW>(d, g);
-    const uint32_t ep = (uint32_t)rfl((int)st->ec_epoch);
-    const int rstones = rfl(st->root_stones);
-    const int at = tt_probe(h, t.mask, [&](uint32_t at) {
-        const uint32_t m = (uint32_t)rfl((int)t.meta[at]);
-        if (m == 0u) { if (slot < 0) slot = (int)at; return TT_MISS; }             // never used: the position is not in the table
-        const bool cur = (m >> 8) == ep;
-        if ((cur || d.ec_keep) && tt_key_is<NW>(t, at, black, white)) return TT_HIT;
-        // replaceable: another epoch, or a position that cannot come back (a leaf has more stones than the root)
-        if (slot < 0 && (!cur || (int)(m & 0xFFu) <= rstones)) slot = (int)at;
-        return TT_NEXT;
-    });
-    if (slot < 0) slot = (int)tt_first(h, t.mask);                                 // every probed entry is live: replace the first
-    return at >= 0 ? src_cache((uint32_t)at) : SRC_NONE;
+    if (d.ec.meta) {
+        const PosTable t = cache_of<NW>(d, g);
+        const uint32_t ep = (uint32_t)rfl((int)st->ec_epoch);
+        const int rstones = rfl(st->root_stones);
+        const int at = tt_probe(h, t.mask, [&](uint32_t at) {
+            const uint32_t m = (uint32_t)rfl((int)t.meta[at]);
+            if (m == 0u) { if (slot < 0) slot = (int)at; return TT_MISS; }         // never used: the position is not in the table
+            const bool cur = (m >> 8) == ep;
+            if ((cur || d.ec_keep) && tt_key_is<NW>(t, at, black, white)) return TT_HIT;
+            // replaceable: another epoch, or a position that cannot come back (a leaf has more stones than the root)
+            if (slot < 0 && (!cur || (int)(m & 0xFFu) <= rstones)) slot = (int)at;
+            return TT_NEXT;
+        });
+        if (slot < 0) slot = (int)tt_first(h, t.mask);                             // every probed entry is live: replace the first
+        if (at >= 0) return src_cache((uint32_t)at);
+    }
+    // the shared evaluation table: what any game of the context had evaluated in an EARLIER launch.  An entry that carries this
+    // launch's stamp is passed over -- another workgroup may still be writing its key and row, and nothing of this launch has
+    // been published (no fence, no acquire: the kernel boundary publishes) -- so everything trusted here was complete before
+    // this launch began.  A stale 0 read for a slot claimed in this launch ends the probe one entry early: a miss, never a wrong hit
+    if (d.sh.meta) {
+        const int at = tt_probe(h, d.sh.mask, [&](uint32_t at) {
+            const uint32_t m = (uint32_t)rfl((int)d.sh.meta[at]);
+            if (m == 0u) return TT_MISS;
+            if (m == stamp) return TT_NEXT;
+            return tt_key_is<NW>(d.sh, at, black, white) ? TT_HIT : TT_NEXT;
+        });
+        if (at >= 0) return src_shared((uint32_t)at);
+    }
+    return SRC_NONE;
 }
 
 // the evaluation of game g's pending leaf: its policy row and value, from the evaluator's row g or the slot `src` names.
@@ -479,6 +498,10 @@ template <int NW>
 __device__ __forceinline__ LeafEval leaf_eval(const MctsDev &d, const int g, const int src, const float *policy,
                                               const float *value) {
     if (src == SRC_NONE) return LeafEval{policy + (size_t)g * d.geo.A, value ? rflf(value[g]) : 0.0f};
+    if (src >= SRC_SHARED) {                                                       // only ever set with a shared table
+        const size_t s = (size_t)(src - SRC_SHARED);
+        return LeafEval{d.sh.pol + s * d.geo.A, rflf(d.sh.val[s])};
+    }
     const bool book = src < SRC_NONE;
     const PosTable t = book ? d.bk : cache_of<NW>(d, g);
     const size_t s = (size_t)(book ? -2 - src : src);
@@ -503,6 +526,40 @@ __device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *s
         for (int i = 0; i < 2 * NW; i++) t.key[slot * 2 * NW + i] = board[i];
         t.val[slot] = v;
         t.meta[slot] = (st->ec_epoch << 8) | (uint32_t)(pos_stones<NW>(bb_load<NW>(board), bb_load<NW>(board + NW)) & 0xFF);
+    }
+}
+
+// The same fresh evaluation goes into the shared table: lane 0 claims the first slot of the probe window that nobody has ever
+// used (the one atomic of the option, as in k_book_insert), stamped with this launch's stamp so that no lookup of this launch
+// trusts it; key, value and row follow as plain stores, published by the end of the launch.  Insert-only: a claimed slot is
+// never written again, a full window drops the row.  Two games that insert one position in one launch take two slots.
+template <int NW>
+__device__ __forceinline__ void shared_store(const MctsDev &d, GameState *st, const int g, const float *policy, const float v,
+                                             const uint32_t stamp) {
+    const int lane = lane_id(), A = d.geo.A;
+    const uint64_t *board = st->leaf.board;
+    int got = -1;
+    if (lane == 0) {
+        // a slot that a plain load already shows taken stays taken (insert-only), so it costs no atomic: once the table is full
+        // a dropped row is eight loads.  A stale 0 is settled by the atomicCAS that follows
+        got = tt_probe(bb_hash<NW>(board, board + NW), d.sh.mask, [&](uint32_t at) {
+            if (d.sh.meta[at] != 0u) return TT_NEXT;
+            return atomicCAS(&d.sh.meta[at], 0u, stamp) == 0u ? TT_HIT : TT_NEXT;
+        });
+        st->shc[got >= 0 ? 1 : 2] += 1;
+    }
+    got = rfl(got);
+    if (got < 0) return;
+    const size_t slot = (size_t)got;
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const int cell = j * 64 + lane;
+        if (cell < A) d.sh.pol[slot * A + cell] = policy[(size_t)g * A + cell];
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 2 * NW; i++) d.sh.key[slot * 2 * NW + i] = board[i];
+        d.sh.val[slot] = v;
     }
 }
 
@@ -765,7 +822,8 @@ template <int NW> __global__ void __launch_bounds__(64) k_begin(MctsDev d, Multi
 
 // ---- selection: mcts.py:356-362 (descent), 385-391 (state of the leaf), 63-71 (its rules)
 template <int NW>
-__device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *planes, uint8_t *needs_eval) {
+__device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *planes, uint8_t *needs_eval,
+                                          const uint32_t stamp) {
     GameState *st = d.state + g;
     const int lane = lane_id();
     // a game whose root has had its budget of simulations selects nothing, like an inactive one: no arena, no counter.  The
@@ -894,7 +952,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         float tv;
         leaf_rules<NW>(d.geo, gb, black, white, lplayer, mask, term, tv);
         int slot;
-        const int src = leaf_lookup<NW>(d, st, g, black, white, slot);
+        const int src = leaf_lookup<NW>(d, st, g, black, white, slot, stamp);
         if (src == SRC_NONE) write_eval_planes<NW>(planes + (size_t)g * 5 * d.geo.A, d.geo, d.sym, d.sym_seed, black, white);
         leaf_store<NW>(&st->leaf, black, white, mask, lplayer, term, tv);
         if (lane == 0) {
@@ -902,7 +960,10 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             st->leaf_ec_slot = slot;
         }
         need = src == SRC_NONE;
-        if (!need && lane == 0) st->ctr[7] += 1;
+        if (!need && lane == 0) {
+            st->ctr[7] += 1;
+            if (src >= SRC_SHARED) st->shc[0] += 1;
+        }
     }
     if (lane == 0) {
         st->leaf.kind = (uint8_t)kind;
@@ -944,7 +1005,8 @@ __device__ __forceinline__ void noise_kept_root(const MctsDev &d, const int g, c
 // ---- expansion + backup: mcts.py:50-91 (expand_leaf), 147-156 + 406-412 (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, const float *policy,
-                                                 const float *value, const double *noise, const double eps) {
+                                                 const float *value, const double *noise, const double eps,
+                                                 const uint32_t stamp) {
     GameState *st = d.state + g;
     const int lane = lane_id();
     const int kind = rfl((int)st->leaf.kind);
@@ -969,7 +1031,7 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
     } else {
         // the root call of mcts.py:288 looks nothing up, and its value is discarded: yy_mcts_expand_root is not given it
         const bool root = kind == K_ROOTINIT;
-        const int src = (root || !(d.ec.meta || d.bk.meta)) ? SRC_NONE : rfl(st->leaf_src);
+        const int src = (root || !(d.ec.meta || d.bk.meta || d.sh.meta)) ? SRC_NONE : rfl(st->leaf_src);
         const LeafEval ev = leaf_eval<NW>(d, g, src, policy, root ? nullptr : value);
         v = ev.v;
         const bool hold = d.reuse && !root;   // a pass node keeps its value; a pass root that of its first simulation
@@ -979,6 +1041,7 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
             return;
         }
         if (d.ec.meta && src == SRC_NONE && !root) cache_store<NW>(d, st, g, policy, v);
+        if (d.sh.meta && src == SRC_NONE && !root) shared_store<NW>(d, st, g, policy, v, stamp);
     }
     if (lane == 0) st->leaf.kind = K_NONE;
     if (kind == K_ROOTINIT) return;                                                 // no backup
@@ -990,9 +1053,20 @@ template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do
                                                                const double *noise, double eps, float *planes,
                                                                uint8_t *needs_eval) {
     const int g = blockIdx.x;
-    if (do_backup) do_expand_backup<NW>(d, g, policy, value, noise, eps);
+    // the step stamp of this launch, read once per wave: k_stamp advanced it in front of this launch (launch_mcts)
+    const uint32_t stamp = d.sh.meta ? rfl(*d.sh_stamp) : 0u;
+    if (do_backup) do_expand_backup<NW>(d, g, policy, value, noise, eps, stamp);
     if (do_backup && do_sel) __syncthreads();   // edges/nodes written above are re-read below by other lanes
-    if (do_sel) do_select<NW>(d, g, planes, needs_eval);
+    if (do_sel) do_select<NW>(d, g, planes, needs_eval, stamp);
+}
+
+// The step stamp of the shared evaluation table: one thread, in a launch of its own between two tree-step launches of the
+// context's stream, so that every tree-step launch has a stamp of its own.  Never 0 (0 marks a slot nobody has used).  The
+// stamp lives in device memory: a captured step freezes its arguments.
+__global__ void k_stamp(uint32_t *stamp) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t s = *stamp + 1u;
+    *stamp = s ? s : 1u;
 }
 
 // =============================================================================== leaf-parallel steps (K > 1)
@@ -1375,6 +1449,7 @@ __global__ void k_reset_counters(MctsDev d) {
     if (g >= d.G) return;
     for (int i = 0; i < 8; i++) d.state[g].ctr[i] = 0;
     d.state[g].forced = 0;
+    for (int i = 0; i < 3; i++) d.state[g].shc[i] = 0;
 }
 
 __global__ void k_forced_sum(MctsDev d, uint64_t *out) {
@@ -1558,6 +1633,11 @@ extern "C" int yy_mcts_advance(yy_mcts *c, const int32_t *actions, int32_t *kept
 
 static int launch_mcts(yy_mcts *c, int backup, int sel, const float *policy, const float *value, const double *noise,
                        double eps, float *planes, uint8_t *needs_eval, yy_stream_t s) {
+    // shared evaluation table: every tree-step launch gets a stamp of its own; without the table nothing is launched here
+    if (c->dev.sh.meta) {
+        hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, (hipStream_t)s, c->dev.sh_stamp);
+        HIP_TRY(hipGetLastError());
+    }
     if (c->multi.K > 1) {
         DISPATCH_NW(c->dev.geo.NW, k_mcts_multi<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi, backup, sel,
                                                        policy, value, noise, eps, planes, needs_eval));
@@ -1699,6 +1779,51 @@ extern "C" int yy_mcts_set_book(yy_mcts *c, const uint32_t *meta, const uint64_t
     // the caller's arrays are only read through this table (leaf_lookup, leaf_eval)
     c->dev.bk = PosTable{(uint32_t *)meta, (uint64_t *)keys, (float *)val, (float *)pol, (uint32_t)(cap - 1)};
     c->dev.bk_stones = max_stones;
+    return YY_OK;
+}
+
+// ---- shared evaluation table (MctsDev.sh)
+extern "C" int yy_mcts_set_shared_evaluations(yy_mcts *c, uint32_t *meta, uint64_t *keys, float *val, float *pol, int64_t slots,
+                                              uint32_t *stamp) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    // a pending leaf may name a slot of the table that is set now (GameState.leaf_src)
+    if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_set_shared_evaluations with a select or a root expansion pending%s%s");
+    if (!meta) { c->dev.sh = PosTable{}; c->dev.sh_stamp = nullptr; return YY_OK; }
+    if (c->cfg.flags & YY_FLAG_ALIASED)
+        return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_shared_evaluations needs copied boards (YY_FLAG_ALIASED reproduces the reference, which asks the network for every leaf)%s%s");
+    if (c->multi.K > 1)
+        return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_shared_evaluations: leaves_per_step > 1 does not support evaluation reuse%s%s");
+    if (!keys || !val || !pol || !stamp || slots < 64 || (slots & (slots - 1)) || slots > (1ll << 30))
+        return set_err(YY_E_INVALID, "yy_mcts_set_shared_evaluations: bad argument (slots must be a power of two in 64 .. 2^30)%s%s");
+    c->dev.sh = PosTable{meta, keys, val, pol, (uint32_t)(slots - 1)};
+    c->dev.sh_stamp = stamp;
+    return YY_OK;
+}
+
+__global__ void k_shared_sum(MctsDev d, uint64_t *out) {
+    uint64_t acc[3] = {0, 0, 0};
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x)
+        for (int i = 0; i < 3; i++) acc[i] += d.state[g].shc[i];
+    for (int i = 0; i < 3; i++)
+        if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
+}
+
+extern "C" int yy_mcts_shared_counters(yy_mcts *c, uint64_t *out) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(c->scratch, 0, 3 * sizeof(uint64_t)));
+    hipLaunchKernelGGL(k_shared_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, c->scratch, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_shared_evaluations_clear(yy_mcts *c, yy_stream_t s) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    // a pending leaf may name a slot (GameState.leaf_src): emptied, another game could claim and rewrite it in the launch that reads it
+    if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_shared_evaluations_clear with a select or a root expansion pending%s%s");
+    const PosTable &sh = c->dev.sh;
+    if (sh.meta) HIP_TRY(hipMemsetAsync(sh.meta, 0, ((size_t)sh.mask + 1) * sizeof(uint32_t), (hipStream_t)s));
     return YY_OK;
 }
 

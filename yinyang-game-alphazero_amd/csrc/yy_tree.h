@@ -218,7 +218,8 @@ struct GameState {
     uint8_t kept;           // yy_mcts_advance left this game's tree re-rooted at node 0; consumed by the next yy_mcts_begin
     uint8_t root_kept;      // the root of the current search is a kept node: its own first visit expanded it, so its children's
                             // visits sum to root_N - 1 (a fresh root's: root_N)
-    int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot)
+    int32_t leaf_src;       // where this leaf's evaluation comes from: SRC_NONE (an evaluator row), src_cache(slot), src_book(slot),
+                            // src_shared(slot)
     int32_t leaf_ec_slot;   // leaf_src == SRC_NONE: the cache slot this leaf's evaluation goes into
     uint32_t ec_epoch;      // entries of other epochs are replaceable (see root_setup)
     int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
@@ -226,12 +227,13 @@ struct GameState {
     LeafRec leaf;           // K = 1: the pending leaf
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
     uint64_t forced;        // forced playouts: root descents that took a forced edge, since create / yy_mcts_reset_counters
+    uint64_t shc[3];        // shared evaluation table: leaves it served, rows inserted, inserts dropped (probe window full)
 };
 
 // A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
 // game g's evaluation cache another (cache_of: a slice of the context's ec arrays).
 struct PosTable {
-    uint32_t *meta;         // [slots]  0 = never used; cache: epoch << 8 | stones, book: 1
+    uint32_t *meta;         // [slots]  0 = never used; cache: epoch << 8 | stones, book: 1, shared table: the inserting launch's stamp
     uint64_t *key;          // [slots, 2*NW]  the position
     float *val;             // [slots]  the evaluator's value
     float *pol;             // [slots, A]  the evaluator's policy row
@@ -256,6 +258,11 @@ struct MctsDev {
     // shared book of pre-evaluated positions (yy_mcts_set_book; arrays owned by the caller, read-only here); meta == nullptr: none
     PosTable bk;
     int32_t bk_stones;
+    // shared evaluation table (yy_mcts_set_shared_evaluations; arrays owned by the caller): what any game of the context had
+    // evaluated in an EARLIER launch serves every game; insert-only.  meta == nullptr: off, every kernel does what it did
+    // without it.  *sh_stamp: the step stamp, never 0, advanced by k_stamp in front of every tree-step launch
+    PosTable sh;
+    uint32_t *sh_stamp;
     GameState *state;
     float *sqrt_tab;
     int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .options import forced_k, fpu_r
+from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, forced_k, fpu_r, shared_slots
 from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
@@ -565,6 +565,61 @@ class OpeningBook:
         self.bytes = sum(t.numel() * t.element_size() for t in (self.meta, self.table_keys, self.value, self.policy))
 
 
+# ------------------------------------------------------------------ shared evaluation table: the book the games write themselves
+class SharedEvaluations:
+    """A shared evaluation table (include/yy_engine.h, yy_mcts_set_shared_evaluations): an open-addressing table in HBM
+    [position -> policy row f32[A], value] that the games of ONE BatchedMCTS context fill while they play.  Every fresh
+    evaluator row of a non-root leaf is inserted, and a leaf whose position any game of the context had evaluated in an earlier
+    launch is served from it without an evaluator row -- the opening book's sharing between games without its build phase,
+    stone limit or board-size limit, paid for only in positions that were visited.  Insert-only: no eviction; a full probe
+    window drops the insert.  One table per context (never two contexts or two streams on one table), one network and one
+    (evaluation_symmetry, symmetry_seed) per table: `symmetry` is compared by BatchedMCTS.set_shared_evaluations, and
+    clear() is the caller's job when the network changes.
+    slots: rounded up to a power of two; None = SHARED_EVALUATIONS_DEFAULT_SLOTS = 2^23, which at 8x8 costs what the 8-stone
+    opening book costs (2.3 GB) -- a starting point, not a measured optimum."""
+
+    COUNTERS = ("hits", "inserts", "dropped")
+
+    def __init__(self, rows, cols, slots=None, device=None, evaluation_symmetry="off", symmetry_seed=None):
+        self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.R, self.C, self.A = int(rows), int(cols), int(rows) * int(cols)
+        self.slots = shared_slots(True if slots is None else slots)
+        if not self.slots:
+            raise ValueError("SharedEvaluations: slots must be positive")
+        nw, dev = (self.A + 63) // 64, self.device
+        self.meta = torch.zeros(self.slots, dtype=torch.int32, device=dev)
+        self.keys = torch.empty((self.slots, 2 * nw), dtype=torch.int64, device=dev)
+        self.value = torch.empty(self.slots, dtype=torch.float32, device=dev)
+        self.policy = torch.empty((self.slots, self.A), dtype=torch.float32, device=dev)
+        self.stamp = torch.ones(1, dtype=torch.int32, device=dev)        # the step stamp: never 0, advanced on the device
+        self.ctx = None                                                   # the one context that reads and writes the table
+
+    @property
+    def memory_bytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.meta, self.keys, self.value, self.policy, self.stamp))
+
+    def clear(self):
+        """Empty the table (asynchronous, on the current stream: call it on the stream of the table's context).  Through the
+        context that holds the table, which refuses while a search is in progress (a pending leaf may name a slot); a
+        context armed for a free-running run stays in that state."""
+        if self.ctx is None:
+            self.meta.zero_()
+            return
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_shared_evaluations_clear(self.ctx._h, _stream()))
+
+    def fill(self):
+        """sync; slots in use."""
+        return int((self.meta != 0).sum())
+
+    def counters(self):
+        """sync; {hits, inserts, dropped} of the table's context since it was made / its last reset_counters()."""
+        if self.ctx is None:
+            return dict.fromkeys(self.COUNTERS, 0)
+        return self.ctx.shared_counters()
+
+
 # ------------------------------------------------------------------ batched MCTS context
 class BatchedMCTS:
     """G games searched in lockstep on one GPU; replaces Node + MCTS.search/_simulate
@@ -629,6 +684,7 @@ class BatchedMCTS:
         self._num_sims = self.max_sims
         self._budgets = None                   # device int32 [G] the next begin() reads (set_sim_budgets); None: the scalar
         self.book, self.book_version, self._evaluator_owner = None, 0, None
+        self.shared = None                     # engine.SharedEvaluations (set_shared_evaluations)
 
     # -- lifetime
     def close(self):
@@ -636,6 +692,9 @@ class BatchedMCTS:
             torch.cuda.synchronize(self.device)
             lib().yy_mcts_destroy(self._h)
             self._h = None
+        if getattr(self, "shared", None) is not None:      # table and context name each other: let go, so the arrays are freed now
+            self.shared.ctx = None
+            self.shared = None
 
     def __del__(self):
         try:
@@ -793,16 +852,56 @@ class BatchedMCTS:
         self.book = book
         self.book_version += 1      # captured steps hold the table's pointers: LockstepSearch re-captures
 
+    def set_shared_evaluations(self, table):
+        """The games of this context share their evaluations through `table` (SharedEvaluations, or None to unset): every fresh
+        evaluator row is inserted, and leaves are looked up there after the book and the game's own cache.  Copied boards and
+        leaves_per_step == 1 only; with no search in progress, and before steps are captured (captured steps hold the table's
+        pointers: LockstepSearch re-captures).  A table belongs to one context; one built for another board or under another
+        (evaluation_symmetry, symmetry_seed) is refused (ValueError)."""
+        if table is not None:
+            if (table.R, table.C) != (self.R, self.C):
+                raise ValueError("the shared evaluation table was built for another board size")
+            if table.symmetry != self.symmetry:
+                raise ValueError(f"the shared evaluation table was built with (evaluation_symmetry, symmetry_seed) = {table.symmetry}, "
+                                 f"this context evaluates with {self.symmetry}: its rows are in another frame")
+            if table.ctx is not None and table.ctx is not self:
+                raise ValueError("the shared evaluation table belongs to another context: one table per context (two contexts on "
+                                 "two streams would read each other's unfinished entries)")
+            if table.device != self.device:
+                raise ValueError("the shared evaluation table lives on another device")
+        with torch.cuda.device(self.device):
+            if table is None:
+                check(lib().yy_mcts_set_shared_evaluations(self._h, None, None, None, None, 0, None))
+            else:
+                check(lib().yy_mcts_set_shared_evaluations(self._h, _p(table.meta), _p(table.keys), _p(table.value), _p(table.policy),
+                                                           table.slots, _p(table.stamp)))
+        if self.shared is not None and self.shared is not table:
+            self.shared.ctx = None
+        if table is not None:
+            table.ctx = self
+        self.shared = table
+        self.book_version += 1      # captured steps hold the table's pointers, like the book's
+
+    def shared_counters(self):
+        """sync; shared evaluation table: {hits, inserts, dropped} over all games since create / reset_counters()."""
+        ctr = (ct.c_uint64 * 3)()
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_shared_counters(self._h, ctr))
+        return dict(zip(SharedEvaluations.COUNTERS, [int(x) for x in ctr[:3]]))
+
     def bind_evaluator(self, evaluator):
         """Evaluations kept across searches (keep_evaluations) and the opening book are results of ONE network: the engine-level
         searches (search.LockstepSearch: SelfPlayEngine, MCTS, Arena) bind the context to their evaluator object; a search with
-        another one clears the cache and drops the book instead of silently mixing two networks' numbers.  The low-level
+        another one clears the cache, drops the book and empties the shared evaluation table instead of silently mixing two
+        networks' numbers.  The low-level
         search() below takes any callable per call and does not bind: there clear_evaluation_cache() is the caller's job."""
         if self._evaluator_owner is not None and self._evaluator_owner is not evaluator:
             if self.keep_evaluations:
                 self.clear_evaluation_cache()
             if self.book is not None:
                 self.set_book(None)
+            if self.shared is not None:
+                self.shared.clear()
         self._evaluator_owner = evaluator
 
     def clear_evaluation_cache(self):

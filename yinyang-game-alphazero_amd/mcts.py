@@ -136,8 +136,15 @@ class MCTS:
     def __init__(self, game, neural_net, num_simulations=800, cpuct=1.0, temperature=1.0, num_threads=1,
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
-                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
-        """fpu_reduction=r > 0 with fpu_reduction_root (None: r) (not in the reference; None / 0 = off): first-play urgency
+                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
+                 shared_evaluations=None):
+        """shared_evaluations (not in the reference; None / False = off, True = the default size, an int = slots): the searches
+        of a context share their evaluations through an engine.SharedEvaluations table -- a position evaluated in an earlier
+        step of any game of the batch, or in an earlier search, needs no evaluator row again; same results.  Needs
+        board_semantics="copied", leaves_per_step == 1 and an evaluator that declares `row_independent` (network.BatchedEvaluator
+        in its float32-accurate modes; a search with any other evaluator raises ValueError); the table is emptied when the
+        network object changes.
+        fpu_reduction=r > 0 with fpu_reduction_root (None: r) (not in the reference; None / 0 = off): first-play urgency
         reduction -- an unvisited child is scored with the mean value of its visited siblings less r * sqrt(their share of the
         prior) instead of q = 0 (engine.BatchedMCTS); both board semantics, every leaves_per_step.
         forced_playouts=k > 0 (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; None / 0 = off):
@@ -171,6 +178,11 @@ class MCTS:
         if self.forced_playouts:                                # the resolver's refusals: aliased boards, leaves_per_step > 1
             options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts)
         self.fpu_reduction, self.fpu_reduction_root = options.fpu_r(fpu_reduction, fpu_reduction_root)
+        # the resolver's refusals: aliased boards, leaves_per_step > 1
+        self.shared_evaluations = options.shared_slots(shared_evaluations)
+        if self.shared_evaluations:
+            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, shared_evaluations=shared_evaluations)
+        self._shared_owner = None              # the network whose rows the tables hold
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
         self.num_threads = max(1, num_threads)
@@ -199,7 +211,15 @@ class MCTS:
                                      evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
                                      forced_playouts=self.forced_playouts, fpu_reduction=self.fpu_reduction,
                                      fpu_reduction_root=self.fpu_reduction_root)
+            if self.shared_evaluations:
+                ctx.set_shared_evaluations(engine.SharedEvaluations(self.R, self.C, self.shared_evaluations, ctx.device,
+                                                                    *self.symmetry))
             self._ctx[G] = ctx
+        if ctx.shared is not None and self._shared_owner is not self.neural_net:
+            if self._shared_owner is not None:                   # another network: its rows are not this one's
+                for c in self._ctx.values():
+                    c.shared.clear()
+            self._shared_owner = self.neural_net
         return ctx
 
     def _capturable(self, ev):
@@ -223,6 +243,9 @@ class MCTS:
         budget per game (engine.BatchedMCTS.run_search), none above the constructor's num_simulations."""
         ctx = self._context(boards.shape[0])
         ev = self._evaluator(ctx)
+        if self.shared_evaluations and not getattr(ev, "row_independent", False):
+            raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
+                             "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
         sims = self.num_simulations if num_simulations is None else num_simulations
         if not isinstance(sims, (int, np.integer)):
             sims = np.asarray(sims.cpu() if isinstance(sims, torch.Tensor) else sims)

@@ -86,7 +86,21 @@ class SearchOptions:
     self-play; it goes with every leaves_per_step, both board semantics, the playout cap, tree reuse, free-running, evaluation
     symmetry, forced playouts, evaluation reuse and the book (which hold evaluator outputs only).  It changes which moves a
     search picks.  The reference has no such option: refused with reference_quirks and rng="numpy", which exist for transcript
-    parity with it."""
+    parity with it.
+
+    shared_evaluations (True: SHARED_EVALUATIONS_DEFAULT_SLOTS slots, or a slot count, rounded up to a power of two; resolved
+    to the slot count, 0: off): a shared evaluation table per tree context (engine.SharedEvaluations; include/yy_engine.h
+    yy_mcts_set_shared_evaluations).  The per-game evaluation cache serves a position twice only inside the
+    game that asked for it, and the opening book shares between games only what was enumerated before play.  With the option
+    every fresh evaluator row also goes into a table of the context, and a leaf whose position ANY game of the context had
+    evaluated in an earlier launch takes its row from there: no build phase, no stone limit, every board the tree kernels
+    cover, memory for visited positions only (insert-only; a full probe window drops the insert).  The games played are the
+    same, move for move; the evaluator sees fewer rows.  The default size costs at 8x8 what the 8-stone book costs (2.3 GB per
+    context): a starting point, not a measured optimum.  Like evaluation_reuse="auto" it needs an evaluator that declares
+    `row_independent` (ValueError otherwise, where the evaluator is known), copied boards and one descent per step: refused
+    with board_semantics="aliased", leaves_per_step > 1 and reference_quirks.  It goes with evaluation reuse on or off, the
+    book, the playout cap, tree reuse, free-running, evaluation symmetry (the table is tied to (mode, seed) like the book),
+    forced playouts and fpu_reduction.  Every lane of SelfPlayLanes has a table of its own."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -97,6 +111,7 @@ class SearchOptions:
     forced_playouts: float = 0.0            # 0.0: off
     fpu_reduction: float = 0.0              # 0.0: off
     fpu_reduction_root: float = 0.0         # resolved: fpu_reduction where it was not given; 0.0 when the option is off
+    shared_evaluations: int = 0             # slots of the shared evaluation table (a power of two); 0: off
 
     @property
     def playout_cap(self):
@@ -113,6 +128,8 @@ class SearchOptions:
             on.update(forced_playouts=self.forced_playouts)
         if self.fpu_reduction:
             on.update(fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
+        if self.shared_evaluations:
+            on.update(shared_evaluations=self.shared_evaluations)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
@@ -128,6 +145,31 @@ def forced_k(forced_playouts):
     if not 0.0 <= k < float("inf"):
         raise OptionConflict(f"forced_playouts={forced_playouts!r}: a finite number >= 0 (0 / None: off; KataGo uses 2)", "forced_playouts")
     return k
+
+
+SHARED_EVALUATIONS_DEFAULT_SLOTS = 1 << 23   # 8x8: 280 bytes a slot = 2.3 GB, the 8-stone opening book's size
+
+
+def shared_slots(shared_evaluations):
+    """shared_evaluations as the device takes it: 0 for None / False (off), SHARED_EVALUATIONS_DEFAULT_SLOTS for True, an int
+    slot count rounded up to a power of two (at least 64, at most 2^30).  OptionConflict for anything else."""
+    if shared_evaluations is None or shared_evaluations is False:
+        return 0
+    if shared_evaluations is True:
+        return SHARED_EVALUATIONS_DEFAULT_SLOTS
+    try:
+        n = int(shared_evaluations)
+        if n != shared_evaluations:
+            n = -1
+    except (TypeError, ValueError):
+        n = -1
+    if not 0 < n <= 1 << 30:
+        raise OptionConflict(f"shared_evaluations={shared_evaluations!r}: None / False (off), True (the default size) or a slot "
+                             "count in 1 .. 2^30", "shared_evaluations")
+    slots = 64
+    while slots < n:
+        slots *= 2
+    return slots
 
 
 def fpu_r(fpu_reduction, fpu_reduction_root=None):
@@ -156,13 +198,14 @@ def fpu_r(fpu_reduction, fpu_reduction_root=None):
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-            fpu_reduction=None, fpu_reduction_root=None):
+            fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction -- so two
-    broken rules name the same option everywhere.  forced_playouts, fpu_reduction: None and 0 = off."""
+    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
+    shared_evaluations -- so two broken rules name the same option everywhere.  forced_playouts, fpu_reduction: None and 0 = off;
+    shared_evaluations: None and False = off."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
     if evaluation_symmetry not in ("off", "random"):
@@ -226,7 +269,18 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             raise OptionConflict(f"fpu_reduction={fpu_reduction}: the reference has no such option, so it does not go with what exists "
                                  f"for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
                                  "fpu_reduction", [b[0] for b in bad])
+    shared = shared_slots(shared_evaluations)
+    if shared:
+        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"),
+               (reference_quirks, "reference_quirks", "reference_quirks=True")]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f"shared_evaluations={shared_evaluations}: a shared evaluation table serves a position's stored row "
+                                 "to every game, which needs copied boards, one descent per step and a search that is not the "
+                                 f"reference's literal one -- not with {', '.join(b[1] for b in bad)}",
+                                 "shared_evaluations", [b[0] for b in bad])
     cap = fast is not None and P < 1.0
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
-                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root)
+                         evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
+                         shared)

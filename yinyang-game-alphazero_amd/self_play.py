@@ -88,8 +88,12 @@ class _Engine:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: `seed`),
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
+        """shared_evaluations (None / False: off; True: the default size; an int: slots, rounded up to a power of two): the games
+        of this engine share their evaluations through an engine.SharedEvaluations table of the engine's own (`self.shared`),
+        tied to its evaluator and (evaluation_symmetry, symmetry_seed); same games, fewer evaluator rows.  Needs an evaluator
+        that declares `row_independent` (ValueError otherwise).
+        leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: `seed`),
         forced_playouts (the recorded pi and the move draw use the pruned counts; fast and full searches alike),
         fpu_reduction / fpu_reduction_root (first-play urgency reduction in every search, fast and full alike)
         and the mode (free_running): options.SearchOptions; a refused combination raises ValueError before anything touches the
@@ -112,7 +116,10 @@ class _Engine:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations)
+        if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
+            raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
+                             "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
         self.K, self.tree_reuse, self.forced_playouts = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts
         self.fpu_reduction, self.fpu_reduction_root = opts.fpu_reduction, opts.fpu_reduction_root
         self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
@@ -142,6 +149,12 @@ class _Engine:
         self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
+        # one table per context: the kernel boundary of the context's own stream is what publishes its entries
+        self.shared = (engine.SharedEvaluations(self.R, self.C, opts.shared_evaluations, self.device, *self.symmetry)
+                       if opts.shared_evaluations else None)
+        if self.shared is not None:
+            with self._on_stream():
+                self.ctx.set_shared_evaluations(self.shared)
         self.seed = int(seed)                     # key of the per-game counter streams (csrc/yy_selfplay.hip)
         self.rng = rng
         self.first_game_index, self.stride = int(first_game_index), int(game_index_stride)
@@ -176,8 +189,15 @@ class _Engine:
         ex = {k: torch.cat([o[k] for o in out]) for k in out[0]}
         return sort_examples(ex) if self.free_running else ex
 
+    def memory_bytes(self):
+        """HBM of the search state: the tree context (arenas and the per-game evaluation cache), the opening book and the
+        shared evaluation table."""
+        return dict(context=self.ctx.memory_bytes(), book=self.book.bytes if self.book is not None else 0,
+                    shared_evaluations=self.shared.memory_bytes if self.shared is not None else 0)
+
     def close(self):
         self.ctx.close()
+        self.shared = None
 
 
 class LockstepEngine(_Engine):
@@ -584,6 +604,13 @@ class _LaneCounters:
                 tot[k] = tot.get(k, 0) + v
         return tot
 
+    def shared_counters(self):
+        tot = {}
+        for ln in self.lanes:
+            for k, v in ln.ctx.shared_counters().items():
+                tot[k] = tot.get(k, 0) + v
+        return tot
+
 
 class SelfPlayLanes:
     """K independent SelfPlayEngine lanes of G / K games each on K HIP streams of ONE GPU, their moves enqueued back to back.
@@ -601,15 +628,18 @@ class SelfPlayLanes:
                  first_game_index=0, game_index_stride=1, opening_book=None, board_semantics="copied", reference_quirks=False,
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, **engine_kwargs):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
+                 **engine_kwargs):
+        """shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
+        size asked for; memory_bytes() reports their sum.
+        leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
         (None: `seed`, the same in every lane), forced_playouts, fpu_reduction / fpu_reduction_root: options.SearchOptions, in every lane; resolved here once, before the book or any
         lane is built.  Free-running lanes each run on their own stream and the host alternates their batches of graph replays.
         The other keywords are SelfPlayEngine's."""
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -685,6 +715,12 @@ class SelfPlayLanes:
         for k, l in enumerate(self.lanes):
             l.begin_run(shard_games(int(num_games), k, K)[0])
         return self.play_to_completion(progress)
+
+    def memory_bytes(self):
+        """The lanes' _Engine.memory_bytes() summed; the one book the lanes share counted once."""
+        per = [l.memory_bytes() for l in self.lanes]
+        return dict(context=sum(m["context"] for m in per), book=self.book.bytes if self.book is not None else 0,
+                    shared_evaluations=sum(m["shared_evaluations"] for m in per))
 
     def collect(self):
         torch.cuda.synchronize(self.device)
@@ -806,8 +842,11 @@ class SelfPlayWorker:
                  dirichlet_alpha=0.3, dirichlet_epsilon=0.25, cpuct=1.0, num_parallel=1,
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
-                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
+                 evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
+                 shared_evaluations=None):
+        """shared_evaluations: MCTS's (a table shared by the one game's searches; needs board_semantics="copied",
+        reference_quirks=False and a network whose evaluator is row-independent).
+        leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
         class has no seed of its own), forced_playouts, fpu_reduction / fpu_reduction_root (needs reference_quirks=False):
         options.SearchOptions, through MCTS; K > 1, tree_reuse, evaluation_symmetry
         and forced_playouts need board_semantics="copied", K > 1, evaluation_symmetry and forced_playouts also
@@ -821,7 +860,7 @@ class SelfPlayWorker:
                                full_search_probability=full_search_probability, tree_reuse=tree_reuse,
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
                                forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
-                               fpu_reduction_root=fpu_reduction_root)
+                               fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations)
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -842,7 +881,7 @@ class SelfPlayWorker:
                          leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse,
                          evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
                          forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
-                         fpu_reduction_root=opts.fpu_reduction_root)
+                         fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None)
 
     def play_game(self):
         game, examples = self.game, []
@@ -925,17 +964,17 @@ class SelfPlayManager:
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-                 fpu_reduction=None, fpu_reduction_root=None):
+                 fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
-        (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root:
-        options.SearchOptions.
+        (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root,
+        shared_evaluations (a table per lane; its counters, fill and memory go into `stats`): options.SearchOptions.
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine; off at leaves_per_step > 1, where opening_book_stones=None also means no
         book); False = the network is asked for every leaf like the reference."""
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
                                        tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
-                                       fpu_reduction, fpu_reduction_root)
+                                       fpu_reduction, fpu_reduction_root, shared_evaluations)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -982,6 +1021,10 @@ class SelfPlayManager:
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         counters = eng.ctx.status()
+        if self.options.shared_evaluations:
+            counters.update({f"shared_{k}": v for k, v in eng.ctx.shared_counters().items()},
+                            shared_fill=sum(l.shared.fill() for l in eng.lanes), shared_slots=sum(l.shared.slots for l in eng.lanes),
+                            memory_bytes=eng.memory_bytes())
         ex = gather_examples(ex, capacity=example_capacity(total, world, eng.T))
         self.stats = dict(seconds=t1 - t0, positions=eng.positions, games=eng.games_finished, **counters,
                           **(dict(steps_issued=eng.steps_issued) if self.options.free_running else {}))
@@ -997,7 +1040,8 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
-    the other keywords (tree_reuse, free_running, forced_playouts and fpu_reduction / fpu_reduction_root among them) are SelfPlayManager's too."""
+    the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root and shared_evaluations among
+    them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
