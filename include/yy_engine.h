@@ -332,8 +332,8 @@ int yy_mcts_cache_clear(yy_mcts *ctx, yy_stream_t stream);
  *   of every tree-step launch (only while a table is set) and keeps it non-zero; the tree kernel reads it once per wave.
  * An entry that carries the current stamp is passed over by lookups -- its key and row may still be in flight in another
  * workgroup -- so everything a lookup trusts was written by a launch that completed earlier on the same stream: the kernel
- * boundary publishes, and the slot claim (one atomicCAS, as in yy_book_insert) is the only atomic.  Insert-only: no
- * eviction, no overwrite; a full probe window drops the insert (counted); two games inserting one position in one launch
+ * boundary publishes, and the slot claim (one atomicCAS, as in yy_book_insert) is the only atomic.  Insert-only (the
+ * replacing form below is the one that deduplicates and evicts): no eviction, no overwrite; a full probe window drops the insert (counted); two games inserting one position in one launch
  * take two slots.  The arrays stay owned by the caller and must outlive the context (or be unset with meta = NULL); ONE
  * table belongs to ONE context on ONE stream, and holds the outputs of one evaluator under one symmetry setting.  Set it
  * with no select pending and before the first step is captured.  YY_E_UNSUPPORTED for YY_FLAG_ALIASED and
@@ -347,6 +347,36 @@ int yy_mcts_set_shared_evaluations(yy_mcts *ctx, uint32_t *meta, uint64_t *keys,
                                    uint32_t *stamp);
 int yy_mcts_shared_evaluations_clear(yy_mcts *ctx, yy_stream_t stream);
 int yy_mcts_shared_counters(yy_mcts *ctx, uint64_t *out);
+/* The replacing form of the shared evaluation table: one slot per position and launch, and eviction, so that a table of a fixed
+ * size serves a run of any length.  Everything above holds -- lookup order, the stamp, what a lookup trusts, the refusals,
+ * the owner of the arrays, yy_mcts_shared_evaluations_clear (which zeroes the claim words) -- except "insert-only".
+ *   claim u64 [slots] (zeroed by the caller) in the place of meta: low half = the stamp of the inserting launch (0 = never used,
+ *     0xFFFFFFFF = TOMBSTONE, an evicted slot; both are free, and the stamp takes neither value), high half = a tag of the
+ *     position, the half of its hash that indexing does not use.  Slot and tag are taken in ONE 64-bit atomicCAS on the value
+ *     observed, still the only atomic of the option.
+ *   last_hit u32 [slots]: the stamp of the last launch that served the entry (a plain store by the lookup that hits; its
+ *     insert stamp until then).
+ *   sweep_state u64 [8] (zeroed by the caller): the sweeps' counters and the stamp the last evicting sweep recorded.
+ * One inserter per position and launch: an inserter that meets a slot claimed in ITS launch with ITS tag stops and counts a
+ * duplicate; of all games that insert one position in one launch exactly one takes a slot.  (Two different positions with one
+ * tag in one probe window and one launch cost one insert, nothing else: lookups compare keys in full.)  A lookup passes over
+ * a TOMBSTONE instead of ending its probe there.
+ * yy_mcts_shared_evaluations_sweep enqueues the eviction on `stream` (no host sync; YY_E_STATE for a context without a replacing
+ * table, nothing is launched): a counting pass over the claim words, then an evicting pass that does nothing while the live
+ * entries are <= high_water_slots and else turns every entry into a TOMBSTONE whose insert stamp and last-hit stamp are both
+ * older (modulo 2^32, on ages) than the stamp recorded by the last sweep that evicted, and records the current stamp for
+ * the next one; the first sweep above the mark only records.  Second chance over the whole table: what was inserted or
+ * served since the last evicting sweep stays.  It must run on the context's stream BETWEEN two tree-step launches, never
+ * captured into a step; it may run with selects pending -- a pending leaf found its slot in the latest launch, so the slot's
+ * last-hit stamp is the current one, which no cutoff is newer than -- which is what excludes the hazard named above for
+ * the clear.  No eviction or duplicate decision changes a game: a table only returns the evaluator's own row for a position.
+ * yy_mcts_shared_counters_ex (sync; host out [6]): hits, inserts, dropped, duplicates (since create or the last
+ * yy_mcts_reset_counters), evicted (since the table was set or the last yy_mcts_reset_counters), live entries left by the
+ * last sweep; the last three are 0 for an insert-only table. */
+int yy_mcts_set_shared_evaluations_replacing(yy_mcts *ctx, uint64_t *claim, uint32_t *last_hit, uint64_t *keys, float *value,
+                                             float *policy, int64_t slots, uint32_t *stamp, uint64_t *sweep_state);
+int yy_mcts_shared_evaluations_sweep(yy_mcts *ctx, int64_t high_water_slots, yy_stream_t stream);
+int yy_mcts_shared_counters_ex(yy_mcts *ctx, uint64_t *out);
 
 /* ------------------------------------------------------------------ evaluator epilogue
  * Batched leaf evaluator fast path (the reference evaluates one board per call:

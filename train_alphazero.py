@@ -8,7 +8,7 @@
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
 --dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability, --tree-reuse, --free-running,
---evaluation-symmetry, --symmetry-seed, --forced-playouts, --fpu-reduction, --fpu-reduction-root, --shared-evaluations.
+--evaluation-symmetry, --symmetry-seed, --forced-playouts, --fpu-reduction, --fpu-reduction-root, --shared-evaluations, --shared-evaluations-replace.
 `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
@@ -111,6 +111,10 @@ def parse_args(argv=None):
                         "-- a position any of them has had evaluated needs no evaluator row again (SLOTS: table slots per lane, "
                         "rounded up to a power of two; without a number 2^23, which at 8x8 costs what the 8-stone book costs; "
                         "default off; the same games; not with --leaves-per-step > 1, --board-semantics aliased or --reference-quirks)")
+    p.add_argument("--shared-evaluations-replace", action="store_true",
+                   help="self-play and train, with --shared-evaluations: the table keeps one slot per position and sheds what is no "
+                        "longer used (a sweep per move, or per poll with --free-running), so it serves a run of any length from "
+                        "its fixed size (default off; the same games)")
     return p.parse_args(argv)
 
 
@@ -118,7 +122,8 @@ def parse_args(argv=None):
 # train's self-play always runs on copied boards without the quirks, so --tree-reuse and --free-running do not look at those two
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
-           "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations")
+           "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
+           "shared_evaluations_replace")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root")]}
@@ -186,7 +191,8 @@ def main(argv=None):
                            tree_reuse=args.tree_reuse, free_running=args.free_running,
                            evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
                            forced_playouts=args.forced_playouts, fpu_reduction=args.fpu_reduction,
-                           fpu_reduction_root=args.fpu_reduction_root, shared_evaluations=args.shared_evaluations)
+                           fpu_reduction_root=args.fpu_reduction_root, shared_evaluations=args.shared_evaluations,
+                           shared_evaluations_replace=args.shared_evaluations_replace)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -219,7 +225,8 @@ def main(argv=None):
                                        free_running=args.free_running, evaluation_symmetry=args.evaluation_symmetry,
                                        symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts,
                                        fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
-                                       shared_evaluations=args.shared_evaluations)
+                                       shared_evaluations=args.shared_evaluations,
+                                       shared_evaluations_replace=args.shared_evaluations_replace)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

@@ -48,7 +48,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip into libyy_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in ("yy_engine.hip", "yy_nn_epilogue.hip", "yy_tower.hip", "yy_tower_f32.hip",
                                             "yy_tower_h3r.hip", "yy_tower_g.hip", "yy_fc_heads.hip", "yy_selfplay.hip",
-                                            "yy_selfplay_move.hip", "yy_bitboard.h", "yy_common.h", "yy_tree.h",
+                                            "yy_selfplay_move.hip", "yy_shared_table.hip", "yy_bitboard.h", "yy_common.h", "yy_tree.h",
                                             "yy_draws.h")] + [HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
@@ -103,6 +103,9 @@ _SIGS = {
     "yy_mcts_set_shared_evaluations": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp],
     "yy_mcts_shared_evaluations_clear": [_vp, _vp],
     "yy_mcts_shared_counters": [_vp, C.POINTER(C.c_uint64)],
+    "yy_mcts_set_shared_evaluations_replacing": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp],
+    "yy_mcts_shared_evaluations_sweep": [_vp, C.c_int64, _vp],
+    "yy_mcts_shared_counters_ex": [_vp, C.POINTER(C.c_uint64)],
     "yy_nn_bias_act_bf16": [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp],
     "yy_nn_tower_bf16": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_nn_tower_heads_bf16": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],

@@ -329,8 +329,10 @@ class AlphaZero:
                  mcts_threads=1, arena_games=40, nn_mode="auto", num_channels=128, num_res_blocks=10,
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
-        """shared_evaluations: the loop's self-play shares evaluations between the games of a lane (options.SearchOptions); every
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
+                 shared_evaluations_replace=False):
+        """shared_evaluations_replace: the loop's self-play uses the replacing table (options.SearchOptions).
+        shared_evaluations: the loop's self-play shares evaluations between the games of a lane (options.SearchOptions); every
         iteration's self-play builds its engines, and with them new, empty tables, for the network it plays with.  The arena
         plays two networks and takes no table.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry /
@@ -343,7 +345,7 @@ class AlphaZero:
                                        free_running=free_running, evaluation_symmetry=evaluation_symmetry,
                                        symmetry_seed=symmetry_seed, forced_playouts=forced_playouts,
                                        fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root,
-                                       shared_evaluations=shared_evaluations)
+                                       shared_evaluations=shared_evaluations, shared_evaluations_replace=shared_evaluations_replace)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold

@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 108
+#define YY_VERSION 109
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -478,8 +478,12 @@ __device__ __forceinline__ int leaf_lookup(const MctsDev &d, const GameState *st
     // the shared evaluation table: what any game of the context had evaluated in an EARLIER launch.  An entry that carries this
     // launch's stamp is passed over -- another workgroup may still be writing its key and row, and nothing of this launch has
     // been published (no fence, no acquire: the kernel boundary publishes) -- so everything trusted here was complete before
-    // this launch began.  A stale 0 read for a slot claimed in this launch ends the probe one entry early: a miss, never a wrong hit
-    if (d.sh.meta) {
+    // this launch began.  A stale 0 read for a slot claimed in this launch ends the probe one entry early: a miss, never a wrong hit.
+    // Replacing mode (d.sh_claim, the second branch): the stamp is the low half of the slot's claim word;
+    // an evicted slot (SH_TOMBSTONE, stale or claimed again in this launch alike) is passed over, not the end of the chain --
+    // entries behind it were inserted while it was taken; and a hit leaves this launch's stamp in the slot's last-hit word (a
+    // plain store: every writer of a launch writes the same value, and the sweep that reads it is a later launch)
+    if (d.sh.meta && !d.sh_claim) {
         const int at = tt_probe(h, d.sh.mask, [&](uint32_t at) {
             const uint32_t m = (uint32_t)rfl((int)d.sh.meta[at]);
             if (m == 0u) return TT_MISS;
@@ -487,6 +491,18 @@ __device__ __forceinline__ int leaf_lookup(const MctsDev &d, const GameState *st
             return tt_key_is<NW>(d.sh, at, black, white) ? TT_HIT : TT_NEXT;
         });
         if (at >= 0) return src_shared((uint32_t)at);
+    } else if (d.sh_claim) {
+        const uint32_t *low = (const uint32_t *)d.sh_claim;       // the stamp: the low half of a claim word (little-endian)
+        const int at = tt_probe(h, d.sh.mask, [&](uint32_t at) {
+            const uint32_t m = (uint32_t)rfl((int)low[2 * (size_t)at]);
+            if (m == 0u) return TT_MISS;
+            if (m == stamp || m == SH_TOMBSTONE) return TT_NEXT;
+            return tt_key_is<NW>(d.sh, at, black, white) ? TT_HIT : TT_NEXT;
+        });
+        if (at >= 0) {
+            if (lane_id() == 0) d.sh_hit[at] = stamp;
+            return src_shared((uint32_t)at);
+        }
     }
     return SRC_NONE;
 }
@@ -533,13 +549,14 @@ __device__ __forceinline__ void cache_store(const MctsDev &d, const GameState *s
 // used (the one atomic of the option, as in k_book_insert), stamped with this launch's stamp so that no lookup of this launch
 // trusts it; key, value and row follow as plain stores, published by the end of the launch.  Insert-only: a claimed slot is
 // never written again, a full window drops the row.  Two games that insert one position in one launch take two slots.
+// Replacing mode (d.sh_claim) differs in the claim alone: see there.
 template <int NW>
 __device__ __forceinline__ void shared_store(const MctsDev &d, GameState *st, const int g, const float *policy, const float v,
                                              const uint32_t stamp) {
     const int lane = lane_id(), A = d.geo.A;
     const uint64_t *board = st->leaf.board;
     int got = -1;
-    if (lane == 0) {
+    if (lane == 0 && !d.sh_claim) {
         // a slot that a plain load already shows taken stays taken (insert-only), so it costs no atomic: once the table is full
         // a dropped row is eight loads.  A stale 0 is settled by the atomicCAS that follows
         got = tt_probe(bb_hash<NW>(board, board + NW), d.sh.mask, [&](uint32_t at) {
@@ -547,6 +564,32 @@ __device__ __forceinline__ void shared_store(const MctsDev &d, GameState *st, co
             return atomicCAS(&d.sh.meta[at], 0u, stamp) == 0u ? TT_HIT : TT_NEXT;
         });
         st->shc[got >= 0 ? 1 : 2] += 1;
+    } else if (lane == 0) {
+        // Replacing mode: ONE inserter per position and launch.  The claim word carries this launch's stamp and the half of the
+        // hash that indexing does not use, taken in ONE 64-bit atomicCAS on the value observed (0 or a tombstone: both free), so
+        // a slot is never claimed without its tag.  An inserter that meets its own (stamp, tag) -- by the plain load or as the
+        // value its failed CAS returns -- stops: the position is being inserted by another game of this launch.  Exactly one of
+        // the games that insert position P in a launch takes a slot (if the window has room): within a launch a slot only goes
+        // from free to taken (the sweep is a launch of its own), and all of them walk the same window in the same order.  Had
+        // two of them taken slots a before b, the second would have passed a, which it does only when a shows a claim that is
+        // not P's in this launch -- a taken slot that P's first inserter could then never have claimed.  A stale load can only
+        // show an older state (free), which the CAS settles.  Two positions with one tag in one window and one launch: the
+        // second stops as a duplicate and its row is not stored -- one insert lost, nothing else, since lookups compare keys
+        const uint64_t h = bb_hash<NW>(board, board + NW);
+        const unsigned long long mine = SH_CLAIM((uint32_t)(h >> 32), stamp);
+        bool dup = false;
+        got = tt_probe(h, d.sh.mask, [&](uint32_t at) {
+            unsigned long long seen = d.sh_claim[at];
+            if (sh_free(sh_stamp_of(seen))) {
+                const unsigned long long old = atomicCAS(&d.sh_claim[at], seen, mine);
+                if (old == seen) return TT_HIT;
+                seen = old;
+            }
+            if (seen == mine) { dup = true; return TT_MISS; }
+            return TT_NEXT;
+        });
+        st->shc[got >= 0 ? 1 : dup ? 3 : 2] += 1;
+        if (got >= 0) d.sh_hit[got] = stamp;         // no lookup of this launch reads or marks a slot claimed in it
     }
     got = rfl(got);
     if (got < 0) return;
@@ -1063,10 +1106,10 @@ template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do
 // The step stamp of the shared evaluation table: one thread, in a launch of its own between two tree-step launches of the
 // context's stream, so that every tree-step launch has a stamp of its own.  Never 0 (0 marks a slot nobody has used).  The
 // stamp lives in device memory: a captured step freezes its arguments.
+// SH_TOMBSTONE (an evicted slot of the replacing table) is skipped like 0.
 __global__ void k_stamp(uint32_t *stamp) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const uint32_t s = *stamp + 1u;
-    *stamp = s ? s : 1u;
+    *stamp = sh_next_stamp(*stamp);
 }
 
 // =============================================================================== leaf-parallel steps (K > 1)
@@ -1449,7 +1492,8 @@ __global__ void k_reset_counters(MctsDev d) {
     if (g >= d.G) return;
     for (int i = 0; i < 8; i++) d.state[g].ctr[i] = 0;
     d.state[g].forced = 0;
-    for (int i = 0; i < 3; i++) d.state[g].shc[i] = 0;
+    for (int i = 0; i < 4; i++) d.state[g].shc[i] = 0;
+    if (g == 0 && d.sh_sweep) d.sh_sweep[SH_SW_EVICTED] = 0;
 }
 
 __global__ void k_forced_sum(MctsDev d, uint64_t *out) {
@@ -1788,7 +1832,14 @@ extern "C" int yy_mcts_set_shared_evaluations(yy_mcts *c, uint32_t *meta, uint64
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
     // a pending leaf may name a slot of the table that is set now (GameState.leaf_src)
     if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_set_shared_evaluations with a select or a root expansion pending%s%s");
-    if (!meta) { c->dev.sh = PosTable{}; c->dev.sh_stamp = nullptr; return YY_OK; }
+    if (!meta) {
+        c->dev.sh = PosTable{};
+        c->dev.sh_stamp = nullptr;
+        c->dev.sh_claim = nullptr;
+        c->dev.sh_hit = nullptr;
+        c->dev.sh_sweep = nullptr;
+        return YY_OK;
+    }
     if (c->cfg.flags & YY_FLAG_ALIASED)
         return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_shared_evaluations needs copied boards (YY_FLAG_ALIASED reproduces the reference, which asks the network for every leaf)%s%s");
     if (c->multi.K > 1)
@@ -1797,23 +1848,59 @@ extern "C" int yy_mcts_set_shared_evaluations(yy_mcts *c, uint32_t *meta, uint64
         return set_err(YY_E_INVALID, "yy_mcts_set_shared_evaluations: bad argument (slots must be a power of two in 64 .. 2^30)%s%s");
     c->dev.sh = PosTable{meta, keys, val, pol, (uint32_t)(slots - 1)};
     c->dev.sh_stamp = stamp;
+    c->dev.sh_claim = nullptr;
+    c->dev.sh_hit = nullptr;
+    c->dev.sh_sweep = nullptr;
+    return YY_OK;
+}
+
+// The replacing table: the insert-only setter's checks and state, then the claim words in the place of meta (MctsDev.sh_claim)
+extern "C" int yy_mcts_set_shared_evaluations_replacing(yy_mcts *c, uint64_t *claim, uint32_t *last_hit, uint64_t *keys, float *val,
+                                                        float *pol, int64_t slots, uint32_t *stamp, uint64_t *sweep_state) {
+    if (c && claim && (!last_hit || !sweep_state))
+        return set_err(YY_E_INVALID, "yy_mcts_set_shared_evaluations_replacing: bad argument (last_hit and sweep_state are needed)%s%s");
+    if (int e = yy_mcts_set_shared_evaluations(c, (uint32_t *)claim, keys, val, pol, slots, stamp)) return e;
+    if (!claim) return YY_OK;
+    c->dev.sh_claim = (unsigned long long *)claim;
+    c->dev.sh_hit = last_hit;
+    c->dev.sh_sweep = (unsigned long long *)sweep_state;
     return YY_OK;
 }
 
 __global__ void k_shared_sum(MctsDev d, uint64_t *out) {
-    uint64_t acc[3] = {0, 0, 0};
+    uint64_t acc[4] = {0, 0, 0, 0};
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x)
-        for (int i = 0; i < 3; i++) acc[i] += d.state[g].shc[i];
-    for (int i = 0; i < 3; i++)
+        for (int i = 0; i < 4; i++) acc[i] += d.state[g].shc[i];
+    for (int i = 0; i < 4; i++)
         if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
+}
+
+// hits, inserts, dropped, duplicates summed over the games into c->scratch[0 .. 3]
+static int shared_sum(yy_mcts *c) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(c->scratch, 0, 4 * sizeof(uint64_t)));
+    hipLaunchKernelGGL(k_shared_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
+    HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_shared_counters_ex(yy_mcts *c, uint64_t *out) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (int e = shared_sum(c)) return e;
+    HIP_TRY(hipMemcpy(out, c->scratch, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    out[4] = out[5] = 0;
+    if (c->dev.sh_sweep) {
+        uint64_t sw[SH_SWEEP_WORDS];
+        HIP_TRY(hipMemcpy(sw, c->dev.sh_sweep, sizeof sw, hipMemcpyDeviceToHost));
+        out[4] = sw[SH_SW_EVICTED];
+        out[5] = sw[SH_SW_LIVE];
+    }
+    return YY_OK;
 }
 
 extern "C" int yy_mcts_shared_counters(yy_mcts *c, uint64_t *out) {
     if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(c->scratch, 0, 3 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_shared_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
-    HIP_TRY(hipGetLastError());
+    if (int e = shared_sum(c)) return e;
     HIP_TRY(hipMemcpy(out, c->scratch, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return YY_OK;
 }
@@ -1823,7 +1910,14 @@ extern "C" int yy_mcts_shared_evaluations_clear(yy_mcts *c, yy_stream_t s) {
     // a pending leaf may name a slot (GameState.leaf_src): emptied, another game could claim and rewrite it in the launch that reads it
     if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_shared_evaluations_clear with a select or a root expansion pending%s%s");
     const PosTable &sh = c->dev.sh;
-    if (sh.meta) HIP_TRY(hipMemsetAsync(sh.meta, 0, ((size_t)sh.mask + 1) * sizeof(uint32_t), (hipStream_t)s));
+    // replacing mode: sh.meta names the claim words, eight bytes a slot; the sweeps start over (live, cutoff), the count of
+    // evicted entries goes on
+    const size_t word = c->dev.sh_claim ? sizeof(uint64_t) : sizeof(uint32_t);
+    if (sh.meta) HIP_TRY(hipMemsetAsync(sh.meta, 0, ((size_t)sh.mask + 1) * word, (hipStream_t)s));
+    if (c->dev.sh_sweep) {
+        HIP_TRY(hipMemsetAsync(c->dev.sh_sweep + SH_SW_LIVE, 0, sizeof(uint64_t), (hipStream_t)s));
+        HIP_TRY(hipMemsetAsync(c->dev.sh_sweep + SH_SW_CUTOFF, 0, sizeof(uint64_t), (hipStream_t)s));
+    }
     return YY_OK;
 }
 

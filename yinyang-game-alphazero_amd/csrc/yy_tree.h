@@ -227,7 +227,8 @@ struct GameState {
     LeafRec leaf;           // K = 1: the pending leaf
     uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
     uint64_t forced;        // forced playouts: root descents that took a forced edge, since create / yy_mcts_reset_counters
-    uint64_t shc[3];        // shared evaluation table: leaves it served, rows inserted, inserts dropped (probe window full)
+    uint64_t shc[4];        // shared evaluation table: leaves it served, rows inserted, inserts dropped (probe window full),
+                            // replacing mode: inserts that met their position claimed in the same launch (duplicates)
 };
 
 // A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
@@ -263,6 +264,14 @@ struct MctsDev {
     // without it.  *sh_stamp: the step stamp, never 0, advanced by k_stamp in front of every tree-step launch
     PosTable sh;
     uint32_t *sh_stamp;
+    // replacing mode (yy_mcts_set_shared_evaluations_replacing; nullptr: the insert-only table above, every kernel does what it
+    // did with it).  sh_claim [slots]: SH_CLAIM(tag, stamp) -- the inserting launch's stamp in the low half (0: never used,
+    // SH_TOMBSTONE: evicted, both free), the upper half of the position's bb_hash in the high half; sh.meta then names the
+    // same words and only says "a table is set".  sh_hit [slots]: the stamp of the last launch that served the entry (its
+    // insert stamp until then).  sh_sweep [SH_SWEEP_WORDS]: the state of the sweeps (yy_shared_table.hip)
+    unsigned long long *sh_claim;
+    uint32_t *sh_hit;
+    unsigned long long *sh_sweep;
     GameState *state;
     float *sqrt_tab;
     int32_t sqrt_n;         // entries of sqrt_tab: max_sims + 2 (+ K when K > 1: virtual visits)
@@ -277,6 +286,20 @@ struct MctsDev {
     // does what it did without it (an unvisited child scores q = 0)
     float fpu, fpu_root;
 };
+
+// ---- shared evaluation table, replacing mode: the claim word and the sweep state (yy_engine.hip, yy_shared_table.hip)
+#define SH_TOMBSTONE 0xFFFFFFFFu           // the stamp of an evicted slot; k_stamp never hands it out, as it never hands out 0
+#define SH_CLAIM(tag, stamp) (((unsigned long long)(tag) << 32) | (unsigned long long)(stamp))
+__host__ __device__ __forceinline__ uint32_t sh_stamp_of(unsigned long long claim) { return (uint32_t)claim; }
+__host__ __device__ __forceinline__ bool sh_free(uint32_t stamp) { return stamp == 0u || stamp == SH_TOMBSTONE; }
+// the successor of a stamp: 0 and SH_TOMBSTONE are skipped, so the stamps run 1 .. 2^32 - 2 and wrap to 1
+__host__ __device__ __forceinline__ uint32_t sh_next_stamp(uint32_t s) {
+    s += 1u;
+    return sh_free(s) ? 1u : s;
+}
+// sh_sweep words: live entries counted by the running sweep, entries it evicted, live entries after the last sweep, entries
+// evicted since the table was set or the counters reset, the stamp recorded by the last sweep that evicted (0: none yet)
+enum { SH_SW_COUNT = 0, SH_SW_EVICTING = 1, SH_SW_LIVE = 2, SH_SW_EVICTED = 3, SH_SW_CUTOFF = 4, SH_SWEEP_WORDS = 8 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev
     int32_t K;               // leaves per step (1: one descent per game per step)

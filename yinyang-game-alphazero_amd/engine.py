@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, forced_k, fpu_r, shared_slots
+from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, SHARED_EVALUATIONS_HIGH_WATER, forced_k, fpu_r, shared_slots
 from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
@@ -576,11 +576,22 @@ class SharedEvaluations:
     (evaluation_symmetry, symmetry_seed) per table: `symmetry` is compared by BatchedMCTS.set_shared_evaluations, and
     clear() is the caller's job when the network changes.
     slots: rounded up to a power of two; None = SHARED_EVALUATIONS_DEFAULT_SLOTS = 2^23, which at 8x8 costs what the 8-stone
-    opening book costs (2.3 GB) -- a starting point, not a measured optimum."""
+    opening book costs (2.3 GB) -- a starting point, not a measured optimum.
+    replace=True (yy_mcts_set_shared_evaluations_replacing): the table that does not fill up.  A slot's claim word (`claim`,
+    u64 in the place of `meta`) holds the inserting launch's stamp and a 32-bit tag of the position, so of all games that
+    insert one position in one launch exactly one takes a slot (the others count as `duplicates`); a hit leaves the launch's
+    stamp in the slot's `last_hit` word; and sweep() -- launches of its own between two tree steps, called by the engines --
+    evicts, once more than high_water * slots entries are live, every entry neither inserted nor served since the last sweep
+    that evicted.  high_water (a fraction of the slots, an attribute that may be changed between sweeps): None =
+    options.SHARED_EVALUATIONS_HIGH_WATER; profiles/shared_evaluations_replace.json holds the comparison it was taken from.
+    12 bytes a slot more than the insert-only table.  The same games either way."""
 
     COUNTERS = ("hits", "inserts", "dropped")
+    COUNTERS_EX = COUNTERS + ("duplicates", "evicted", "live")
+    TOMBSTONE = 0xFFFFFFFF
 
-    def __init__(self, rows, cols, slots=None, device=None, evaluation_symmetry="off", symmetry_seed=None):
+    def __init__(self, rows, cols, slots=None, device=None, evaluation_symmetry="off", symmetry_seed=None, replace=False,
+                 high_water=None):
         self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.R, self.C, self.A = int(rows), int(cols), int(rows) * int(cols)
@@ -588,7 +599,17 @@ class SharedEvaluations:
         if not self.slots:
             raise ValueError("SharedEvaluations: slots must be positive")
         nw, dev = (self.A + 63) // 64, self.device
-        self.meta = torch.zeros(self.slots, dtype=torch.int32, device=dev)
+        self.replace = bool(replace)
+        self.high_water = float(SHARED_EVALUATIONS_HIGH_WATER if high_water is None else high_water)
+        if not 0.0 <= self.high_water <= 1.0:
+            raise ValueError(f"SharedEvaluations: high_water={high_water} is a fraction of the slots, in [0, 1]")
+        if self.replace:
+            self.claim = torch.zeros(self.slots, dtype=torch.int64, device=dev)
+            self.last_hit = torch.zeros(self.slots, dtype=torch.int32, device=dev)
+            self.sweep_state = torch.zeros(8, dtype=torch.int64, device=dev)
+            self.meta = None
+        else:
+            self.meta = torch.zeros(self.slots, dtype=torch.int32, device=dev)
         self.keys = torch.empty((self.slots, 2 * nw), dtype=torch.int64, device=dev)
         self.value = torch.empty(self.slots, dtype=torch.float32, device=dev)
         self.policy = torch.empty((self.slots, self.A), dtype=torch.float32, device=dev)
@@ -597,27 +618,48 @@ class SharedEvaluations:
 
     @property
     def memory_bytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.meta, self.keys, self.value, self.policy, self.stamp))
+        own = (self.claim, self.last_hit, self.sweep_state) if self.replace else (self.meta,)
+        return sum(t.numel() * t.element_size() for t in own + (self.keys, self.value, self.policy, self.stamp))
+
+    def stamps(self):
+        """The insert stamp of every slot (int64 [slots]; 0: never used, TOMBSTONE: evicted)."""
+        return (self.claim & 0xFFFFFFFF) if self.replace else (self.meta.to(torch.int64) & 0xFFFFFFFF)
+
+    def live(self):
+        """bool [slots]: the slots that hold an entry."""
+        st = self.stamps()
+        return (st != 0) & (st != self.TOMBSTONE)
+
+    def sweep(self):
+        """replace=True only (RuntimeError otherwise): enqueue one sweep on the current stream, which must be the stream of the
+        table's context, between two tree steps (never inside a captured step).  No host sync.  Legal with selects pending."""
+        if not self.replace:
+            raise RuntimeError("SharedEvaluations.sweep(): an insert-only table has no eviction (replace=True)")
+        if self.ctx is None:
+            return                                                        # no context has ever written to it: nothing to evict
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_shared_evaluations_sweep(self.ctx._h, int(self.high_water * self.slots), _stream()))
 
     def clear(self):
         """Empty the table (asynchronous, on the current stream: call it on the stream of the table's context).  Through the
         context that holds the table, which refuses while a search is in progress (a pending leaf may name a slot); a
         context armed for a free-running run stays in that state."""
         if self.ctx is None:
-            self.meta.zero_()
+            (self.claim if self.replace else self.meta).zero_()
             return
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_shared_evaluations_clear(self.ctx._h, _stream()))
 
     def fill(self):
         """sync; slots in use."""
-        return int((self.meta != 0).sum())
+        return int(self.live().sum())
 
     def counters(self):
-        """sync; {hits, inserts, dropped} of the table's context since it was made / its last reset_counters()."""
+        """sync; {hits, inserts, dropped} of the table's context since it was made / its last reset_counters(); replace=True:
+        also duplicates, evicted and live (the entries the last sweep left)."""
         if self.ctx is None:
-            return dict.fromkeys(self.COUNTERS, 0)
-        return self.ctx.shared_counters()
+            return dict.fromkeys(self.COUNTERS_EX if self.replace else self.COUNTERS, 0)
+        return self.ctx.shared_counters_ex() if self.replace else self.ctx.shared_counters()
 
 
 # ------------------------------------------------------------------ batched MCTS context
@@ -872,6 +914,10 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             if table is None:
                 check(lib().yy_mcts_set_shared_evaluations(self._h, None, None, None, None, 0, None))
+            elif table.replace:
+                check(lib().yy_mcts_set_shared_evaluations_replacing(self._h, _p(table.claim), _p(table.last_hit), _p(table.keys),
+                                                                     _p(table.value), _p(table.policy), table.slots,
+                                                                     _p(table.stamp), _p(table.sweep_state)))
             else:
                 check(lib().yy_mcts_set_shared_evaluations(self._h, _p(table.meta), _p(table.keys), _p(table.value), _p(table.policy),
                                                            table.slots, _p(table.stamp)))
@@ -888,6 +934,14 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_shared_counters(self._h, ctr))
         return dict(zip(SharedEvaluations.COUNTERS, [int(x) for x in ctr[:3]]))
+
+    def shared_counters_ex(self):
+        """sync; shared evaluation table: {hits, inserts, dropped, duplicates, evicted, live}; the last three are 0 for an
+        insert-only table."""
+        ctr = (ct.c_uint64 * 6)()
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_shared_counters_ex(self._h, ctr))
+        return dict(zip(SharedEvaluations.COUNTERS_EX, [int(x) for x in ctr[:6]]))
 
     def bind_evaluator(self, evaluator):
         """Evaluations kept across searches (keep_evaluations) and the opening book are results of ONE network: the engine-level

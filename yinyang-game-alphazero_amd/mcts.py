@@ -137,8 +137,11 @@ class MCTS:
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None):
-        """shared_evaluations (not in the reference; None / False = off, True = the default size, an int = slots): the searches
+                 shared_evaluations=None, shared_evaluations_replace=False):
+        """shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
+        replace=True, options.SearchOptions): one slot per position, and a sweep after every search -- with tree_reuse after
+        the advance that follows it -- evicts what was not used once the table is nearly full.  The same results.
+        shared_evaluations (not in the reference; None / False = off, True = the default size, an int = slots): the searches
         of a context share their evaluations through an engine.SharedEvaluations table -- a position evaluated in an earlier
         step of any game of the batch, or in an earlier search, needs no evaluator row again; same results.  Needs
         board_semantics="copied", leaves_per_step == 1 and an evaluator that declares `row_independent` (network.BatchedEvaluator
@@ -182,6 +185,9 @@ class MCTS:
         self.shared_evaluations = options.shared_slots(shared_evaluations)
         if self.shared_evaluations:
             options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, shared_evaluations=shared_evaluations)
+        # refused without shared_evaluations
+        self.shared_evaluations_replace = options.resolve(shared_evaluations=shared_evaluations,
+                                                          shared_evaluations_replace=shared_evaluations_replace).shared_evaluations_replace
         self._shared_owner = None              # the network whose rows the tables hold
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
@@ -213,7 +219,7 @@ class MCTS:
                                      fpu_reduction_root=self.fpu_reduction_root)
             if self.shared_evaluations:
                 ctx.set_shared_evaluations(engine.SharedEvaluations(self.R, self.C, self.shared_evaluations, ctx.device,
-                                                                    *self.symmetry))
+                                                                    *self.symmetry, replace=self.shared_evaluations_replace))
             self._ctx[G] = ctx
         if ctx.shared is not None and self._shared_owner is not self.neural_net:
             if self._shared_owner is not None:                   # another network: its rows are not this one's
@@ -259,6 +265,8 @@ class MCTS:
             cached[1].run(boards, players, sims, noise=noise, eps=self.dirichlet_epsilon, active=active)
         else:
             ctx.search(boards, players, ev, sims, noise=noise, eps=self.dirichlet_epsilon, active=active)
+        if not self.tree_reuse:
+            self._sweep(ctx)                                     # once per move; with tree_reuse after the advance
         if self.temperature in (0, 1.0):
             pi = ctx.root_policy(temperature_zero=(self.temperature == 0))
         else:
@@ -324,13 +332,23 @@ class MCTS:
         kept_visits (device int32 [G]).  Call it once per move made, the opponent's included."""
         if not self.tree_reuse:
             raise ValueError("advance_batch needs MCTS(tree_reuse=True)")
-        return self._context(actions.shape[0]).advance(actions)
+        ctx = self._context(actions.shape[0])
+        kept = ctx.advance(actions)
+        self._sweep(ctx)
+        return kept
+
+    @staticmethod
+    def _sweep(ctx):
+        """Replacing shared evaluation table: the eviction sweep, between two searches (nothing is pending)."""
+        if ctx.shared is not None and ctx.shared.replace:
+            ctx.shared.sweep()
 
     def reuse_tree(self, old_root, board, player, action_taken):
         if self.tree_reuse and 1 in self._ctx:
             ctx = self._ctx[1]
             a = -1 if action_taken is None else int(action_taken)
             ctx.advance(torch.tensor([a], dtype=torch.int32, device=ctx.device))
+            self._sweep(ctx)
         if old_root is not None and action_taken in old_root.children:
             new_root = old_root.children[action_taken]
             new_root.parent = None

@@ -100,7 +100,17 @@ class SearchOptions:
     `row_independent` (ValueError otherwise, where the evaluator is known), copied boards and one descent per step: refused
     with board_semantics="aliased", leaves_per_step > 1 and reference_quirks.  It goes with evaluation reuse on or off, the
     book, the playout cap, tree reuse, free-running, evaluation symmetry (the table is tied to (mode, seed) like the book),
-    forced playouts and fpu_reduction.  Every lane of SelfPlayLanes has a table of its own."""
+    forced playouts and fpu_reduction.  Every lane of SelfPlayLanes has a table of its own.
+
+    shared_evaluations_replace (needs shared_evaluations; default False): the table in its replacing form
+    (engine.SharedEvaluations(replace=True); include/yy_engine.h yy_mcts_set_shared_evaluations_replacing).
+    Of all games that insert one position in one launch exactly one takes a slot, so the table fills with distinct positions
+    only, and a sweep between tree steps -- once per move in lockstep, at every poll in free-running self-play -- evicts, once
+    more than high_water of the slots are live, every entry that was neither inserted nor served since the last sweep that
+    evicted (second chance over the whole table; SHARED_EVALUATIONS_HIGH_WATER): a table of a fixed size serves a run of any
+    length.  The same games, move for move: a table only ever returns the evaluator's own row for a position, so no eviction
+    or duplicate decision can change one.  Without shared_evaluations it is refused; with it, it is refused wherever
+    shared_evaluations is."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -112,6 +122,7 @@ class SearchOptions:
     fpu_reduction: float = 0.0              # 0.0: off
     fpu_reduction_root: float = 0.0         # resolved: fpu_reduction where it was not given; 0.0 when the option is off
     shared_evaluations: int = 0             # slots of the shared evaluation table (a power of two); 0: off
+    shared_evaluations_replace: bool = False  # the table deduplicates inserts and evicts (needs shared_evaluations)
 
     @property
     def playout_cap(self):
@@ -130,6 +141,8 @@ class SearchOptions:
             on.update(fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
         if self.shared_evaluations:
             on.update(shared_evaluations=self.shared_evaluations)
+        if self.shared_evaluations_replace:
+            on.update(shared_evaluations_replace=True)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
@@ -148,6 +161,9 @@ def forced_k(forced_playouts):
 
 
 SHARED_EVALUATIONS_DEFAULT_SLOTS = 1 << 23   # 8x8: 280 bytes a slot = 2.3 GB, the 8-stone opening book's size
+# replacing table: the share of live slots above which a sweep evicts.  profiles/shared_evaluations_replace.json holds the
+# comparison of 0.5, 0.75 and 0.9 (tools/shared_evaluations.py --high-water)
+SHARED_EVALUATIONS_HIGH_WATER = 0.75
 
 
 def shared_slots(shared_evaluations):
@@ -198,14 +214,14 @@ def fpu_r(fpu_reduction, fpu_reduction_root=None):
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-            fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
+            fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
     -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
-    shared_evaluations -- so two broken rules name the same option everywhere.  forced_playouts, fpu_reduction: None and 0 = off;
-    shared_evaluations: None and False = off."""
+    shared_evaluations, shared_evaluations_replace -- so two broken rules name the same option everywhere.  forced_playouts,
+    fpu_reduction: None and 0 = off; shared_evaluations: None and False = off; shared_evaluations_replace: None and False = off."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
     if evaluation_symmetry not in ("off", "random"):
@@ -279,8 +295,14 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
                                  "to every game, which needs copied boards, one descent per step and a search that is not the "
                                  f"reference's literal one -- not with {', '.join(b[1] for b in bad)}",
                                  "shared_evaluations", [b[0] for b in bad])
+    if shared_evaluations_replace not in (None, False, True):
+        raise OptionConflict(f"shared_evaluations_replace={shared_evaluations_replace!r}: True or False", "shared_evaluations_replace")
+    replace = bool(shared_evaluations_replace)
+    if replace and not shared:
+        raise OptionConflict("shared_evaluations_replace=True: it is the replacing form of the shared evaluation table -- not "
+                             "without shared_evaluations", "shared_evaluations_replace", ["shared_evaluations"])
     cap = fast is not None and P < 1.0
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
                          evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
-                         shared)
+                         shared, replace)

@@ -88,8 +88,13 @@ class _Engine:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None,
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
-                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
-        """shared_evaluations (None / False: off; True: the default size; an int: slots, rounded up to a power of two): the games
+                 symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
+                 shared_evaluations_replace=False):
+        """shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
+        replace=True): one slot per position, and the engine sweeps it -- the lockstep engine once per move, after the move and
+        the re-rooting of tree_reuse, the free-running engine at every poll, between two graph replays -- so that it sheds what
+        is no longer used; `self.shared.high_water` may be set between sweeps.  The same games.
+        shared_evaluations (None / False: off; True: the default size; an int: slots, rounded up to a power of two): the games
         of this engine share their evaluations through an engine.SharedEvaluations table of the engine's own (`self.shared`),
         tied to its evaluator and (evaluation_symmetry, symmetry_seed); same games, fewer evaluator rows.  Needs an evaluator
         that declares `row_independent` (ValueError otherwise).
@@ -116,7 +121,7 @@ class _Engine:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
         if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
             raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
                              "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
@@ -150,7 +155,8 @@ class _Engine:
         if self.book is not None:
             self.ctx.set_book(self.book)
         # one table per context: the kernel boundary of the context's own stream is what publishes its entries
-        self.shared = (engine.SharedEvaluations(self.R, self.C, opts.shared_evaluations, self.device, *self.symmetry)
+        self.shared = (engine.SharedEvaluations(self.R, self.C, opts.shared_evaluations, self.device, *self.symmetry,
+                                                replace=opts.shared_evaluations_replace)
                        if opts.shared_evaluations else None)
         if self.shared is not None:
             with self._on_stream():
@@ -449,6 +455,8 @@ class LockstepEngine(_Engine):
         if self.tree_reuse:
             # re-root every tree at the move played; a game that ended (its slot may be refilled) or did not search keeps nothing
             self.kept_visits = self.ctx.advance(torch.where(fin, torch.full_like(action, -1), action))
+        if self.shared is not None and self.shared.replace:
+            self.shared.sweep()                                                # once per move: no select is pending here
         counts = [searching.sum(), fin.sum()] + ([record.sum()] if self.fast_sims is not None else [])
         stats = torch.stack(counts)                                            # the move's one host read, taken in finish_move()
         if self._stats_host is None:
@@ -530,6 +538,9 @@ class FreeRunningEngine(_Engine):
         t, run = self._tick, self.run_state
         with self._on_stream():
             self.free_search.issue(t["poll"])
+            if self.shared is not None and self.shared.replace:
+                # between two graph replays, never captured: legal with selects pending (csrc/yy_shared_table.hip)
+                self.shared.sweep()
             t["steps"] += t["poll"]
             self.steps_issued += t["poll"]
             t["prev"], t["cur"] = t["cur"], run.poll_counters() + (t["steps"],)
@@ -611,6 +622,13 @@ class _LaneCounters:
                 tot[k] = tot.get(k, 0) + v
         return tot
 
+    def shared_counters_ex(self):
+        tot = {}
+        for ln in self.lanes:
+            for k, v in ln.ctx.shared_counters_ex().items():
+                tot[k] = tot.get(k, 0) + v
+        return tot
+
 
 class SelfPlayLanes:
     """K independent SelfPlayEngine lanes of G / K games each on K HIP streams of ONE GPU, their moves enqueued back to back.
@@ -629,9 +647,10 @@ class SelfPlayLanes:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 **engine_kwargs):
+                 shared_evaluations_replace=False, **engine_kwargs):
         """shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
-        size asked for; memory_bytes() reports their sum.
+        size asked for; memory_bytes() reports their sum.  shared_evaluations_replace: every lane's table is a replacing one,
+        swept by its lane on the lane's stream.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
         (None: `seed`, the same in every lane), forced_playouts, fpu_reduction / fpu_reduction_root: options.SearchOptions, in every lane; resolved here once, before the book or any
         lane is built.  Free-running lanes each run on their own stream and the host alternates their batches of graph replays.
@@ -639,7 +658,7 @@ class SelfPlayLanes:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -843,9 +862,9 @@ class SelfPlayWorker:
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None):
+                 shared_evaluations=None, shared_evaluations_replace=False):
         """shared_evaluations: MCTS's (a table shared by the one game's searches; needs board_semantics="copied",
-        reference_quirks=False and a network whose evaluator is row-independent).
+        reference_quirks=False and a network whose evaluator is row-independent).  shared_evaluations_replace: MCTS's too.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
         class has no seed of its own), forced_playouts, fpu_reduction / fpu_reduction_root (needs reference_quirks=False):
         options.SearchOptions, through MCTS; K > 1, tree_reuse, evaluation_symmetry
@@ -860,7 +879,8 @@ class SelfPlayWorker:
                                full_search_probability=full_search_probability, tree_reuse=tree_reuse,
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
                                forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
-                               fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations)
+                               fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
+                               shared_evaluations_replace=shared_evaluations_replace)
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -881,7 +901,8 @@ class SelfPlayWorker:
                          leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse,
                          evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
                          forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
-                         fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None)
+                         fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None,
+                         shared_evaluations_replace=opts.shared_evaluations_replace)
 
     def play_game(self):
         game, examples = self.game, []
@@ -964,17 +985,18 @@ class SelfPlayManager:
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-                 fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None):
+                 fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False):
         """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
         (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root,
-        shared_evaluations (a table per lane; its counters, fill and memory go into `stats`): options.SearchOptions.
+        shared_evaluations (a table per lane; its counters, fill and memory go into `stats`), shared_evaluations_replace (the
+        replacing table; `stats` then holds its six counters): options.SearchOptions.
         evaluation_reuse: None = the engine's default (on for copied boards with the float32-accurate evaluator: pass values +
         per-game evaluation cache, SelfPlayEngine; off at leaves_per_step > 1, where opening_book_stones=None also means no
         book); False = the network is asked for every leaf like the reference."""
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
                                        tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
-                                       fpu_reduction, fpu_reduction_root, shared_evaluations)
+                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -1022,7 +1044,8 @@ class SelfPlayManager:
         t1 = time.perf_counter()
         counters = eng.ctx.status()
         if self.options.shared_evaluations:
-            counters.update({f"shared_{k}": v for k, v in eng.ctx.shared_counters().items()},
+            shc = eng.ctx.shared_counters_ex() if self.options.shared_evaluations_replace else eng.ctx.shared_counters()
+            counters.update({f"shared_{k}": v for k, v in shc.items()},
                             shared_fill=sum(l.shared.fill() for l in eng.lanes), shared_slots=sum(l.shared.slots for l in eng.lanes),
                             memory_bytes=eng.memory_bytes())
         ex = gather_examples(ex, capacity=example_capacity(total, world, eng.T))
@@ -1040,8 +1063,8 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
-    the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root and shared_evaluations among
-    them) are SelfPlayManager's too."""
+    the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root, shared_evaluations and
+    shared_evaluations_replace among them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
