@@ -364,7 +364,7 @@ int yy_mcts_shared_counters(yy_mcts *ctx, uint64_t *out);
  * yy_mcts_shared_evaluations_sweep enqueues the eviction on `stream` (no host sync; YY_E_STATE for a context without a replacing
  * table, nothing is launched): a counting pass over the claim words, then an evicting pass that does nothing while the live
  * entries are <= high_water_slots and else turns every entry into a TOMBSTONE whose insert stamp and last-hit stamp are both
- * older (modulo 2^32, on ages) than the stamp recorded by the last sweep that evicted, and records the current stamp for
+ * older (modulo 2^32, on ages) than the stamp recorded by the last sweep above the mark, and records the current stamp for
  * the next one; the first sweep above the mark only records.  Second chance over the whole table: what was inserted or
  * served since the last evicting sweep stays.  It must run on the context's stream BETWEEN two tree-step launches, never
  * captured into a step; it may run with selects pending -- a pending leaf found its slot in the latest launch, so the slot's

@@ -6,11 +6,12 @@
 //   k_shared_count   live entries (claim stamp neither 0 nor SH_TOMBSTONE), reduced per wave, one atomic add per workgroup
 //   k_shared_evict   every workgroup reads that count and returns at once when it is <= high_water; else every entry whose
 //                    insert stamp AND last-hit stamp are both older than the cutoff -- the stamp recorded by the last sweep
-//                    that evicted -- becomes a tombstone: what was inserted or served since then stays, the rest goes
-//   k_shared_close   one thread: books the sweep (live after it, evicted in all) and, when the sweep evicted, records the current
+//                    above the mark -- becomes a tombstone: what was inserted or served since then stays, the rest goes
+//   k_shared_close   one thread: books the sweep (live after it, evicted in all) and, above the mark, records the current
 //                    stamp as the next cutoff -- in a launch of its own, after every workgroup of the pass has read the old one
-// A sweep under the high-water mark records nothing, so the interval an entry has to be used in runs from the last sweep that
-// evicted: a whole fill of the table, not one move.  Before the first recording there is no cutoff and nothing is evicted.
+// A sweep under the high-water mark records nothing, so the interval an entry has to be used in runs from the last sweep above
+// the mark (whether or not it found an entry to evict): a whole fill of the table, not one move.  Before the first recording
+// there is no cutoff and nothing is evicted.
 //
 // Why a sweep may run with selects pending (free-running self-play): a pending leaf that names a slot found it in the latest
 // tree-step launch, which left the current stamp in the slot's last-hit word; the cutoff is a stamp recorded earlier, never

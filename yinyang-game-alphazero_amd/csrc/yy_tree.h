@@ -298,7 +298,7 @@ __host__ __device__ __forceinline__ uint32_t sh_next_stamp(uint32_t s) {
     return sh_free(s) ? 1u : s;
 }
 // sh_sweep words: live entries counted by the running sweep, entries it evicted, live entries after the last sweep, entries
-// evicted since the table was set or the counters reset, the stamp recorded by the last sweep that evicted (0: none yet)
+// evicted since the table was set or the counters reset, the stamp recorded by the last sweep above the mark (0: none yet)
 enum { SH_SW_COUNT = 0, SH_SW_EVICTING = 1, SH_SW_LIVE = 2, SH_SW_EVICTED = 3, SH_SW_CUTOFF = 4, SH_SWEEP_WORDS = 8 };
 
 struct MultiDev {  // by-value kernel argument of the K > 1 kernels, next to MctsDev

@@ -582,7 +582,7 @@ class SharedEvaluations:
     insert one position in one launch exactly one takes a slot (the others count as `duplicates`); a hit leaves the launch's
     stamp in the slot's `last_hit` word; and sweep() -- launches of its own between two tree steps, called by the engines --
     evicts, once more than high_water * slots entries are live, every entry neither inserted nor served since the last sweep
-    that evicted.  high_water (a fraction of the slots, an attribute that may be changed between sweeps): None =
+    above that mark.  high_water (a fraction of the slots, an attribute that may be changed between sweeps): None =
     options.SHARED_EVALUATIONS_HIGH_WATER; profiles/shared_evaluations_replace.json holds the comparison it was taken from.
     12 bytes a slot more than the insert-only table.  The same games either way."""
 
