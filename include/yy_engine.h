@@ -69,7 +69,13 @@ extern "C" {
                               into: at 8x8 / 800 simulations about half of the rows that are new within a search were
                               evaluated by an earlier search of the same game).  Entries are replaced oldest-game first,
                               then positions that cannot recur (no more stones than the root).  REQUIRES that every
-                              search of the context uses the same evaluator: call yy_mcts_cache_clear when it changes. */
+                              search of the context uses the same evaluator: call yy_mcts_cache_clear when it changes.
+                              The rules in full (restated by tests/eval_cache_model.py): a fresh evaluation goes into the
+                              first probed slot that is never used, of another epoch, or holds no more stones than the
+                              root, else into the first slot of the window; a hit refreshes nothing (an entry of an older
+                              epoch that is hit is still the first to be replaced); a pass root's own position is stored
+                              as one that cannot recur and is found until its slot is taken; the epoch (24 bits, never
+                              0) advances only at a root without stones, and yy_mcts_cache_clear leaves it. */
 
 #define YY_FLAG_EVAL_SYMMETRY 32u /* symmetry-randomised evaluation (not in the reference; copied boards only: create refuses it
                               with YY_FLAG_ALIASED).  Every position (black, white) is shown to the evaluator under a board symmetry

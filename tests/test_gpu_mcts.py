@@ -8,7 +8,9 @@ import os
 import numpy as np
 import pytest
 
+import eval_cache_cases as K
 import oracle_lib as O
+from eval_cache_model import HIT, cache_slots, replay
 from hash_eval import hash_eval_batch, planes_to_boards
 
 pytestmark = pytest.mark.gpu
@@ -362,7 +364,8 @@ def test_evaluation_reuse_returns_the_same_search(pkg, fused, shape, G, sims, ma
 def test_evaluation_cache_replacement_keeps_results(pkg):
     """A tiny cache (sized from nodes_per_game: 128 slots per game) across eight consecutive searches of advancing positions:
     the table fills, entries of positions that cannot recur are replaced, then live ones; every search still returns what the
-    plain search returns, and later searches find positions of earlier ones."""
+    plain search returns, and later searches find positions of earlier ones -- exactly as often as the restatement of the cache
+    (tests/eval_cache_model.py) predicts from the leaves a reuse_pass_value context of the same searches consults."""
     import torch
     from hash_eval import hash_eval_torch
     E = pkg.engine
@@ -371,12 +374,20 @@ def test_evaluation_cache_replacement_keeps_results(pkg):
     ev = lambda p: hash_eval_torch(p, 6, 4)
     plain = E.BatchedMCTS(G, R, C, sims)
     cached = E.BatchedMCTS(G, R, C, sims, reuse_pass_value=True, reuse_transpositions=True, keep_evaluations=True, nodes_per_game=32)
+    looked = E.BatchedMCTS(G, R, C, sims, reuse_pass_value=True, nodes_per_game=32)   # its flagged rows are `cached`'s lookups
+    rec = K.Recorder(looked, True)
+    lookups = [[] for _ in range(G)]
     gen = torch.Generator(device="cuda")
     gen.manual_seed(1)
     hits = []
     for rnd in range(8):
         c0 = plain.search(boards, players, ev, sims)
         w0 = plain.root_stats()[1]
+        assert torch.equal(c0, looked.search(boards, players, rec, sims))
+        ne, pos = rec.take()
+        stones = (boards != 0).sum((1, 2)).cpu().numpy()
+        for g in range(G):
+            lookups[g].append((int(stones[g]), *K.game_lookups(ne, pos, g)[1:]))
         cached.reset_counters()
         c1 = cached.search(boards, players, ev, sims)
         assert torch.equal(c0, c1) and torch.equal(w0, cached.root_stats()[1]), rnd
@@ -388,7 +399,13 @@ def test_evaluation_cache_replacement_keeps_results(pkg):
     plain.status()
     plain.close()
     cached.close()
-    assert min(hits[1:]) > 0, hits
+    looked.close()
+    want = np.zeros(8, np.int64)
+    for g in range(G):
+        out, _ = replay(lookups[g], cache_slots(32, G, R * C), True)
+        want += [int((o == HIT).sum()) for o in out]
+    print("hits per search", hits)
+    assert hits == want.tolist() and min(hits[1:]) > 0, (hits, want.tolist())
 
 
 def test_opening_book_enumerates_the_reachable_positions(pkg):
