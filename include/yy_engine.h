@@ -128,6 +128,26 @@ extern "C" {
                               the mean over its visited children on purpose: it is in the units and the sign convention of the
                               W / N it stands in for.  Flag clear: every kernel does what it did without it. */
 
+#define YY_FLAG_SOLVER 256u /* MCTS-Solver (Winands et al. 2008; Lc0's "certainty propagation"; not in the reference): exact
+                              results are proven in the tree and descents stop below them.  Copied boards and leaves_per_step
+                              <= 1 only (create returns YY_E_UNSUPPORTED otherwise); every other flag.  A node may carry a proven
+                              status for its side to move -- 1 WIN, 2 LOSS, 3 DRAW -- with the exact value f32 1 / -1 / 1e-4,
+                              the terminal values of the tree.  A terminal node is proven with the class of its terminal value.
+                              A node without children (the mover has no move, the game is not over) is never proven: no proof
+                              looks through a pass.  After the backup of a descent that ended on a terminal node (a revisit, or
+                              the expansion that found the position terminal) or on a proven node, the path is walked upwards
+                              from the leaf's parent: a node with k > 0 children becomes WIN if any child that exists is LOSS
+                              for the child's mover; otherwise, if all k children exist and all are proven, DRAW if any is
+                              DRAW, else LOSS; the walk stops at the first node whose status does not change.  The root may
+                              become proven.  A proven node below the root ends a descent there: no evaluator row
+                              (needs_eval = 0), its exact value is backed up exactly as a terminal revisit's is (a python
+                              number, the same arithmetic), and the walk runs again (it changes nothing).  The root is never
+                              treated as terminal: a search keeps spreading its budget over the root's children.  Selection
+                              scores, visit counts, value sums and the root distribution are computed as without the flag;
+                              the value sums of a proven node are not rewritten.  yy_mcts_advance carries the statuses with
+                              the node records.  Flag clear: no node ever carries a status and every kernel does what it did
+                              without it. */
+
 typedef void *yy_stream_t;
 
 const char *yy_last_error(void);
@@ -312,6 +332,14 @@ int yy_mcts_reset_counters(yy_mcts *ctx, yy_stream_t stream);
 /* sync. YY_FLAG_FORCED_PLAYOUTS: the root descents, over all games, that took a forced edge since create or the last
  * yy_mcts_reset_counters (host out; 0 without the flag). */
 int yy_mcts_forced_descents(yy_mcts *ctx, uint64_t *out);
+/* YY_FLAG_SOLVER.  yy_mcts_root_proven: the proven status of every game's root, root int8 [G], and of the root's children by
+ * action, child int8 [G,A] (0 none -- also: no such child yet --, 1 WIN, 2 LOSS, 3 DRAW, each for the side to move AT THAT NODE:
+ * a child that is LOSS is a winning move); all 0 without the flag and for an inactive game.  yy_mcts_solver_counters: sync;
+ * host out[3] = {nodes proven by propagation, descents that ended on a proven node below the root, searches whose root became
+ * proven} over all games since create or the last yy_mcts_reset_counters (0 without the flag).  Both after a completed search:
+ * YY_E_STATE with a select or a root expansion pending. */
+int yy_mcts_root_proven(yy_mcts *ctx, int8_t *root, int8_t *child, yy_stream_t stream);
+int yy_mcts_solver_counters(yy_mcts *ctx, uint64_t *out);
 /* Shared book of pre-evaluated positions.  Every self-play game starts from the empty board, so the searches of the first plies
  * of ALL games walk the same few hundred thousand positions (8x8: 770 232 positions with <= 8 stones are reachable).  The
  * caller enumerates them, evaluates them once in large batches with the SAME evaluator the searches use, and hands the table

@@ -8,7 +8,8 @@
 Flags added to the reference's set: --concurrent-games, --lanes, --board-semantics {copied,aliased}, --reference-quirks,
 --nn {auto,f16x3,bf16,fp32,fp32t}, --evaluation-reuse, --opening-book-stones, --seed, --arena-games, --channels, --blocks, --fresh,
 --dist-backend, --reference-format, --leaves-per-step, --fast-simulations, --full-search-probability, --tree-reuse, --free-running,
---evaluation-symmetry, --symmetry-seed, --forced-playouts, --fpu-reduction, --fpu-reduction-root, --shared-evaluations, --shared-evaluations-replace.
+--evaluation-symmetry, --symmetry-seed, --forced-playouts, --fpu-reduction, --fpu-reduction-root, --shared-evaluations, --shared-evaluations-replace,
+--solver.
 `--mode train` runs
 the iteration loop (GPU self-play -> PyTorch-ROCm training -> batched arena -> promote at 0.6) and
 `--mode evaluate` plays 10 games against RandomPlayer, like the reference's modes.
@@ -115,6 +116,11 @@ def parse_args(argv=None):
                    help="self-play and train, with --shared-evaluations: the table keeps one slot per position and sheds what is no "
                         "longer used (a sweep per move, or per poll with --free-running), so it serves a run of any length from "
                         "its fixed size (default off; the same games)")
+    p.add_argument("--solver", action="store_true",
+                   help="self-play, train (self-play and arena) and evaluate: MCTS-Solver -- wins, losses and draws proven from "
+                        "terminal positions are propagated up the tree, a descent stops at a proven node below the root without "
+                        "asking the network, and the arena plays a proven winning move when the root has one (default off; changes "
+                        "which moves are picked; not with --leaves-per-step > 1, --board-semantics aliased or --reference-quirks)")
     return p.parse_args(argv)
 
 
@@ -123,10 +129,10 @@ def parse_args(argv=None):
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
            "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
-           "shared_evaluations_replace")
+           "shared_evaluations_replace", "solver")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
-          "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root")]}
+          "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root", "solver")]}
 
 
 def _flag(args, name):
@@ -192,7 +198,7 @@ def main(argv=None):
                            evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
                            forced_playouts=args.forced_playouts, fpu_reduction=args.fpu_reduction,
                            fpu_reduction_root=args.fpu_reduction_root, shared_evaluations=args.shared_evaluations,
-                           shared_evaluations_replace=args.shared_evaluations_replace)
+                           shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -206,7 +212,8 @@ def main(argv=None):
         res = pkg.evaluate_vs_random(game, model_path, num_games=10, num_simulations=args.simulations, nn_mode=args.nn,
                                      num_channels=args.channels, num_res_blocks=args.blocks,
                                      leaves_per_step=args.leaves_per_step, tree_reuse=args.tree_reuse,
-                                     fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root)
+                                     fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
+                                     solver=args.solver)
         print(json.dumps(res))
         return
     if not os.path.exists(model_path):           # same contract as the reference (train_alphazero.py:107-109)
@@ -226,7 +233,7 @@ def main(argv=None):
                                        symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts,
                                        fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
                                        shared_evaluations=args.shared_evaluations,
-                                       shared_evaluations_replace=args.shared_evaluations_replace)
+                                       shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

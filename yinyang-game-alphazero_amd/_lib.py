@@ -19,6 +19,7 @@ FLAG_KEEP_EVALUATIONS = 16
 FLAG_EVAL_SYMMETRY = 32
 FLAG_FORCED_PLAYOUTS = 64
 FLAG_FPU_REDUCTION = 128
+FLAG_SOLVER = 256
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -97,6 +98,8 @@ _SIGS = {
     "yy_mcts_status": [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)],
     "yy_mcts_reset_counters": [_vp, _vp],
     "yy_mcts_forced_descents": [_vp, C.POINTER(C.c_uint64)],
+    "yy_mcts_root_proven": [_vp, _vp, _vp, _vp],
+    "yy_mcts_solver_counters": [_vp, C.POINTER(C.c_uint64)],
     "yy_mcts_cache_clear": [_vp, _vp],
     "yy_book_insert": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, _vp],
     "yy_mcts_set_book": [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int],

@@ -97,6 +97,16 @@ def _lowest_argmax(pi):
     return torch.where(best, idx, torch.full_like(idx, A)).min(1).values.to(torch.int32)
 
 
+def proven_winning_move(ctx):
+    """solver: per game of the finished search on `ctx` the root child that is proven lost for its own side to move -- a move
+    that wins by force -- with the most visits, the lowest action among ties; -1 where there is none (int32 [G], device)."""
+    _, child = ctx.root_proven()
+    counts = ctx.root_counts()
+    wins = child == 2
+    pick = _lowest_argmax(torch.where(wins, counts, torch.full_like(counts, -1)))
+    return torch.where(wins.any(1), pick, torch.full_like(pick, -1))
+
+
 class Arena:
     """num_games games between two players on one GPU.  A player is a batched evaluator
     (planes -> policy, value) searched with `num_simulations`, or the string "random" (uniformly random
@@ -106,8 +116,11 @@ class Arena:
 
     def __init__(self, game, player_a, player_b, num_simulations=800, cpuct=1.0, device=None, seed=0,
                  reference_scoring=False, literal=False, evaluation_reuse=True, leaves_per_step=1, tree_reuse=False,
-                 fpu_reduction=None, fpu_reduction_root=None):
-        """fpu_reduction r > 0 with fpu_reduction_root (None: r): first-play urgency reduction in every search of the match, both
+                 fpu_reduction=None, fpu_reduction_root=None, solver=False):
+        """solver=True: the MCTS-Solver in every search of the match, both players' (options.SearchOptions; default off), and
+        a searching player whose root has a child that is proven lost for the opponent plays the most visited such child (the
+        lowest action among ties) instead of the most visited move.  Not with literal=True or leaves_per_step > 1.
+        fpu_reduction r > 0 with fpu_reduction_root (None: r): first-play urgency reduction in every search of the match, both
         players' (options.SearchOptions; None / 0 = off, the reference's q = 0 for an unvisited child).
         evaluation_reuse: inside one search a position is evaluated once (pass values, other move orders) when both players
         are row-independent compacting evaluators (the float32-accurate BatchedEvaluator); the moves are the same.
@@ -128,9 +141,11 @@ class Arena:
         player's next search tops the kept root up to num_simulations.  Not with literal=True or leaves_per_step > 1."""
         self.game = game
         opts = options.resolve(num_simulations, leaves_per_step, "aliased" if literal else "copied", tree_reuse=tree_reuse,
-                               fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root)
+                               fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root, solver=solver)
         self.tree_reuse, self.K = opts.tree_reuse, opts.leaves_per_step
         self.fpu = dict(fpu_reduction=opts.fpu_reduction, fpu_reduction_root=opts.fpu_reduction_root) if opts.fpu_reduction else {}
+        self.solver = opts.solver
+        self.ctx_keywords = dict(self.fpu, **(dict(solver=True) if self.solver else {}))   # of every tree context of the match
         self.literal = bool(literal)
         self.evaluation_reuse = bool(evaluation_reuse)
         self.reference_scoring = bool(reference_scoring) or self.literal
@@ -162,7 +177,7 @@ class Arena:
                  and self.K == 1)
         ctx = engine.BatchedMCTS(G, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
                                  aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse,
-                                 leaves_per_step=self.K, **self.fpu)
+                                 leaves_per_step=self.K, **self.ctx_keywords)
         own = []           # tree_reuse: (the player moves as A, its evaluator's search on its own context)
         try:
             search = LockstepSearch(ctx, dual, use_graph=dense)     # routed mode: the row sets change every move
@@ -172,7 +187,7 @@ class Arena:
                         n = len(range(par, G, 2))
                         if who != "random" and n > 0:
                             c = engine.BatchedMCTS(n, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
-                                                       **self.fpu)
+                                                       **self.ctx_keywords)
                             own.append((is_a, par, LockstepSearch(c, ev, use_graph=dense)))
             result = torch.zeros(G, dtype=torch.int8, device=dev)   # +1 black won, -1 white won, 2 draw
             ended_at = torch.zeros(G, dtype=torch.float64, device=dev)
@@ -214,12 +229,11 @@ class Arena:
                     if bool(mine.any()):
                         own_search.run(boards[par::2].contiguous(), players[par::2].contiguous(), self.sims, noise=None,
                                        active=mine.to(torch.uint8).contiguous())
-                        action[par::2] = torch.where(mine, _lowest_argmax(own_search.ctx.root_policy()), action[par::2])
+                        action[par::2] = torch.where(mine, self._move(own_search.ctx), action[par::2])
                 if not own and bool(srch.any()):
                     dual.assign(a_to_move)
                     search.run(boards, players, self.sims, noise=None, active=srch.to(torch.uint8))
-                    pi = ctx.root_policy()                               # search() returns the T == 1 distribution (:329)
-                    action = torch.where(srch, _lowest_argmax(pi), action)   # select_action(temperature=0), :471-472
+                    action = torch.where(srch, self._move(ctx), action)
                     if self.literal:                                     # the search mutated the game's board (Q2)
                         boards = torch.where(srch[:, None, None], ctx.boards(), boards).contiguous()
                 rnd = movers & rand_rows
@@ -261,6 +275,15 @@ class Arena:
         b_wins = int(((black_won & ~a_is_black) | (white_won & a_is_black)).sum())
         return dict(a_wins=a_wins, b_wins=b_wins, draws=G - a_wins - b_wins, games=G)
 
+    def _move(self, ctx):
+        """The move of every game of the finished search on `ctx`: np.argmax of the T == 1 distribution search() returns
+        (mcts.py:329), select_action(temperature=0) (:471-472); with the solver a proven winning move first."""
+        action = _lowest_argmax(ctx.root_policy())
+        if self.solver:
+            won = proven_winning_move(ctx)
+            action = torch.where(won >= 0, won, action)
+        return action
+
 
 class RandomPlayer:
     """yin_yang_players.py:5-42 (without the print)."""
@@ -277,8 +300,10 @@ class AlphaZeroPlayer:
     """alphazero.py:272-365: network + MCTS behind `play(board, player) -> action` (-1 = no move)."""
 
     def __init__(self, game, model_path, num_simulations=800, num_threads=1, device=None, leaves_per_step=1, tree_reuse=False,
-                 fpu_reduction=None, fpu_reduction_root=None):
-        """fpu_reduction / fpu_reduction_root: first-play urgency reduction in the player's searches (MCTS).
+                 fpu_reduction=None, fpu_reduction_root=None, solver=False):
+        """solver: the MCTS-Solver in the player's searches (MCTS); play() then takes the most visited root child that is
+        proven lost for the opponent when there is one (the lowest action among ties), else the move it takes without it.
+        fpu_reduction / fpu_reduction_root: first-play urgency reduction in the player's searches (MCTS).
         tree_reuse: play() re-roots the search tree at the move chosen and notify() at the opponent's reply (MCTS tree_reuse),
         so that the next play() continues from the kept subtree."""
         self.game = game
@@ -290,7 +315,8 @@ class AlphaZeroPlayer:
         self.neural_net = net.to(dev).eval()
         self.mcts = MCTS(game, self.neural_net, num_simulations=num_simulations, num_threads=num_threads,
                          board_semantics="copied", device=dev, leaves_per_step=leaves_per_step,
-                         tree_reuse=tree_reuse, fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root)
+                         tree_reuse=tree_reuse, fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root,
+                         solver=solver)
         self.root = None
 
     def reset(self):
@@ -303,6 +329,9 @@ class AlphaZeroPlayer:
         if np.sum(valid) == 0:
             return -1
         action = int(self.mcts.select_action(board, player, temperature=0, valid_moves=valid))
+        if self.mcts.solver:
+            won = int(proven_winning_move(self.mcts._ctx[1])[0])
+            action = won if won >= 0 else action
         if self.tree_reuse:
             self.mcts.reuse_tree(None, board, -player, action)                  # alphazero.py:346
         return action
@@ -330,8 +359,9 @@ class AlphaZero:
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False):
-        """shared_evaluations_replace: the loop's self-play uses the replacing table (options.SearchOptions).
+                 shared_evaluations_replace=False, solver=False):
+        """solver: the MCTS-Solver (options.SearchOptions) in the loop's self-play and, as a playing-strength parameter, its arena.
+        shared_evaluations_replace: the loop's self-play uses the replacing table (options.SearchOptions).
         shared_evaluations: the loop's self-play shares evaluations between the games of a lane (options.SearchOptions); every
         iteration's self-play builds its engines, and with them new, empty tables, for the network it plays with.  The arena
         plays two networks and takes no table.
@@ -345,7 +375,8 @@ class AlphaZero:
                                        free_running=free_running, evaluation_symmetry=evaluation_symmetry,
                                        symmetry_seed=symmetry_seed, forced_playouts=forced_playouts,
                                        fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root,
-                                       shared_evaluations=shared_evaluations, shared_evaluations_replace=shared_evaluations_replace)
+                                       shared_evaluations=shared_evaluations, shared_evaluations_replace=shared_evaluations_replace,
+                                       solver=solver)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold
@@ -405,7 +436,8 @@ class AlphaZero:
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
                      leaves_per_step=self.options.leaves_per_step, tree_reuse=self.options.tree_reuse,
-                     fpu_reduction=self.options.fpu_reduction, fpu_reduction_root=self.options.fpu_reduction_root).play(mine)
+                     fpu_reduction=self.options.fpu_reduction, fpu_reduction_root=self.options.fpu_reduction_root,
+                     solver=self.options.solver).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)
@@ -449,13 +481,13 @@ class AlphaZero:
 
 def evaluate_vs_random(game, model_path, num_games=10, num_simulations=800, nn_mode="auto", device=None,
                        num_channels=128, num_res_blocks=10, leaves_per_step=1, tree_reuse=False,
-                       fpu_reduction=None, fpu_reduction_root=None):
+                       fpu_reduction=None, fpu_reduction_root=None, solver=False):
     """`--mode evaluate` (train_alphazero.py:124-243): the model against RandomPlayer, alternating colours.  leaves_per_step:
-    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search).  tree_reuse, fpu_reduction / fpu_reduction_root:
-    Arena's."""
+    leaf-parallel searches (MCTS leaves_per_step; 1 = the reference's search).  tree_reuse, fpu_reduction / fpu_reduction_root,
+    solver: Arena's."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     ev = _load_evaluator(game, model_path, dev, nn_mode, num_channels, num_res_blocks)
     res = Arena(game, ev, "random", num_simulations, device=dev, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse,
-                fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root).play(num_games)
+                fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root, solver=solver).play(num_games)
     return dict(alphazero_wins=res["a_wins"], random_wins=res["b_wins"], draws=res["draws"],
                 win_rate=res["a_wins"] / num_games)

@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 109
+#define YY_VERSION 110
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -895,7 +895,12 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         const uint4 hdr = nodes[node];
         const uint32_t hy = rfl(hdr.y);
         const int k = node_k(hy), first = rfl((int)hdr.x);
-        if (node_flags(hy) & NF_TERMINAL) { kind = K_TERMINAL; break; }            // mcts.py:360, 365
+        // solver: a proven flag is only ever set with YY_FLAG_SOLVER, so without it this is the terminal test it was.  A proven
+        // node below the root ends the descent like a terminal one; the root is never treated as terminal
+        if (node_flags(hy) & (NF_TERMINAL | NF_PROVEN_MASK)) {
+            if (node_flags(hy) & NF_TERMINAL) { kind = K_TERMINAL; break; }        // mcts.py:360, 365
+            if (node != 0) { kind = K_PROVEN; break; }
+        }
         if (k == 0) {                                                              // mcts.py:93-95
             // A node without children is evaluated again on every visit.  With copied boards its board never changes,
             // so that evaluation returns the value it returned the first time: YY_FLAG_REUSE_PASS_VALUE takes it from
@@ -908,8 +913,10 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         // sum of child visits (mcts.py:112).  Copied boards: every visit of an expanded node after its
         // first descends into exactly one child, so the sum is N(node)-1 (root: completed simulations) and
         // is carried down the descent; aliased boards can give a pass node children later, so sum there.
+        // solver: only the root is descended from while proven (a kept root, or one proven in this search), and the visits
+        // that ended ON it while it was a proven node below a root went into no child: sum there as well.
         int S;
-        if (d.aliased) {
+        if (d.aliased | (node_flags(hy) & NF_PROVEN_MASK)) {
             uint32_t part = 0;
             for (int j = lane; j < k; j += 64) part += edges[first + j].y;
             S = (int)wave_uadd(part);
@@ -1017,6 +1024,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         if (need) st->ctr[0] += 1;
         if (kind == K_TERMINAL) st->ctr[4] += 1;
         if (kind == K_REUSE) st->ctr[6] += 1;
+        if (kind == K_PROVEN) st->sv[1] += 1;
         if (c_forced) st->forced += 1;
         if (needs_eval) needs_eval[g] = need;
     }
@@ -1045,6 +1053,49 @@ __device__ __forceinline__ void noise_kept_root(const MctsDev &d, const int g, c
     }
 }
 
+// ---- solver (YY_FLAG_SOLVER; Winands et al. 2008, "Monte-Carlo Tree Search Solver"): after the backup of a descent of `depth`
+// edges that ended on a terminal or proven node, the path is walked upwards from the leaf's parent.  A node with k > 0 children
+// is a WIN for its side to move if any child that exists is a LOSS for the child's; else, if all k children exist and all are
+// proven, a DRAW if any is one, else a LOSS.  The walk stops at the first node whose status does not change (a status never
+// changes once set, so that is a node that stays open or one that is proven already); the root may become proven.  A node
+// without children (a pass) is never proven, and the statistics of a proven node are not rewritten.  Wave-uniform: per level one
+// pass over the node's edges and the headers of its children.
+__device__ __forceinline__ void solver_propagate(GameState *st, uint4 *nodes, const uint4 *edges, const int32_t *path,
+                                                 const int depth) {
+    const int lane = lane_id();
+    int c_proven = 0, c_root = 0;
+    for (int lvl = depth - 1; lvl >= 0; lvl--) {
+        __syncthreads();   // lane 0 wrote the leaf's record and its parent's edge (expand_leaf), and the level below
+        const int n = (lvl == 0) ? 0 : (int)(rfl(edges[path[lvl - 1]].w) & CHILD_NONE);
+        const uint4 hdr = nodes[n];
+        const uint32_t hy = rfl(hdr.y);
+        const int k = node_k(hy), first = rfl((int)hdr.x);
+        if ((node_flags(hy) & (NF_TERMINAL | NF_PROVEN_MASK)) || k == 0) break;
+        uint64_t loss = 0, draw = 0, open = 0;
+        for (int j0 = 0; j0 < k; j0 += 64) {
+            const int j = j0 + lane;
+            int s = -1;                                                             // no such child
+            if (j < k) {
+                const uint32_t c = edges[first + j].w & CHILD_NONE;
+                s = (c == CHILD_NONE) ? (int)PV_NONE : node_proven(nodes[c]);
+            }
+            loss |= __ballot(s == PV_LOSS);
+            draw |= __ballot(s == PV_DRAW);
+            open |= __ballot(s == PV_NONE);
+        }
+        const int s = loss ? PV_WIN : open ? PV_NONE : draw ? PV_DRAW : PV_LOSS;
+        if (s == PV_NONE) break;
+        if (lane == 0)
+            nodes[n] = make_uint4(hdr.x, hdr.y | ((uint32_t)s << (16 + NF_PROVEN_SHIFT)), __float_as_uint(proven_value(s)), hdr.w);
+        c_proven += 1;
+        c_root += (n == 0);
+    }
+    if (lane == 0 && c_proven) {
+        st->sv[0] += (uint64_t)c_proven;
+        st->sv[2] += (uint64_t)c_root;
+    }
+}
+
 // ---- expansion + backup: mcts.py:50-91 (expand_leaf), 147-156 + 406-412 (backup_path)
 template <int NW>
 __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, const float *policy,
@@ -1066,9 +1117,11 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
     const int node = rfl(st->leaf.node);
     float v;
     bool v_is_py = false;   // value is a python number (terminal value), not np.float32
-    if (kind == K_TERMINAL) {
-        v = rflf(__uint_as_float(nodes[node].z));                                   // mcts.py:366
+    bool exact = false;     // solver: the descent ended on a terminal or proven node
+    if (kind == K_TERMINAL || kind == K_PROVEN) {
+        v = rflf(__uint_as_float(nodes[node].z));                                   // mcts.py:366; a proven node's exact value
         v_is_py = true;
+        exact = true;
     } else if (kind == K_REUSE) {
         v = rflf(__uint_as_float(nodes[node].w));                                   // the np.float32 the evaluator returned for this node
     } else {
@@ -1085,10 +1138,12 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
         }
         if (d.ec.meta && src == SRC_NONE && !root) cache_store<NW>(d, st, g, policy, v);
         if (d.sh.meta && src == SRC_NONE && !root) shared_store<NW>(d, st, g, policy, v, stamp);
+        exact = d.solver && kind == K_EXPAND && rfl((int)st->leaf.terminal) != 0;   // the new node is a terminal one
     }
     if (lane == 0) st->leaf.kind = K_NONE;
     if (kind == K_ROOTINIT) return;                                                 // no backup
     backup_path(edges, path, depth, v, v_is_py, st);
+    if (d.solver && exact) solver_propagate(st, d.nodes + (size_t)g * d.node_cap, edges, path, depth);   // wave-uniform
 }
 
 template <int NW> __global__ void __launch_bounds__(64) k_mcts(MctsDev d, int do_backup, int do_sel,
@@ -1493,6 +1548,7 @@ __global__ void k_reset_counters(MctsDev d) {
     for (int i = 0; i < 8; i++) d.state[g].ctr[i] = 0;
     d.state[g].forced = 0;
     for (int i = 0; i < 4; i++) d.state[g].shc[i] = 0;
+    for (int i = 0; i < 3; i++) d.state[g].sv[i] = 0;
     if (g == 0 && d.sh_sweep) d.sh_sweep[SH_SW_EVICTED] = 0;
 }
 
@@ -1500,6 +1556,34 @@ __global__ void k_forced_sum(MctsDev d, uint64_t *out) {
     uint64_t acc = 0;
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x) acc += d.state[g].forced;
     if (acc) atomicAdd((unsigned long long *)out, (unsigned long long)acc);
+}
+
+// solver: the root's proven status int8 [G] and that of the root's children by action int8 [G,A] (PV_*: 0 none, 1 WIN, 2 LOSS,
+// 3 DRAW, each for the side to move at that node); all 0 without YY_FLAG_SOLVER and for an inactive game
+template <int NW> __global__ void __launch_bounds__(64) k_root_proven(MctsDev d, int8_t *root, int8_t *child) {
+    const int g = blockIdx.x, A = d.geo.A;
+    const uint4 *nodes = d.nodes + (size_t)g * d.node_cap;
+    const uint4 hdr = nodes[0];
+    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+    const bool on = d.solver && rfl((int)d.state[g].active) != 0;
+    for (int a = lane_id(); a < A; a += 64) child[(size_t)g * A + a] = 0;
+    if (lane_id() == 0) root[g] = on ? (int8_t)node_proven(hdr) : (int8_t)0;
+    __syncthreads();
+    if (!on || (node_flags(rfl(hdr.y)) & NF_TERMINAL)) return;
+    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    for (int j = lane_id(); j < k; j += 64) {
+        const uint4 e = edges[first + j];
+        const uint32_t c = e.w & CHILD_NONE;
+        if (c != CHILD_NONE) child[(size_t)g * A + (int)(e.w >> 24)] = (int8_t)node_proven(nodes[c]);
+    }
+}
+
+__global__ void k_solver_sum(MctsDev d, uint64_t *out) {
+    uint64_t acc[3] = {0, 0, 0};
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x)
+        for (int i = 0; i < 3; i++) acc[i] += d.state[g].sv[i];
+    for (int i = 0; i < 3; i++)
+        if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
 }
 
 // ---------------------------------------------------------------------------------- host API
@@ -1524,6 +1608,12 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
             return set_err(YY_E_INVALID, "YY_FLAG_FPU_REDUCTION: fpu_reduction must be positive and finite%s%s");
         if (!(cfg->fpu_reduction_root >= 0.0f && cfg->fpu_reduction_root < INFINITY))
             return set_err(YY_E_INVALID, "YY_FLAG_FPU_REDUCTION: fpu_reduction_root must be finite and >= 0%s%s");
+    }
+    if (cfg->flags & YY_FLAG_SOLVER) {
+        if (cfg->flags & YY_FLAG_ALIASED)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_SOLVER needs copied boards: with the aliased board a node's position changes between visits%s%s");
+        if (cfg->leaves_per_step > 1)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_SOLVER: leaves_per_step > 1 is not supported (proofs under virtual visits are a follow-up)%s%s");
     }
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
@@ -1550,6 +1640,7 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.forced = (cfg->flags & YY_FLAG_FORCED_PLAYOUTS) ? cfg->forced_playouts : 0.0;
     d.fpu = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction : 0.0f;
     d.fpu_root = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction_root : 0.0f;
+    d.solver = (cfg->flags & YY_FLAG_SOLVER) ? 1u : 0u;
     m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
@@ -1783,6 +1874,25 @@ extern "C" int yy_mcts_forced_descents(yy_mcts *c, uint64_t *out) {
     hipLaunchKernelGGL(k_forced_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, c->scratch, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_root_proven(yy_mcts *c, int8_t *root, int8_t *child, yy_stream_t s) {
+    if (!c || !root || !child) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_root_proven with a select or a root expansion pending%s%s");
+    DISPATCH_NW(c->dev.geo.NW, k_root_proven<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, root, child));
+    HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_solver_counters(yy_mcts *c, uint64_t *out) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_solver_counters with a select or a root expansion pending%s%s");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(c->scratch, 0, 3 * sizeof(uint64_t)));
+    hipLaunchKernelGGL(k_solver_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, c->scratch, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return YY_OK;
 }
 

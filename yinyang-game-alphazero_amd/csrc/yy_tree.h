@@ -188,10 +188,16 @@ __device__ __forceinline__ double bb_game_ended(const YYGeo &geo, const GeoBB<NW
 }
 
 // =============================================================================== MCTS context records
-enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6, K_ROOTKEPT = 7 };
+enum : uint8_t { K_NONE = 0, K_TERMINAL = 1, K_EXPAND = 2, K_REEXPAND = 3, K_ROOTPASS = 4, K_ROOTINIT = 5, K_REUSE = 6, K_ROOTKEPT = 7,
+                 K_PROVEN = 8 };   // YY_FLAG_SOLVER: the descent ended on a proven node below the root
 #define CHILD_NONE 0x00FFFFFFu
 #define NF_TERMINAL 1u
 #define NF_HASVALUE 2u   // childless node whose evaluator value (record .w) may be reused (YY_FLAG_REUSE_PASS_VALUE)
+// YY_FLAG_SOLVER: the proven status of a node with children, for its side to move, in two flag bits (PV_*); its exact value
+// is kept where a terminal node keeps its terminal value (record .z).  Never set without the flag.
+#define NF_PROVEN_SHIFT 2
+#define NF_PROVEN_MASK 0xCu
+enum { PV_NONE = 0, PV_WIN = 1, PV_LOSS = 2, PV_DRAW = 3 };
 
 // The pending leaf of one descent: what selection leaves for the expansion + backup that follows the evaluator.  K = 1 keeps
 // the one record of a game in its GameState; leaf-parallel steps (leaves_per_step K > 1) keep descent j of game g in
@@ -229,6 +235,8 @@ struct GameState {
     uint64_t forced;        // forced playouts: root descents that took a forced edge, since create / yy_mcts_reset_counters
     uint64_t shc[4];        // shared evaluation table: leaves it served, rows inserted, inserts dropped (probe window full),
                             // replacing mode: inserts that met their position claimed in the same launch (duplicates)
+    uint64_t sv[3];         // solver (YY_FLAG_SOLVER): nodes proven by propagation, descents ended on a proven node below the
+                            // root, searches whose root became proven
 };
 
 // A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
@@ -285,6 +293,9 @@ struct MctsDev {
     // first-play urgency reduction (YY_FLAG_FPU_REDUCTION): r below the root and r at the root; fpu == 0: off, every kernel
     // does what it did without it (an unvisited child scores q = 0)
     float fpu, fpu_root;
+    // MCTS solver (YY_FLAG_SOLVER): proven statuses are propagated after a descent that ended on an exact value, and a proven
+    // node below the root ends a descent; 0: off, no node ever carries a proven flag and every kernel does what it did without it
+    uint32_t solver;
 };
 
 // ---- shared evaluation table, replacing mode: the claim word and the sweep state (yy_engine.hip, yy_shared_table.hip)
@@ -327,6 +338,15 @@ __device__ __forceinline__ uint32_t node_pack(int k, uint32_t flags, int player)
 __device__ __forceinline__ int node_k(uint32_t y) { return (int)(y & 0xFFFFu); }
 __device__ __forceinline__ uint32_t node_flags(uint32_t y) { return (y >> 16) & 0xFFu; }
 __device__ __forceinline__ int node_player(uint32_t y) { return (int)(int8_t)(y >> 24); }
+
+// ---- solver (YY_FLAG_SOLVER): the three exact values are the terminal ones, f32 of 1 / -1 / 1e-4 for the side to move
+__device__ __forceinline__ int proven_class(float v) { return (v == 1.0f) ? PV_WIN : (v == -1.0f) ? PV_LOSS : PV_DRAW; }
+__device__ __forceinline__ float proven_value(int s) { return (s == PV_WIN) ? 1.0f : (s == PV_LOSS) ? -1.0f : 0.0001f; }
+// the proven status of a node record: a terminal node's is the class of its terminal value, every other node's its flag pair
+__device__ __forceinline__ int node_proven(uint4 hdr) {
+    const uint32_t f = node_flags(hdr.y);
+    return (f & NF_TERMINAL) ? proven_class(__uint_as_float(hdr.z)) : (int)((f & NF_PROVEN_MASK) >> NF_PROVEN_SHIFT);
+}
 
 // getGameEnded(board, player) as float32 + the mask of `player` (yin_yang_game.py:80-110)
 template <int NW>

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, SHARED_EVALUATIONS_HIGH_WATER, forced_k, fpu_r, shared_slots
-from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_SOLVER, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -673,8 +673,12 @@ class BatchedMCTS:
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
                  keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-                 fpu_reduction=None, fpu_reduction_root=None):
-        """fpu_reduction=r > 0 (None / 0 = off: every launch is what it is without the option; KataGo: 0.2), fpu_reduction_root
+                 fpu_reduction=None, fpu_reduction_root=None, solver=False):
+        """solver=True (copied boards and leaves_per_step == 1 only; default off: every launch is what it is without the
+        option): the MCTS-Solver (YY_FLAG_SOLVER, include/yy_engine.h).  Terminal results are propagated up the tree as proven
+        WIN / LOSS / DRAW statuses, a descent that reaches a proven node below the root stops there without an evaluator row,
+        and the root keeps being searched; root_proven() and solver_counters() read the proofs.  Fixed at creation.
+        fpu_reduction=r > 0 (None / 0 = off: every launch is what it is without the option; KataGo: 0.2), fpu_reduction_root
         (None: r; KataGo: 0 at a noised root): first-play urgency reduction (YY_FLAG_FPU_REDUCTION, include/yy_engine.h).  A child
         that has not been visited is scored with the mean value of its visited siblings less r * sqrt(their share of the prior)
         instead of q = 0; the root uses fpu_reduction_root.  Every board semantics and leaves_per_step.  Fixed at creation.
@@ -708,13 +712,15 @@ class BatchedMCTS:
         self.symmetry = symmetry_key(evaluation_symmetry, symmetry_seed)
         self.forced_playouts = forced_k(forced_playouts)
         self.fpu_reduction, self.fpu_reduction_root = fpu_r(fpu_reduction, fpu_reduction_root)
+        self.solver = bool(solver)
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
                          | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0)
                          | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0)
                          | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0)
-                         | (FLAG_FPU_REDUCTION if self.fpu_reduction else 0),
+                         | (FLAG_FPU_REDUCTION if self.fpu_reduction else 0)
+                         | (FLAG_SOLVER if self.solver else 0),
                          int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
                          self.forced_playouts, self.fpu_reduction, self.fpu_reduction_root)
         h = ct.c_void_p()
@@ -854,6 +860,28 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_forced_descents(self._h, ct.byref(n)))
         return int(n.value)
+
+    PROVEN = ("none", "win", "loss", "draw")     # the codes of root_proven(), each for the side to move at that node
+    SOLVER_COUNTERS = ("proven_nodes", "proven_descents", "proven_roots")
+
+    def root_proven(self):
+        """solver: (root int8 [G], children int8 [G,A]) -- the proven status of every game's root and of the root's children
+        by action (0 none, 1 WIN, 2 LOSS, 3 DRAW, each for the side to move at that node: a child that is LOSS is a winning
+        move); all 0 without the option.  After a finished search (YYError with a select pending)."""
+        root = torch.empty(self.G, dtype=torch.int8, device=self.device)
+        child = torch.empty((self.G, self.A), dtype=torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_root_proven(self._h, _p(root), _p(child), _stream()))
+        return root, child
+
+    def solver_counters(self):
+        """sync; solver: {proven_nodes: nodes proven by propagation, proven_descents: descents that ended on a proven node below
+        the root, proven_roots: searches whose root became proven} over all games since create / reset_counters().  After a
+        finished search (YYError with a select pending)."""
+        ctr = (ct.c_uint64 * 3)()
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_solver_counters(self._h, ctr))
+        return dict(zip(self.SOLVER_COUNTERS, [int(x) for x in ctr[:3]]))
 
     def root_stats(self):
         visits = torch.empty(self.G, dtype=torch.int32, device=self.device)

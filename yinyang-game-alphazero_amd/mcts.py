@@ -137,8 +137,13 @@ class MCTS:
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False):
-        """shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False):
+        """solver=True (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; default off): the
+        MCTS-Solver (engine.BatchedMCTS, options.SearchOptions) -- proven wins, losses and draws are propagated in the tree, a
+        descent stops at a proven node below the root without asking the network, and the root keeps being searched.  The
+        distribution search() returns is computed from the visit counts as without it; the proofs are read with the
+        context's root_proven().
+        shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
         replace=True, options.SearchOptions): one slot per position, and a sweep after every search -- with tree_reuse after
         the advance that follows it -- evicts what was not used once the table is nearly full.  The same results.
         shared_evaluations (not in the reference; None / False = off, True = the default size, an int = slots): the searches
@@ -188,6 +193,9 @@ class MCTS:
         # refused without shared_evaluations
         self.shared_evaluations_replace = options.resolve(shared_evaluations=shared_evaluations,
                                                           shared_evaluations_replace=shared_evaluations_replace).shared_evaluations_replace
+        # the resolver's refusals: aliased boards, leaves_per_step > 1
+        self.solver = bool(solver) and options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics,
+                                                       solver=solver).solver
         self._shared_owner = None              # the network whose rows the tables hold
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
@@ -216,7 +224,7 @@ class MCTS:
                                      reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
                                      evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
                                      forced_playouts=self.forced_playouts, fpu_reduction=self.fpu_reduction,
-                                     fpu_reduction_root=self.fpu_reduction_root)
+                                     fpu_reduction_root=self.fpu_reduction_root, solver=self.solver)
             if self.shared_evaluations:
                 ctx.set_shared_evaluations(engine.SharedEvaluations(self.R, self.C, self.shared_evaluations, ctx.device,
                                                                     *self.symmetry, replace=self.shared_evaluations_replace))

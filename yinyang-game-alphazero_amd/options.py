@@ -110,7 +110,21 @@ class SearchOptions:
     evicted (second chance over the whole table; SHARED_EVALUATIONS_HIGH_WATER): a table of a fixed size serves a run of any
     length.  The same games, move for move: a table only ever returns the evaluator's own row for a position, so no eviction
     or duplicate decision can change one.  Without shared_evaluations it is refused; with it, it is refused wherever
-    shared_evaluations is."""
+    shared_evaluations is.
+
+    solver (default False): the MCTS-Solver (Winands et al. 2008; Lc0's "certainty propagation"; include/yy_engine.h
+    YY_FLAG_SOLVER).  Yin-Yang games end by filling the board, so from the middle game on many descents run
+    into terminal positions, whose exact results the reference only ever averages into its value sums.  With the option a node
+    may be proven WIN, LOSS or DRAW for its side to move: a terminal node is; a node with children is a WIN when some child is a
+    LOSS for the opponent, and a LOSS or DRAW once all its children exist and are proven.  A position whose mover has no move is
+    never proven, so every proof consists of real moves and terminal positions only.  A descent that reaches a proven node below
+    the root stops there, backs the exact value up and asks for no evaluator row; the root itself keeps being searched.
+    Scores, visit counts, pi, the temperature rule and self-play's move draw are untouched: the option changes which descents
+    are made, not how they are scored.  AlphaZeroPlayer and the arena play, at temperature 0, the most visited root child that
+    is proven lost for the opponent when there is one.  It goes with the playout cap, tree reuse (statuses travel with the
+    kept nodes), free-running, evaluation reuse, the book, the shared table, evaluation symmetry, forced playouts and
+    fpu_reduction.  Proofs under virtual visits and on a board that changes under a node are follow-ups, and the reference has
+    no such option: refused with leaves_per_step > 1, board_semantics="aliased", reference_quirks and rng="numpy"."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -123,6 +137,7 @@ class SearchOptions:
     fpu_reduction_root: float = 0.0         # resolved: fpu_reduction where it was not given; 0.0 when the option is off
     shared_evaluations: int = 0             # slots of the shared evaluation table (a power of two); 0: off
     shared_evaluations_replace: bool = False  # the table deduplicates inserts and evicts (needs shared_evaluations)
+    solver: bool = False                    # proven wins, losses and draws in the tree
 
     @property
     def playout_cap(self):
@@ -143,6 +158,8 @@ class SearchOptions:
             on.update(shared_evaluations=self.shared_evaluations)
         if self.shared_evaluations_replace:
             on.update(shared_evaluations_replace=True)
+        if self.solver:
+            on.update(solver=True)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
@@ -214,13 +231,14 @@ def fpu_r(fpu_reduction, fpu_reduction_root=None):
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-            fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False):
+            fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
+            solver=False):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
     -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
-    shared_evaluations, shared_evaluations_replace -- so two broken rules name the same option everywhere.  forced_playouts,
+    shared_evaluations, shared_evaluations_replace, solver -- so two broken rules name the same option everywhere.  forced_playouts,
     fpu_reduction: None and 0 = off; shared_evaluations: None and False = off; shared_evaluations_replace: None and False = off."""
     K = max(1, int(leaves_per_step))
     aliased = board_semantics == "aliased"
@@ -301,8 +319,18 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     if replace and not shared:
         raise OptionConflict("shared_evaluations_replace=True: it is the replacing form of the shared evaluation table -- not "
                              "without shared_evaluations", "shared_evaluations_replace", ["shared_evaluations"])
+    if solver not in (None, False, True):
+        raise OptionConflict(f"solver={solver!r}: True or False", "solver")
+    if solver:
+        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
+               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict("solver=True: a proof belongs to a node whose position does not change and to one descent per step, "
+                                 f"and the reference has no such option -- not with {', '.join(b[1] for b in bad)}",
+                                 "solver", [b[0] for b in bad])
     cap = fast is not None and P < 1.0
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
                          evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
-                         shared, replace)
+                         shared, replace, bool(solver))

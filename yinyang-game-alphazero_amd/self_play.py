@@ -89,8 +89,11 @@ class _Engine:
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False):
-        """shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
+                 shared_evaluations_replace=False, solver=False):
+        """solver (default off): the MCTS-Solver in every search, fast and full alike (options.SearchOptions) -- descents stop
+        at proven nodes below the root and ask for no evaluator row; the move draw and the recorded pi are computed from the
+        visit counts as without it and do not look at proofs.
+        shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
         replace=True): one slot per position, and the engine sweeps it -- the lockstep engine once per move, after the move and
         the re-rooting of tree_reuse, the free-running engine at every poll, between two graph replays -- so that it sheds what
         is no longer used; `self.shared.high_water` may be set between sweeps.  The same games.
@@ -121,12 +124,14 @@ class _Engine:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
+                               solver)
         if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
             raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
                              "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
         self.K, self.tree_reuse, self.forced_playouts = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts
         self.fpu_reduction, self.fpu_reduction_root = opts.fpu_reduction, opts.fpu_reduction_root
+        self.solver = opts.solver
         self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
@@ -150,7 +155,8 @@ class _Engine:
                                       reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations,
                                       leaves_per_step=self.K, evaluation_symmetry=self.symmetry[0],
                                       symmetry_seed=self.symmetry[1], forced_playouts=self.forced_playouts,
-                                      fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
+                                      fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root,
+                                      solver=self.solver)
         self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
@@ -629,6 +635,13 @@ class _LaneCounters:
                 tot[k] = tot.get(k, 0) + v
         return tot
 
+    def solver_counters(self):
+        tot = {}
+        for ln in self.lanes:
+            for k, v in ln.ctx.solver_counters().items():
+                tot[k] = tot.get(k, 0) + v
+        return tot
+
 
 class SelfPlayLanes:
     """K independent SelfPlayEngine lanes of G / K games each on K HIP streams of ONE GPU, their moves enqueued back to back.
@@ -647,8 +660,9 @@ class SelfPlayLanes:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, **engine_kwargs):
-        """shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
+                 shared_evaluations_replace=False, solver=False, **engine_kwargs):
+        """solver: the MCTS-Solver in every lane (options.SearchOptions).
+        shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
         size asked for; memory_bytes() reports their sum.  shared_evaluations_replace: every lane's table is a replacing one,
         swept by its lane on the lane's stream.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
@@ -658,7 +672,8 @@ class SelfPlayLanes:
         opts = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, rng,
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
-                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
+                               forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
+                               solver)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -862,8 +877,9 @@ class SelfPlayWorker:
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False):
-        """shared_evaluations: MCTS's (a table shared by the one game's searches; needs board_semantics="copied",
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False):
+        """solver: MCTS's (needs board_semantics="copied" and reference_quirks=False, which are not this class's defaults).
+        shared_evaluations: MCTS's (a table shared by the one game's searches; needs board_semantics="copied",
         reference_quirks=False and a network whose evaluator is row-independent).  shared_evaluations_replace: MCTS's too.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
         class has no seed of its own), forced_playouts, fpu_reduction / fpu_reduction_root (needs reference_quirks=False):
@@ -880,7 +896,7 @@ class SelfPlayWorker:
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
                                forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
                                fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
-                               shared_evaluations_replace=shared_evaluations_replace)
+                               shared_evaluations_replace=shared_evaluations_replace, solver=solver)
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -902,7 +918,7 @@ class SelfPlayWorker:
                          evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
                          forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
                          fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None,
-                         shared_evaluations_replace=opts.shared_evaluations_replace)
+                         shared_evaluations_replace=opts.shared_evaluations_replace, solver=opts.solver)
 
     def play_game(self):
         game, examples = self.game, []
@@ -985,8 +1001,11 @@ class SelfPlayManager:
                  nn_mode="auto", seed=0, num_channels=128, num_res_blocks=10, evaluation_reuse=None,
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-                 fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False):
-        """leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
+                 fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
+                 solver=False):
+        """solver (its three counters go into `stats` as solver_*, in lockstep runs: a free-running context stays armed, and
+        the counters are read after a finished search),
+        leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
         (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root,
         shared_evaluations (a table per lane; its counters, fill and memory go into `stats`), shared_evaluations_replace (the
         replacing table; `stats` then holds its six counters): options.SearchOptions.
@@ -996,7 +1015,7 @@ class SelfPlayManager:
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
                                        tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
-                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace)
+                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace, solver)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -1048,6 +1067,8 @@ class SelfPlayManager:
             counters.update({f"shared_{k}": v for k, v in shc.items()},
                             shared_fill=sum(l.shared.fill() for l in eng.lanes), shared_slots=sum(l.shared.slots for l in eng.lanes),
                             memory_bytes=eng.memory_bytes())
+        if self.options.solver and not self.options.free_running:
+            counters.update({f"solver_{k}": v for k, v in eng.ctx.solver_counters().items()})
         ex = gather_examples(ex, capacity=example_capacity(total, world, eng.T))
         self.stats = dict(seconds=t1 - t0, positions=eng.positions, games=eng.games_finished, **counters,
                           **(dict(steps_issued=eng.steps_issued) if self.options.free_running else {}))
@@ -1063,8 +1084,8 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     alias of `states`) instead of pickled board objects; `reference_format=True` writes the reference's pickled-object
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
-    the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root, shared_evaluations and
-    shared_evaluations_replace among them) are SelfPlayManager's too."""
+    the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root, shared_evaluations,
+    shared_evaluations_replace and solver among them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
