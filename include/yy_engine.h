@@ -48,8 +48,8 @@ extern "C" {
                               With copied boards the node's position never changes, so the evaluator returns the
                               same value each time; with this flag the value of the first evaluation is kept in the
                               node record and a revisit takes it from there: no planes written, needs_eval = 0,
-                              counters[6] += 1.  Visit counts, value sums and pi are unchanged (tests/test_gpu_mcts.py
-                              ::test_evaluation_reuse_*); counters[0] (evaluator rows) gets smaller.  Default off:
+                              counters[6] (TC_REUSED) += 1.  Visit counts, value sums and pi are unchanged (tests/test_gpu_mcts.py
+                              ::test_evaluation_reuse_*); counters[0] (TC_EVALS, evaluator rows) gets smaller.  Default off:
                               the evaluator call sequence is then the reference's, row for row. */
 
 #define YY_FLAG_REUSE_TRANSPOSITIONS 8u /* evaluation cache, one search at a time.  The reference evaluates every leaf
@@ -60,7 +60,7 @@ extern "C" {
                               [position -> policy row f32[A], value], open addressing on a 64-bit mix of the bitboards,
                               <= 8 probes, keys compared in full; a leaf whose position is in the table takes its
                               evaluation from there instead of an evaluator row (needs_eval = 0, no planes written,
-                              counters[7] += 1).  Only entries written by the current search are used.  Same visit
+                              counters[7] (TC_TABLE_HITS) += 1).  Only entries written by the current search are used.  Same visit
                               counts, value sums and pi (tests/test_gpu_mcts.py::test_evaluation_reuse_*).  Works with
                               copied and aliased boards (the key is the position, not the node).  Default off: the
                               evaluator's call sequence is then the reference's, row for row. */
@@ -231,7 +231,7 @@ typedef struct yy_mcts_config {
  * A descent that ends on the leaf of an earlier descent of the same step (the same unexpanded edge, the same childless node,
  * the pass root) asks for no row: it shares that descent's evaluation and still counts as a simulation.  A terminal leaf asks
  * for no row either.  Rows are game-major: select / step write planes [G*K,5,R,C] and needs_eval [G*K], row g*K + j for descent
- * j of game g, needs_eval = 1 only for the first occurrence of a leaf that needs an evaluation (counters[0] counts those rows);
+ * j of game g, needs_eval = 1 only for the first occurrence of a leaf that needs an evaluation (counters[0], TC_EVALS, counts those rows);
  * expand_backup / step read policy [G*K,A] and value [G*K].  After the evaluator, for j = 0 .. K_eff-1 in order: the first
  * occurrence of a leaf expands it as with K = 1, then every descent backs its value up along its own path as with K = 1.  So
  * every step adds K_eff visits to the root, and root.visits == num_sims after ceil(num_sims / K) steps.  yy_mcts_begin writes
@@ -326,7 +326,8 @@ int yy_mcts_get_boards(yy_mcts *ctx, int8_t *boards, yy_stream_t stream);
  * does not clear it, only this call does -- and
  * counters[8] = {evaluator rows requested, selection levels walked, children scanned during
  * selection, children created, terminal revisits, nodes created, pass values reused, evaluation-cache hits} accumulated since create
- * or the last yy_mcts_reset_counters.  Returns YY_E_ARENA if any game overflowed. */
+ * or the last yy_mcts_reset_counters: TC_EVALS .. TC_TABLE_HITS of csrc/yy_tree.h, which names every counter of this and the
+ * readers below.  Returns YY_E_ARENA if any game overflowed. */
 int yy_mcts_status(yy_mcts *ctx, int32_t *n_overflow, uint64_t *counters);
 int yy_mcts_reset_counters(yy_mcts *ctx, yy_stream_t stream);
 /* sync. YY_FLAG_FORCED_PLAYOUTS: the root descents, over all games, that took a forced edge since create or the last
@@ -344,7 +345,7 @@ int yy_mcts_solver_counters(yy_mcts *ctx, uint64_t *out);
  * of ALL games walk the same few hundred thousand positions (8x8: 770 232 positions with <= 8 stones are reachable).  The
  * caller enumerates them, evaluates them once in large batches with the SAME evaluator the searches use, and hands the table
  * to the contexts: a leaf with at most `max_stones` stones is looked up there first (same hash / probe / full key compare as
- * the per-game cache) and, on a hit, needs no evaluator row (counters[7]).  Read-only during play, so no atomics on the
+ * the per-game cache) and, on a hit, needs no evaluator row (counters[7], TC_TABLE_HITS).  Read-only during play, so no atomics on the
  * lookup side; arrays stay owned by the caller and must outlive the context (or be unset with meta = NULL).
  *   yy_book_insert: keys u64 [n, 2*NW] (black words, white words), distinct -> slot_of i32 [n] (-1 = no free slot within
  *   the probe window); fills meta u32 [cap] (zeroed by the caller, cap a power of two) and table_keys u64 [cap, 2*NW].
@@ -359,7 +360,7 @@ int yy_mcts_cache_clear(yy_mcts *ctx, yy_stream_t stream);
 /* Shared evaluation table: the dynamic form of the book.  The games of ONE context fill it while they play: every fresh
  * evaluator row of a non-root leaf is inserted (next to the game's own cache), and a leaf whose position any game of the
  * context had evaluated in an EARLIER launch takes the stored policy row and value instead of an evaluator row
- * (counters[7], and hits in yy_mcts_shared_counters).  Lookup order: book, the game's own cache, the shared table.
+ * (counters[7], TC_TABLE_HITS, and hits, TC_SH_HITS, in yy_mcts_shared_counters).  Lookup order: book, the game's own cache, the shared table.
  *   meta u32 [slots] (zeroed by the caller; 0 = never used, else the step stamp of the launch that inserted the entry),
  *   keys u64 [slots, 2*NW], value f32 [slots], policy f32 [slots, A], slots a power of two in 64 .. 2^30,
  *   stamp u32 [1] in device memory: the step stamp.  The context advances it by one thread in a launch of its own in front

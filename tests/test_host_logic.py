@@ -394,3 +394,22 @@ def test_publish_examples_file_name_is_unique_and_leaves_no_partial(tmp_path):
     assert not glob.glob(str(tmp_path / "*.partial"))
     z = np.load(a)
     assert z["states"].shape == (3, 4, 4) and z["policies"].dtype == np.float64
+
+
+def test_lane_counters_sum_every_reader_over_the_lanes():
+    """self_play._LaneCounters: status(), shared_counters(), shared_counters_ex() and solver_counters() are the key-wise sums of
+    the lanes' contexts, whatever keys a reader returns."""
+    import types
+    from yinyang_game_alphazero_amd.self_play import _LaneCounters
+    methods = ("status", "shared_counters", "shared_counters_ex", "solver_counters")
+
+    def lane(base):
+        readings = {m: {f"{m}_k{j}": base * (i + 1) + j for j in range(3)} for i, m in enumerate(methods)}
+        ctx = types.SimpleNamespace(**{m: (lambda m=m: dict(readings[m])) for m in methods})
+        return types.SimpleNamespace(ctx=ctx), readings
+
+    (a, ra), (b, rb) = lane(10), lane(1000)
+    both = _LaneCounters([a, b])
+    for m in methods:
+        assert getattr(both, m)() == {k: ra[m][k] + rb[m][k] for k in ra[m]}, m
+        assert getattr(_LaneCounters([a]), m)() == ra[m], m

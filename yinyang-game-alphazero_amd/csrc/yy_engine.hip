@@ -563,7 +563,7 @@ __device__ __forceinline__ void shared_store(const MctsDev &d, GameState *st, co
             if (d.sh.meta[at] != 0u) return TT_NEXT;
             return atomicCAS(&d.sh.meta[at], 0u, stamp) == 0u ? TT_HIT : TT_NEXT;
         });
-        st->shc[got >= 0 ? 1 : 2] += 1;
+        st->ctr[got >= 0 ? TC_SH_INSERTS : TC_SH_DROPPED] += 1;
     } else if (lane == 0) {
         // Replacing mode: ONE inserter per position and launch.  The claim word carries this launch's stamp and the half of the
         // hash that indexing does not use, taken in ONE 64-bit atomicCAS on the value observed (0 or a tombstone: both free), so
@@ -588,7 +588,7 @@ __device__ __forceinline__ void shared_store(const MctsDev &d, GameState *st, co
             if (seen == mine) { dup = true; return TT_MISS; }
             return TT_NEXT;
         });
-        st->shc[got >= 0 ? 1 : dup ? 3 : 2] += 1;
+        st->ctr[got >= 0 ? TC_SH_INSERTS : dup ? TC_SH_DUPLICATES : TC_SH_DROPPED] += 1;
         if (got >= 0) d.sh_hit[got] = stamp;         // no lookup of this launch reads or marks a slot claimed in it
     }
     got = rfl(got);
@@ -707,7 +707,7 @@ __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, con
         if (lane == 0) {
             uint4 *pe = edges + path[rfl(rec->path_len) - 1];
             pe->w = (pe->w & 0xFF000000u) | (uint32_t)node;
-            st->ctr[5] += 1;
+            st->ctr[TC_NODES] += 1;
         }
     }
     BB<NW> mask;
@@ -773,7 +773,7 @@ __device__ __forceinline__ bool expand_leaf(const MctsDev &d, GameState *st, con
         if (lane == 0) {
             nodes[node] = make_uint4((uint32_t)n_edges, node_pack(k, (hold && k == 0) ? NF_HASVALUE : 0u, lplayer), 0u,
                                      __float_as_uint(v));                       // .w = the evaluator's value of this position
-            st->ctr[3] += (uint64_t)k;
+            st->ctr[TC_CREATED] += (uint64_t)k;
         }
         n_edges += k;
     }
@@ -908,7 +908,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             kind = (d.reuse && (node_flags(hy) & NF_HASVALUE)) ? K_REUSE : (node == 0) ? K_ROOTPASS : K_REEXPAND;
             break;
         }
-        if (depth >= (int)d.path_cap) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }
+        if (depth >= (int)d.path_cap) { kind = K_NONE; if (lane == 0) fail_game(st); break; }
         // ---- Node.select_child (mcts.py:97-145)
         // sum of child visits (mcts.py:112).  Copied boards: every visit of an expanded node after its
         // first descends into exactly one child, so the sum is N(node)-1 (root: completed simulations) and
@@ -966,7 +966,7 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
                 if (key > bk) { bk = key; bi = j; bw = e.w; bn = e.y; }               // strict >: lowest j of a lane
             }
             best = best_child(bk, bi, k);
-            if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) st->err = st->err_ever = 1; break; }  // no selectable child
+            if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) fail_game(st); break; }  // no selectable child
             w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
             s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
         }
@@ -1011,21 +1011,21 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
         }
         need = src == SRC_NONE;
         if (!need && lane == 0) {
-            st->ctr[7] += 1;
-            if (src >= SRC_SHARED) st->shc[0] += 1;
+            st->ctr[TC_TABLE_HITS] += 1;
+            if (src >= SRC_SHARED) st->ctr[TC_SH_HITS] += 1;
         }
     }
     if (lane == 0) {
         st->leaf.kind = (uint8_t)kind;
         st->leaf.node = node;
         st->leaf.path_len = depth;
-        st->ctr[1] += c_levels;
-        st->ctr[2] += c_scan;
-        if (need) st->ctr[0] += 1;
-        if (kind == K_TERMINAL) st->ctr[4] += 1;
-        if (kind == K_REUSE) st->ctr[6] += 1;
-        if (kind == K_PROVEN) st->sv[1] += 1;
-        if (c_forced) st->forced += 1;
+        st->ctr[TC_LEVELS] += c_levels;
+        st->ctr[TC_SCANNED] += c_scan;
+        if (need) st->ctr[TC_EVALS] += 1;
+        if (kind == K_TERMINAL) st->ctr[TC_TERMINAL] += 1;
+        if (kind == K_REUSE) st->ctr[TC_REUSED] += 1;
+        if (kind == K_PROVEN) st->ctr[TC_SV_DESCENTS] += 1;
+        if (c_forced) st->ctr[TC_FORCED] += 1;
         if (needs_eval) needs_eval[g] = need;
     }
 }
@@ -1091,8 +1091,8 @@ __device__ __forceinline__ void solver_propagate(GameState *st, uint4 *nodes, co
         c_root += (n == 0);
     }
     if (lane == 0 && c_proven) {
-        st->sv[0] += (uint64_t)c_proven;
-        st->sv[2] += (uint64_t)c_root;
+        st->ctr[TC_SV_NODES] += (uint64_t)c_proven;
+        st->ctr[TC_SV_ROOTS] += (uint64_t)c_root;
     }
 }
 
@@ -1133,7 +1133,7 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
         const bool hold = d.reuse && !root;   // a pass node keeps its value; a pass root that of its first simulation
         if (!expand_leaf<NW>(d, st, g, &st->leaf, path, ev.prow, v, hold, d.aliased != 0u, root ? noise : nullptr, eps)) {
             // NaN from the evaluator or a full arena: the game stops searching, the error is sticky
-            if (lane == 0) { st->err = st->err_ever = 1; st->leaf.kind = K_NONE; }
+            if (lane == 0) { fail_game(st); st->leaf.kind = K_NONE; }
             return;
         }
         if (d.ec.meta && src == SRC_NONE && !root) cache_store<NW>(d, st, g, policy, v);
@@ -1284,14 +1284,14 @@ __device__ __forceinline__ void do_select_multi(const MctsDev &d, const MultiDev
         c_term += (kind == K_TERMINAL) ? 1 : 0;
         __syncthreads();   // this descent's path is read by the lanes of the next one
     }
-    if (failed && lane == 0) st->err = st->err_ever = 1;           // path too deep / no selectable child: the game stops
+    if (failed && lane == 0) fail_game(st);                     // path too deep / no selectable child: the game stops
     if (needs_eval && lane < K && (failed || lane >= keff)) needs_eval[(size_t)g * K + lane] = 0;
     if (lane == 0) {
         ms[1] = failed ? 0 : keff;
-        st->ctr[1] += c_levels;
-        st->ctr[2] += c_scan;
-        if (!failed) st->ctr[0] += c_evals;
-        st->ctr[4] += c_term;
+        st->ctr[TC_LEVELS] += c_levels;
+        st->ctr[TC_SCANNED] += c_scan;
+        if (!failed) st->ctr[TC_EVALS] += c_evals;
+        st->ctr[TC_TERMINAL] += c_term;
     }
 }
 
@@ -1326,7 +1326,7 @@ __device__ __forceinline__ void do_expand_backup_multi(const MctsDev &d, const M
             v = (kind == K_ROOTINIT) ? 0.0f : rflf(value[row]);
             if (!expand_leaf<NW>(d, st, g, rec, path, policy + row * d.geo.A, v, false, false, noise, eps)) {
                 // NaN from the evaluator or a full arena: the game stops, the error is sticky
-                if (lane == 0) { st->err = st->err_ever = 1; ms[1] = 0; }
+                if (lane == 0) { fail_game(st); ms[1] = 0; }
                 return;
             }
         }
@@ -1471,7 +1471,7 @@ template <int NW> __global__ void __launch_bounds__(64) k_advance(MctsDev d, con
         }
     if (lane == 0) {
         if (bad) {                 // an inconsistent arena: the game fails like one whose arena overflowed
-            st->err = st->err_ever = 1;
+            fail_game(st);
             st->kept = 0;
             if (kept_visits) kept_visits[g] = 0;
         } else {
@@ -1530,32 +1530,37 @@ template <int NW> __global__ void __launch_bounds__(64) k_get_boards(MctsDev d, 
     bb_to_board<NW>(boards + (size_t)g * d.geo.A, d.geo.A, b, w);
 }
 
-__global__ void k_status(MctsDev d, uint64_t *out /*[9]: 8 counters, overflow games*/) {
-    uint64_t acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+// Every counter summed over the games into out[0 .. TC_COUNT).  take_failures (yy_mcts_status alone): out[TC_COUNT] counts the
+// games that failed in ANY search since the last such call, and their sticky marks are cleared; else no mark is touched
+__global__ void k_tree_counters(MctsDev d, int take_failures, uint64_t *out /*[TC_COUNT + 1], zeroed*/) {
+    uint64_t acc[TC_COUNT + 1] = {};
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x) {
         GameState *st = d.state + g;
-        for (int i = 0; i < 8; i++) acc[i] += st->ctr[i];
-        acc[8] += (st->err || st->err_ever) ? 1 : 0;   // a failure in ANY search since the last status call
-        st->err_ever = 0;
+        for (int i = 0; i < TC_COUNT; i++) acc[i] += st->ctr[i];
+        if (take_failures) {
+            acc[TC_COUNT] += (st->err || st->err_ever) ? 1 : 0;
+            st->err_ever = 0;
+        }
     }
-    for (int i = 0; i < 9; i++)
+    for (int i = 0; i <= TC_COUNT; i++)
         if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
+}
+
+// sync; what k_tree_counters sums, on the host
+static int tree_counters(yy_mcts *c, bool take_failures, uint64_t h[TC_COUNT + 1]) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(c->scratch, 0, (TC_COUNT + 1) * sizeof(uint64_t)));
+    hipLaunchKernelGGL(k_tree_counters, dim3(64), dim3(256), 0, 0, c->dev, (int)take_failures, c->scratch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h, c->scratch, (TC_COUNT + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return YY_OK;
 }
 
 __global__ void k_reset_counters(MctsDev d) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
-    for (int i = 0; i < 8; i++) d.state[g].ctr[i] = 0;
-    d.state[g].forced = 0;
-    for (int i = 0; i < 4; i++) d.state[g].shc[i] = 0;
-    for (int i = 0; i < 3; i++) d.state[g].sv[i] = 0;
+    for (int i = 0; i < TC_COUNT; i++) d.state[g].ctr[i] = 0;
     if (g == 0 && d.sh_sweep) d.sh_sweep[SH_SW_EVICTED] = 0;
-}
-
-__global__ void k_forced_sum(MctsDev d, uint64_t *out) {
-    uint64_t acc = 0;
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x) acc += d.state[g].forced;
-    if (acc) atomicAdd((unsigned long long *)out, (unsigned long long)acc);
 }
 
 // solver: the root's proven status int8 [G] and that of the root's children by action int8 [G,A] (PV_*: 0 none, 1 WIN, 2 LOSS,
@@ -1576,14 +1581,6 @@ template <int NW> __global__ void __launch_bounds__(64) k_root_proven(MctsDev d,
         const uint32_t c = e.w & CHILD_NONE;
         if (c != CHILD_NONE) child[(size_t)g * A + (int)(e.w >> 24)] = (int8_t)node_proven(nodes[c]);
     }
-}
-
-__global__ void k_solver_sum(MctsDev d, uint64_t *out) {
-    uint64_t acc[3] = {0, 0, 0};
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x)
-        for (int i = 0; i < 3; i++) acc[i] += d.state[g].sv[i];
-    for (int i = 0; i < 3; i++)
-        if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
 }
 
 // ---------------------------------------------------------------------------------- host API
@@ -1670,7 +1667,7 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         {(void **)&d.sqrt_tab, (size_t)d.sqrt_n * sizeof(float)},
         {(void **)&m.leaves, m.K > 1 ? G * m.K * sizeof(LeafRec) : 0},
         {(void **)&m.mst, m.K > 1 ? G * 2 * sizeof(int32_t) : 0},
-        {(void **)&c->scratch, 9 * sizeof(uint64_t)},
+        {(void **)&c->scratch, (TC_COUNT + 1) * sizeof(uint64_t)},
         {(void **)&d.ec.meta, ec_on ? G * (size_t)ec_cap * sizeof(uint32_t) : 0},
         {(void **)&d.ec.key, ec_on ? G * (size_t)ec_cap * 2 * NW * sizeof(uint64_t) : 0},
         {(void **)&d.ec.val, ec_on ? G * (size_t)ec_cap * sizeof(float) : 0},
@@ -1853,27 +1850,21 @@ extern "C" int yy_mcts_get_boards(yy_mcts *c, int8_t *boards, yy_stream_t s) {
 
 extern "C" int yy_mcts_status(yy_mcts *c, int32_t *n_overflow, uint64_t *counters) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(c->scratch, 0, 9 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_status, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
-    HIP_TRY(hipGetLastError());
-    uint64_t h[9];
-    HIP_TRY(hipMemcpy(h, c->scratch, sizeof h, hipMemcpyDeviceToHost));
+    uint64_t h[TC_COUNT + 1];
+    if (int e = tree_counters(c, true, h)) return e;
     if (counters) {
-        for (int i = 0; i < 8; i++) counters[i] = h[i];
+        for (int i = TC_EVALS; i < TC_FORCED; i++) counters[i] = h[i];
     }
-    if (n_overflow) *n_overflow = (int32_t)h[8];
-    if (h[8]) return set_err(YY_E_ARENA, "tree arena overflow or non-finite evaluator output in at least one game since the last status call%s%s");
+    if (n_overflow) *n_overflow = (int32_t)h[TC_COUNT];
+    if (h[TC_COUNT]) return set_err(YY_E_ARENA, "tree arena overflow or non-finite evaluator output in at least one game since the last status call%s%s");
     return YY_OK;
 }
 
 extern "C" int yy_mcts_forced_descents(yy_mcts *c, uint64_t *out) {
     if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(c->scratch, 0, sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_forced_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, c->scratch, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t h[TC_COUNT + 1];
+    if (int e = tree_counters(c, false, h)) return e;
+    *out = h[TC_FORCED];
     return YY_OK;
 }
 
@@ -1888,11 +1879,9 @@ extern "C" int yy_mcts_root_proven(yy_mcts *c, int8_t *root, int8_t *child, yy_s
 extern "C" int yy_mcts_solver_counters(yy_mcts *c, uint64_t *out) {
     if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
     if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_solver_counters with a select or a root expansion pending%s%s");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(c->scratch, 0, 3 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_solver_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, c->scratch, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t h[TC_COUNT + 1];
+    if (int e = tree_counters(c, false, h)) return e;
+    for (int i = TC_SV_NODES; i < TC_COUNT; i++) out[i - TC_SV_NODES] = h[i];
     return YY_OK;
 }
 
@@ -1977,27 +1966,17 @@ extern "C" int yy_mcts_set_shared_evaluations_replacing(yy_mcts *c, uint64_t *cl
     return YY_OK;
 }
 
-__global__ void k_shared_sum(MctsDev d, uint64_t *out) {
-    uint64_t acc[4] = {0, 0, 0, 0};
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.G; g += gridDim.x * blockDim.x)
-        for (int i = 0; i < 4; i++) acc[i] += d.state[g].shc[i];
-    for (int i = 0; i < 4; i++)
-        if (acc[i]) atomicAdd((unsigned long long *)&out[i], (unsigned long long)acc[i]);
-}
-
-// hits, inserts, dropped, duplicates summed over the games into c->scratch[0 .. 3]
-static int shared_sum(yy_mcts *c) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(c->scratch, 0, 4 * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_shared_sum, dim3(64), dim3(256), 0, 0, c->dev, c->scratch);
-    HIP_TRY(hipGetLastError());
+// hits, inserts, dropped (, duplicates): out[0 .. n)
+static int shared_counters(yy_mcts *c, uint64_t *out, int n) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    uint64_t h[TC_COUNT + 1];
+    if (int e = tree_counters(c, false, h)) return e;
+    for (int i = 0; i < n; i++) out[i] = h[TC_SH_HITS + i];
     return YY_OK;
 }
 
 extern "C" int yy_mcts_shared_counters_ex(yy_mcts *c, uint64_t *out) {
-    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
-    if (int e = shared_sum(c)) return e;
-    HIP_TRY(hipMemcpy(out, c->scratch, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (int e = shared_counters(c, out, 4)) return e;
     out[4] = out[5] = 0;
     if (c->dev.sh_sweep) {
         uint64_t sw[SH_SWEEP_WORDS];
@@ -2008,12 +1987,7 @@ extern "C" int yy_mcts_shared_counters_ex(yy_mcts *c, uint64_t *out) {
     return YY_OK;
 }
 
-extern "C" int yy_mcts_shared_counters(yy_mcts *c, uint64_t *out) {
-    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
-    if (int e = shared_sum(c)) return e;
-    HIP_TRY(hipMemcpy(out, c->scratch, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return YY_OK;
-}
+extern "C" int yy_mcts_shared_counters(yy_mcts *c, uint64_t *out) { return shared_counters(c, out, 3); }
 
 extern "C" int yy_mcts_shared_evaluations_clear(yy_mcts *c, yy_stream_t s) {
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");

@@ -4,6 +4,7 @@
 // (k_begin), the root distribution (k_root_policy), getNextState (k_step) and getGameEnded (k_game_ended).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/yy_engine.h"
@@ -213,6 +214,28 @@ struct LeafRec {
     uint64_t mask[YY_MAX_NW];
 };
 
+// GameState.ctr: what a game counts since create / yy_mcts_reset_counters (lane 0 counts).  In the order of the readers' outputs:
+// yy_mcts_status, yy_mcts_forced_descents, yy_mcts_shared_counters(_ex), yy_mcts_solver_counters
+enum {
+    TC_EVALS,           // evaluator rows requested
+    TC_LEVELS,          // selection levels walked
+    TC_SCANNED,         // children scanned during selection
+    TC_CREATED,         // children (edges) created
+    TC_TERMINAL,        // descents that ended on a terminal node already in the tree
+    TC_NODES,           // nodes created
+    TC_REUSED,          // pass values taken from the node record (YY_FLAG_REUSE_PASS_VALUE)
+    TC_TABLE_HITS,      // leaves served by a position table: the game's cache, the book or the shared table
+    TC_FORCED,          // forced playouts: root descents that took a forced edge
+    TC_SH_HITS,         // shared evaluation table: leaves it served
+    TC_SH_INSERTS,      //   rows inserted
+    TC_SH_DROPPED,      //   inserts dropped (probe window full)
+    TC_SH_DUPLICATES,   //   replacing mode: inserts that met their position claimed in the same launch
+    TC_SV_NODES,        // solver (YY_FLAG_SOLVER): nodes proven by propagation
+    TC_SV_DESCENTS,     //   descents ended on a proven node below the root
+    TC_SV_ROOTS,        //   searches whose root became proven
+    TC_COUNT
+};
+
 struct GameState {
     int32_t n_nodes, n_edges;
     int32_t root_N;
@@ -231,13 +254,14 @@ struct GameState {
     int32_t root_stones;    // stones on the root board: a cached position with no more stones cannot be a leaf again
     int32_t budget;         // K = 1: simulations of this game's current search (root_setup); at root_N == budget selection stops
     LeafRec leaf;           // K = 1: the pending leaf
-    uint64_t ctr[8];        // evals, levels, children scanned, children created, terminal revisits, nodes, reused pass values, position-table hits
-    uint64_t forced;        // forced playouts: root descents that took a forced edge, since create / yy_mcts_reset_counters
-    uint64_t shc[4];        // shared evaluation table: leaves it served, rows inserted, inserts dropped (probe window full),
-                            // replacing mode: inserts that met their position claimed in the same launch (duplicates)
-    uint64_t sv[3];         // solver (YY_FLAG_SOLVER): nodes proven by propagation, descents ended on a proven node below the
-                            // root, searches whose root became proven
+    uint64_t ctr[TC_COUNT]; // the TC_* counters
 };
+static_assert(sizeof(GameState) == 280, "GameState changed size");
+static_assert(offsetof(GameState, ctr) == 152, "GameState.ctr moved");
+
+// A game stops searching (arena overflow, non-finite evaluator output, no selectable child); called by lane 0.  err_ever
+// survives yy_mcts_begin and is cleared only by yy_mcts_status.
+__device__ __forceinline__ void fail_game(GameState *st) { st->err = st->err_ever = 1; }
 
 // A table of evaluated positions: open addressing on bb_hash, keys compared in full.  The shared book is one such table,
 // game g's evaluation cache another (cache_of: a slice of the context's ec arrays).
@@ -324,7 +348,7 @@ struct yy_mcts {
     MultiDev multi;
     int32_t target_sims;    // simulations of the next searches (K > 1: sets the descents of the last step on the device)
     const int32_t *budgets; // device int32 [G] of per-game simulation budgets for the next yy_mcts_begin; nullptr: target_sims for all
-    uint64_t *scratch;      // [8] counters + overflow count
+    uint64_t *scratch;      // [TC_COUNT + 1]: the counters summed over the games, then the failed games (tree_counters)
     int32_t *remap;         // [G][node_cap] old node index -> new one (k_advance); allocated by the first yy_mcts_advance
     uint64_t bytes;
     int pending;            // 1 = a select is pending an expand_backup

@@ -854,12 +854,16 @@ class BatchedMCTS:
             check(lib().yy_mcts_root_policy(self._h, int(bool(temperature_zero)), _p(pi), _stream()))
         return pi
 
+    def _read(self, fn, names, *extra):
+        """One counter reader of the C ABI, fn(ctx, *extra, out uint64 [len(names)]), as {name: int}."""
+        ctr = (ct.c_uint64 * len(names))()
+        with torch.cuda.device(self.device):
+            check(fn(self._h, *extra, ctr))
+        return dict(zip(names, [int(x) for x in ctr]))
+
     def forced_descents(self):
         """sync; forced_playouts: the root descents, over all games, that took a forced edge since create / reset_counters()."""
-        n = ct.c_uint64(0)
-        with torch.cuda.device(self.device):
-            check(lib().yy_mcts_forced_descents(self._h, ct.byref(n)))
-        return int(n.value)
+        return self._read(lib().yy_mcts_forced_descents, ("forced",))["forced"]
 
     PROVEN = ("none", "win", "loss", "draw")     # the codes of root_proven(), each for the side to move at that node
     SOLVER_COUNTERS = ("proven_nodes", "proven_descents", "proven_roots")
@@ -878,10 +882,7 @@ class BatchedMCTS:
         """sync; solver: {proven_nodes: nodes proven by propagation, proven_descents: descents that ended on a proven node below
         the root, proven_roots: searches whose root became proven} over all games since create / reset_counters().  After a
         finished search (YYError with a select pending)."""
-        ctr = (ct.c_uint64 * 3)()
-        with torch.cuda.device(self.device):
-            check(lib().yy_mcts_solver_counters(self._h, ctr))
-        return dict(zip(self.SOLVER_COUNTERS, [int(x) for x in ctr[:3]]))
+        return self._read(lib().yy_mcts_solver_counters, self.SOLVER_COUNTERS)
 
     def root_stats(self):
         visits = torch.empty(self.G, dtype=torch.int32, device=self.device)
@@ -898,11 +899,7 @@ class BatchedMCTS:
 
     def status(self):
         """sync; raises YYError(YY_E_ARENA) when a game's arena overflowed; returns the counters."""
-        n = ct.c_int32(0)
-        ctr = (ct.c_uint64 * 8)()
-        with torch.cuda.device(self.device):
-            check(lib().yy_mcts_status(self._h, ct.byref(n), ctr))
-        return dict(zip(self.COUNTERS, [int(x) for x in ctr[:8]]))
+        return self._read(lib().yy_mcts_status, self.COUNTERS, None)
 
     def set_book(self, book):
         """Shallow leaves are looked up in `book` (OpeningBook, or None to unset) before the evaluator is asked; the context
@@ -958,18 +955,12 @@ class BatchedMCTS:
 
     def shared_counters(self):
         """sync; shared evaluation table: {hits, inserts, dropped} over all games since create / reset_counters()."""
-        ctr = (ct.c_uint64 * 3)()
-        with torch.cuda.device(self.device):
-            check(lib().yy_mcts_shared_counters(self._h, ctr))
-        return dict(zip(SharedEvaluations.COUNTERS, [int(x) for x in ctr[:3]]))
+        return self._read(lib().yy_mcts_shared_counters, SharedEvaluations.COUNTERS)
 
     def shared_counters_ex(self):
         """sync; shared evaluation table: {hits, inserts, dropped, duplicates, evicted, live}; the last three are 0 for an
         insert-only table."""
-        ctr = (ct.c_uint64 * 6)()
-        with torch.cuda.device(self.device):
-            check(lib().yy_mcts_shared_counters_ex(self._h, ctr))
-        return dict(zip(SharedEvaluations.COUNTERS_EX, [int(x) for x in ctr[:6]]))
+        return self._read(lib().yy_mcts_shared_counters_ex, SharedEvaluations.COUNTERS_EX)
 
     def bind_evaluator(self, evaluator):
         """Evaluations kept across searches (keep_evaluations) and the opening book are results of ONE network: the engine-level

@@ -614,33 +614,24 @@ class _LaneCounters:
             with ln._on_stream():
                 ln.ctx.reset_counters()
 
-    def status(self):
+    def _summed(self, method_name):
         tot = {}
         for ln in self.lanes:
-            for k, v in ln.ctx.status().items():
+            for k, v in getattr(ln.ctx, method_name)().items():
                 tot[k] = tot.get(k, 0) + v
         return tot
+
+    def status(self):
+        return self._summed("status")
 
     def shared_counters(self):
-        tot = {}
-        for ln in self.lanes:
-            for k, v in ln.ctx.shared_counters().items():
-                tot[k] = tot.get(k, 0) + v
-        return tot
+        return self._summed("shared_counters")
 
     def shared_counters_ex(self):
-        tot = {}
-        for ln in self.lanes:
-            for k, v in ln.ctx.shared_counters_ex().items():
-                tot[k] = tot.get(k, 0) + v
-        return tot
+        return self._summed("shared_counters_ex")
 
     def solver_counters(self):
-        tot = {}
-        for ln in self.lanes:
-            for k, v in ln.ctx.solver_counters().items():
-                tot[k] = tot.get(k, 0) + v
-        return tot
+        return self._summed("solver_counters")
 
 
 class SelfPlayLanes:
