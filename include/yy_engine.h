@@ -148,6 +148,39 @@ extern "C" {
                               the node records.  Flag clear: no node ever carries a status and every kernel does what it did
                               without it. */
 
+#define YY_FLAG_GUMBEL_ROOT 512u /* Gumbel root search (Danihelka et al., "Policy improvement by planning with Gumbel", ICLR
+                              2022; not in the reference): Gumbel noise, sequential halving and a completed-Q policy target at
+                              the ROOT of every search; below the root the descent is untouched.  m = yy_mcts_config.gumbel_root
+                              in 2 .. 64, c_visit = gumbel_c_visit finite and >= 0, c_scale = gumbel_c_scale finite and > 0 (else
+                              YY_E_INVALID; the paper's board-game values: 16, 50, 1), fixed at creation.  Copied boards and
+                              leaves_per_step <= 1 only, and not with YY_FLAG_FORCED_PLAYOUTS or YY_FLAG_SOLVER: create returns
+                              YY_E_UNSUPPORTED; yy_mcts_advance returns YY_E_UNSUPPORTED on such a context (each a follow-up).
+                              Base score: the root expansion needs the Gumbel rows of yy_mcts_set_gumbel (YY_E_STATE without)
+                              and writes, for root edge j of action a and stored prior P (the noised one at a noised root;
+                              eps = 0 is recommended), s0[j] = f32(f64(g[a]) + log(f64(P))); P == 0 gives -inf.
+                              Budget: n = the game's simulation budget -- its entry of yy_mcts_set_sim_budgets, else the scalar
+                              of yy_mcts_set_num_sims, which a context with the flag stores at K = 1 as well.
+                              Considered visits: with k root children and m' = min(m, k), seq(m', n) is 0, 1, .. n-1 for
+                              m' <= 1; else, with L = ceil(log2 m'), c = m' and v = 0: phases of extra = max(1, n / (L*c))
+                              (integer division) rounds, round r of a phase being c entries of value v + r; after a phase
+                              v += extra, c = max(2, c / 2); cut after n entries (mctx's table).
+                              Selection at depth 0 of a descent, S the sum of the root children's visits and v = seq[S]:
+                              among the children with N == v (all children when there is none) the largest
+                              f32(s0 + sigma), the lowest edge (= lowest action) on ties, -inf ties included;
+                              sigma = f32(f32(f32(c_visit + f32(maxN)) * c_scale) * q), maxN the largest child visit count,
+                              q = f32(W / f32(N)) for N > 0, else 0, W the edge's value sum as PUCT reads it.  So the first m'
+                              root descents expand the m' children of largest g + log P; no candidate set is stored.
+                              Policy target: yy_mcts_root_policy (both temperatures) and the example record of
+                              yy_mcts_step_selfplay return pi' = softmax(log f64(P) + sigma64(cq)) over the root's edges in
+                              float64, sigma64(x) = (f64(c_visit) + f64(maxN)) * f64(c_scale) * x, cq = f64(W) / f64(N) of a
+                              visited child, and for an unvisited one SW / SN over the visited children, SW = f64(sum of
+                              (int64)(f64(W) * 2^32)) * 2^-32 (each term truncated toward zero: no order dependence), 0 when
+                              none is visited.  The paper's v_mix needs the root's own network value, which the tree does not
+                              keep: a follow-up.  A root without children keeps the uniform row.  yy_mcts_root_counts stays raw.
+                              The move: yy_mcts_root_gumbel_action -- among the children with the largest visit count the
+                              largest f32(s0 + sigma), the lowest edge on ties -- which yy_mcts_step_selfplay plays at every ply
+                              (no temperature rule, no move draw).  Flag clear: every kernel does what it did without it. */
+
 typedef void *yy_stream_t;
 
 const char *yy_last_error(void);
@@ -219,6 +252,9 @@ typedef struct yy_mcts_config {
     double forced_playouts;    /* YY_FLAG_FORCED_PLAYOUTS: k (KataGo: 2.0); ignored without the flag */
     float fpu_reduction;       /* YY_FLAG_FPU_REDUCTION: r below the root (KataGo: 0.2); ignored without the flag */
     float fpu_reduction_root;  /* YY_FLAG_FPU_REDUCTION: r at the root (KataGo: 0 at a noised root); ignored without the flag */
+    int32_t gumbel_root;       /* YY_FLAG_GUMBEL_ROOT: m, the root actions sequential halving starts from (2 .. 64; the paper: 16) */
+    float gumbel_c_visit;      /* YY_FLAG_GUMBEL_ROOT: c_visit of sigma (the paper: 50); ignored without the flag */
+    float gumbel_c_scale;      /* YY_FLAG_GUMBEL_ROOT: c_scale of sigma (the paper: 1.0); ignored without the flag */
 } yy_mcts_config;
 
 /* Leaf-parallel steps (leaves_per_step = K > 1).  Every select (or step) runs, per game, descents j = 0 .. K_eff-1 one after
@@ -341,6 +377,16 @@ int yy_mcts_forced_descents(yy_mcts *ctx, uint64_t *out);
  * YY_E_STATE with a select or a root expansion pending. */
 int yy_mcts_root_proven(yy_mcts *ctx, int8_t *root, int8_t *child, yy_stream_t stream);
 int yy_mcts_solver_counters(yy_mcts *ctx, uint64_t *out);
+/* YY_FLAG_GUMBEL_ROOT (YY_E_UNSUPPORTED without the flag).  yy_mcts_set_gumbel: rows_dev = DEVICE float32 [G,A], the Gumbel
+ * variable of every action at every game's root (yy_selfplay_root_gumbel draws them), owned by the caller.  Host only, like
+ * yy_mcts_set_sim_budgets: it stores the pointer, which the root expansions read on their stream, so the array must stay
+ * valid and in place, and be set before the first step is captured; the caller rewrites its contents before every search.
+ * yy_selfplay_run_create points the context at the run's own rows.  yy_mcts_root_gumbel: out float32 [G,A] = s0 by action, NaN
+ * for an action without a root edge and for an inactive game.  yy_mcts_root_gumbel_action: out int32 [G] = the Gumbel winner
+ * (above), -1 for an inactive game and for a root without children. */
+int yy_mcts_set_gumbel(yy_mcts *ctx, const float *rows_dev);
+int yy_mcts_root_gumbel(yy_mcts *ctx, float *out, yy_stream_t stream);
+int yy_mcts_root_gumbel_action(yy_mcts *ctx, int32_t *out, yy_stream_t stream);
 /* Shared book of pre-evaluated positions.  Every self-play game starts from the empty board, so the searches of the first plies
  * of ALL games walk the same few hundred thousand positions (8x8: 770 232 positions with <= 8 stones are reachable).  The
  * caller enumerates them, evaluates them once in large batches with the SAME evaluator the searches use, and hands the table
@@ -533,6 +579,12 @@ int yy_compact_rows(const uint8_t *flags, int G, int32_t *rows, int32_t *n, yy_s
  * draw[g] != 0: noise float64 [G,A], zero rows elsewhere (yy_mcts_expand_root treats an all-zero row as "no noise"). */
 int yy_selfplay_root_noise(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *draw,
                            const uint8_t *mask, int G, int A, double alpha, double *noise, yy_stream_t stream);
+
+/* yy_selfplay_root_gumbel: Gumbel root search (YY_FLAG_GUMBEL_ROOT).  rows float32 [G,A]: rows[g,a] = f32(-log(-log(u))) in
+ * float64, u the 53-bit uniform of the first two words of the block keyed (seed, game_id[g], ply[g], purpose 4, element a),
+ * strictly inside (0, 1): u == 0 is replaced by 2^-54.  Every game and every action is drawn; what yy_mcts_set_gumbel takes. */
+int yy_selfplay_root_gumbel(uint64_t seed, const int64_t *game_id, const int32_t *ply, int G, int A, float *rows,
+                            yy_stream_t stream);
 
 /* yy_selfplay_sample_actions: the move choice of SelfPlayWorker.play_game (ai/self_play.py:143-160) for the games with
  * searching[g] != 0 (action -1 otherwise): ply < temperature_threshold -> sample from pi * mask renormalised (uniform over

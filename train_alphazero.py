@@ -121,6 +121,16 @@ def parse_args(argv=None):
                         "terminal positions are propagated up the tree, a descent stops at a proven node below the root without "
                         "asking the network, and the arena plays a proven winning move when the root has one (default off; changes "
                         "which moves are picked; not with --leaves-per-step > 1, --board-semantics aliased or --reference-quirks)")
+    p.add_argument("--gumbel-root", type=int, default=None, metavar="M",
+                   help="self-play and train: Gumbel root search -- every root draws Gumbel noise, spends its simulations by "
+                        "sequential halving over its M best actions, records the completed-Q policy target and plays the "
+                        "Gumbel winner at every ply (2 .. 64; the paper: 16; default off; changes which moves are picked; "
+                        "not with --leaves-per-step > 1, --board-semantics aliased, --reference-quirks, --forced-playouts, "
+                        "--tree-reuse or --solver)")
+    p.add_argument("--gumbel-c-visit", type=float, default=None, metavar="X",
+                   help="c_visit of --gumbel-root's sigma (default 50)")
+    p.add_argument("--gumbel-c-scale", type=float, default=None, metavar="Y",
+                   help="c_scale of --gumbel-root's sigma (default 1.0)")
     return p.parse_args(argv)
 
 
@@ -129,7 +139,7 @@ def parse_args(argv=None):
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
            "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
-           "shared_evaluations_replace", "solver")
+           "shared_evaluations_replace", "solver", "gumbel_root", "gumbel_c_visit", "gumbel_c_scale")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root", "solver")]}
@@ -198,7 +208,8 @@ def main(argv=None):
                            evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
                            forced_playouts=args.forced_playouts, fpu_reduction=args.fpu_reduction,
                            fpu_reduction_root=args.fpu_reduction_root, shared_evaluations=args.shared_evaluations,
-                           shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver)
+                           shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver,
+                           gumbel_root=args.gumbel_root, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -233,7 +244,9 @@ def main(argv=None):
                                        symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts,
                                        fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
                                        shared_evaluations=args.shared_evaluations,
-                                       shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver)
+                                       shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver,
+                                       gumbel_root=args.gumbel_root, gumbel_c_visit=args.gumbel_c_visit,
+                                       gumbel_c_scale=args.gumbel_c_scale)
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

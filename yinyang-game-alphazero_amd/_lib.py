@@ -20,6 +20,7 @@ FLAG_EVAL_SYMMETRY = 32
 FLAG_FORCED_PLAYOUTS = 64
 FLAG_FPU_REDUCTION = 128
 FLAG_SOLVER = 256
+FLAG_GUMBEL_ROOT = 512
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -35,7 +36,8 @@ class MctsConfig(C.Structure):
     _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_sims", C.c_int32),
                 ("cpuct", C.c_float), ("flags", C.c_uint32), ("edges_per_game", C.c_int64),
                 ("nodes_per_game", C.c_int64), ("leaves_per_step", C.c_int32), ("symmetry_seed", C.c_uint64),
-                ("forced_playouts", C.c_double), ("fpu_reduction", C.c_float), ("fpu_reduction_root", C.c_float)]
+                ("forced_playouts", C.c_double), ("fpu_reduction", C.c_float), ("fpu_reduction_root", C.c_float),
+                ("gumbel_root", C.c_int32), ("gumbel_c_visit", C.c_float), ("gumbel_c_scale", C.c_float)]
 
 
 class SelfPlayConfig(C.Structure):
@@ -100,6 +102,9 @@ _SIGS = {
     "yy_mcts_forced_descents": [_vp, C.POINTER(C.c_uint64)],
     "yy_mcts_root_proven": [_vp, _vp, _vp, _vp],
     "yy_mcts_solver_counters": [_vp, C.POINTER(C.c_uint64)],
+    "yy_mcts_set_gumbel": [_vp, _vp],
+    "yy_mcts_root_gumbel": [_vp, _vp, _vp],
+    "yy_mcts_root_gumbel_action": [_vp, _vp, _vp],
     "yy_mcts_cache_clear": [_vp, _vp],
     "yy_book_insert": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, _vp],
     "yy_mcts_set_book": [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int],
@@ -124,6 +129,7 @@ _SIGS = {
                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_nn_fc_heads_f16x3": [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "yy_selfplay_root_noise": [C.c_uint64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp],
+    "yy_selfplay_root_gumbel": [C.c_uint64, _vp, _vp, C.c_int, C.c_int, _vp, _vp],
     "yy_selfplay_sample_actions": [C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "yy_selfplay_draw_budgets": [C.c_uint64, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp],
     "yy_selfplay_run_create": [_vp, C.POINTER(SelfPlayConfig), C.POINTER(_vp)],

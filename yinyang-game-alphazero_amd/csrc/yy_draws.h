@@ -173,6 +173,17 @@ __device__ __forceinline__ bool draw_full_search(uint64_t seed, int64_t gid, int
     return u01(r.x, r.y) < p_full;
 }
 
+// Gumbel root search (YY_FLAG_GUMBEL_ROOT): the Gumbel(0, 1) variable of action a at the root of (game, ply), purpose 4 (0 .. 3
+// are the streams above): g = f32(-log(-log(u))) in float64, u the 53-bit uniform of the block's first two words, strictly
+// inside (0, 1) -- the one value u01 can give outside it, 0, is replaced by 2^-54.
+#define YY_DRAW_GUMBEL 4
+__device__ __forceinline__ float gumbel_draw(uint64_t seed, int64_t gid, int ply, int a) {
+    const U4 r = draw(seed, gid, ply, YY_DRAW_GUMBEL, (uint32_t)a);
+    double u = u01(r.x, r.y);
+    if (u == 0.0) u = 0x1.0p-54;
+    return (float)(-log(-log(u)));
+}
+
 // symmetry-randomised evaluation: the symmetry a POSITION is evaluated under, a pure function of (seed, black, white) -- not
 // of game, ply, slot or batch.  The four counter words of every block are taken by the position, so the domain tag sits in the
 // key: seed ^ SYM_TAG, where every other stream keys with the seed itself.  The NW word pairs are chained: block i has the

@@ -32,7 +32,7 @@
 #include "yy_common.h"
 #include "yy_tree.h"
 
-#define YY_VERSION 110
+#define YY_VERSION 111
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -945,6 +945,29 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             const uint4 e = edges[first + best];
             w = rfl(e.w);
             s_carry = (int)rfl(e.y) - 1;
+        } else if (depth == 0 && d.gumbel) {
+            // Gumbel root search: sequential halving as a pure function of the root's edges and S (include/yy_engine.h).  The
+            // child to visit is, among those with N == seq(min(m, k), budget)[S] (all when there is none), the one of the
+            // largest g + log P + sigma(q), the lowest edge on ties.  Wave-uniform branch, like the forced-playouts one
+            uint32_t mxn = 0;
+            for (int j = lane; j < k; j += 64) mxn = umax32(mxn, edges[first + j].y);
+            const int maxN = (int)wave_umax(mxn);
+            const int v = gumbel_seq_at(min((int)d.gumbel, k), rfl(s_budget), S);
+            const float *s0 = d.g_s0 + (size_t)g * d.geo.A;
+            uint32_t ck = 0, cw = 0, cn = 0, ak = 0, aw = 0, an = 0;              // best of the considered children / of all
+            int ci = BEST_NONE, ai = BEST_NONE;
+            for (int j = lane; j < k; j += 64) {
+                const uint4 e = edges[first + j];
+                const uint32_t key = gumbel_key(d, s0[j], maxN, (int)e.y, __uint_as_float(e.z));
+                if (key > ak) { ak = key; ai = j; aw = e.w; an = e.y; }
+                if ((int)e.y == v && key > ck) { ck = key; ci = j; cw = e.w; cn = e.y; }
+            }
+            const bool considered = __ballot(ci != BEST_NONE) != 0;
+            const uint32_t bw = considered ? cw : aw, bn = considered ? cn : an;
+            best = best_child(considered ? ck : ak, considered ? ci : ai, k);
+            if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) fail_game(st); break; }  // every score NaN
+            w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
+            s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
         } else {
             const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
             // first-play urgency: one more pass over the node's edges for the sums behind the q of its unvisited children
@@ -1139,6 +1162,18 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
         if (d.ec.meta && src == SRC_NONE && !root) cache_store<NW>(d, st, g, policy, v);
         if (d.sh.meta && src == SRC_NONE && !root) shared_store<NW>(d, st, g, policy, v, stamp);
         exact = d.solver && kind == K_EXPAND && rfl((int)st->leaf.terminal) != 0;   // the new node is a terminal one
+        if (root && d.gumbel) {                                                     // wave-uniform
+            // Gumbel root search: the base score of every root edge, from its STORED prior (the noised one at a noised root)
+            __syncthreads();                                                        // the edges other lanes wrote in expand_leaf
+            const uint4 hdr = nodes[0];
+            const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+            const float *grow = d.g_rows + (size_t)g * d.geo.A;
+            float *s0 = d.g_s0 + (size_t)g * d.geo.A;
+            for (int j = lane; j < k; j += 64) {
+                const uint4 e = edges[first + j];
+                s0[j] = (float)__dadd_rn((double)grow[e.w >> 24], log((double)__uint_as_float(e.x)));
+            }
+        }
     }
     if (lane == 0) st->leaf.kind = K_NONE;
     if (kind == K_ROOTINIT) return;                                                 // no backup
@@ -1583,6 +1618,22 @@ template <int NW> __global__ void __launch_bounds__(64) k_root_proven(MctsDev d,
     }
 }
 
+// Gumbel root search: s0 by action f32 [G,A] (NaN: no such root edge, an inactive game) / the Gumbel winner int32 [G]
+template <int NW> __global__ void __launch_bounds__(64) k_root_gumbel_scores(MctsDev d, float *out) {
+    const int g = blockIdx.x, A = d.geo.A;
+    const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
+    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+    for (int a = lane_id(); a < A; a += 64) out[(size_t)g * A + a] = __uint_as_float(0x7FC00000u);
+    __syncthreads();
+    if (rfl((int)d.state[g].active) == 0) return;
+    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    for (int j = lane_id(); j < k; j += 64) out[(size_t)g * A + (int)(edges[first + j].w >> 24)] = d.g_s0[(size_t)g * A + j];
+}
+template <int NW> __global__ void __launch_bounds__(64) k_root_gumbel_action(MctsDev d, int32_t *out) {
+    const int a = gumbel_winner<NW>(d, blockIdx.x);
+    if (lane_id() == 0) out[blockIdx.x] = a;
+}
+
 // ---------------------------------------------------------------------------------- host API
 extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     if (!cfg || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
@@ -1612,6 +1663,20 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         if (cfg->leaves_per_step > 1)
             return set_err(YY_E_UNSUPPORTED, "YY_FLAG_SOLVER: leaves_per_step > 1 is not supported (proofs under virtual visits are a follow-up)%s%s");
     }
+    if (cfg->flags & YY_FLAG_GUMBEL_ROOT) {
+        if (cfg->flags & YY_FLAG_ALIASED)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_GUMBEL_ROOT needs copied boards (YY_FLAG_ALIASED reproduces the reference, which has no such option)%s%s");
+        if (cfg->leaves_per_step > 1)
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_GUMBEL_ROOT: leaves_per_step > 1 is not supported (sequential halving is part of the one-descent selection)%s%s");
+        if (cfg->flags & (YY_FLAG_FORCED_PLAYOUTS | YY_FLAG_SOLVER))
+            return set_err(YY_E_UNSUPPORTED, "YY_FLAG_GUMBEL_ROOT does not go with YY_FLAG_FORCED_PLAYOUTS or YY_FLAG_SOLVER (each plans the root's visits itself)%s%s");
+        if (cfg->gumbel_root < 2 || cfg->gumbel_root > 64)
+            return set_err(YY_E_INVALID, "YY_FLAG_GUMBEL_ROOT: gumbel_root outside 2 .. 64%s%s");
+        if (!(cfg->gumbel_c_visit >= 0.0f && cfg->gumbel_c_visit < INFINITY))
+            return set_err(YY_E_INVALID, "YY_FLAG_GUMBEL_ROOT: gumbel_c_visit must be finite and >= 0%s%s");
+        if (!(cfg->gumbel_c_scale > 0.0f && cfg->gumbel_c_scale < INFINITY))
+            return set_err(YY_E_INVALID, "YY_FLAG_GUMBEL_ROOT: gumbel_c_scale must be positive and finite%s%s");
+    }
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
     if (cfg->leaves_per_step > 1) {
@@ -1638,6 +1703,9 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.fpu = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction : 0.0f;
     d.fpu_root = (cfg->flags & YY_FLAG_FPU_REDUCTION) ? cfg->fpu_reduction_root : 0.0f;
     d.solver = (cfg->flags & YY_FLAG_SOLVER) ? 1u : 0u;
+    d.gumbel = (cfg->flags & YY_FLAG_GUMBEL_ROOT) ? (uint32_t)cfg->gumbel_root : 0u;
+    d.g_cvisit = d.gumbel ? cfg->gumbel_c_visit : 0.0f;
+    d.g_cscale = d.gumbel ? cfg->gumbel_c_scale : 0.0f;
     m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
@@ -1672,6 +1740,7 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         {(void **)&d.ec.key, ec_on ? G * (size_t)ec_cap * 2 * NW * sizeof(uint64_t) : 0},
         {(void **)&d.ec.val, ec_on ? G * (size_t)ec_cap * sizeof(float) : 0},
         {(void **)&d.ec.pol, ec_on ? G * (size_t)ec_cap * A * sizeof(float) : 0},
+        {(void **)&d.g_s0, d.gumbel ? G * A * sizeof(float) : 0},
     };
     for (auto &a : allocs) {
         if (a.n == 0) continue;
@@ -1693,6 +1762,7 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     if (e == hipSuccess) e = hipMemset(d.nodes, 0, G * d.node_cap * sizeof(uint4));
     if (e == hipSuccess && d.ec.meta) e = hipMemset(d.ec.meta, 0, G * (size_t)ec_cap * sizeof(uint32_t));
     if (e == hipSuccess && m.mst) e = hipMemset(m.mst, 0, G * 2 * sizeof(int32_t));
+    if (e == hipSuccess && d.g_s0) e = hipMemset(d.g_s0, 0, G * A * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(d.sqrt_tab, tab, (size_t)d.sqrt_n * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     delete[] tab;
@@ -1705,7 +1775,7 @@ extern "C" int yy_mcts_destroy(yy_mcts *c) {
     if (!c) return YY_OK;
     const MctsDev &d = c->dev;
     void *ps[] = {d.edges, d.nodes, d.nboard, d.gboard, d.path, d.state, d.sqrt_tab, c->scratch, d.ec.meta, d.ec.key, d.ec.val, d.ec.pol,
-                  c->multi.leaves, c->multi.mst, c->remap};
+                  c->multi.leaves, c->multi.mst, c->remap, d.g_s0};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     delete c;
@@ -1725,6 +1795,29 @@ extern "C" int yy_mcts_set_sim_budgets(yy_mcts *c, const int32_t *budgets_dev) {
     return YY_OK;
 }
 
+extern "C" int yy_mcts_set_gumbel(yy_mcts *c, const float *rows_dev) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (!c->dev.gumbel) return set_err(YY_E_UNSUPPORTED, "yy_mcts_set_gumbel: the context was created without YY_FLAG_GUMBEL_ROOT%s%s");
+    c->dev.g_rows = rows_dev;
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_root_gumbel(yy_mcts *c, float *out, yy_stream_t s) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (!c->dev.gumbel) return set_err(YY_E_UNSUPPORTED, "yy_mcts_root_gumbel: the context was created without YY_FLAG_GUMBEL_ROOT%s%s");
+    DISPATCH_NW(c->dev.geo.NW, k_root_gumbel_scores<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, out));
+    HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
+extern "C" int yy_mcts_root_gumbel_action(yy_mcts *c, int32_t *out, yy_stream_t s) {
+    if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (!c->dev.gumbel) return set_err(YY_E_UNSUPPORTED, "yy_mcts_root_gumbel_action: the context was created without YY_FLAG_GUMBEL_ROOT%s%s");
+    DISPATCH_NW(c->dev.geo.NW, k_root_gumbel_action<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, out));
+    HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
 extern "C" int yy_mcts_memory_bytes(const yy_mcts *c, uint64_t *out) {
     if (!c || !out) return set_err(YY_E_INVALID, "null pointer%s%s");
     *out = c->bytes;
@@ -1735,7 +1828,8 @@ extern "C" int yy_mcts_begin(yy_mcts *c, const int8_t *boards, const int8_t *pla
                              float *planes, yy_stream_t s) {
     if (!c || !boards || !players || !planes) return set_err(YY_E_INVALID, "null pointer%s%s");
     DISPATCH_NW(c->dev.geo.NW, k_begin<NW><<<dim3(c->cfg.G), dim3(64), 0, (hipStream_t)s>>>(c->dev, c->multi,
-                                                   c->multi.K > 1 ? c->target_sims : 0x7FFFFFFF, c->target_sims, c->budgets, c->cfg.max_sims,
+                                                   // Gumbel root search plans the budget: the real count, not "no limit"
+                                                   (c->multi.K > 1 || c->dev.gumbel) ? c->target_sims : 0x7FFFFFFF, c->target_sims, c->budgets, c->cfg.max_sims,
                                                    boards, players, active, planes));
     HIP_TRY(hipGetLastError());
     c->pending = 2;  // root expansion pending
@@ -1747,6 +1841,8 @@ extern "C" int yy_mcts_advance(yy_mcts *c, const int32_t *actions, int32_t *kept
     if (c->cfg.flags & YY_FLAG_ALIASED)
         return set_err(YY_E_UNSUPPORTED, "yy_mcts_advance needs copied boards: with the aliased board a node's position changes between visits%s%s");
     if (c->multi.K > 1) return set_err(YY_E_UNSUPPORTED, "yy_mcts_advance: leaves_per_step > 1 does not support tree reuse%s%s");
+    if (c->dev.gumbel)
+        return set_err(YY_E_UNSUPPORTED, "yy_mcts_advance: YY_FLAG_GUMBEL_ROOT does not support tree reuse (a kept root has no base scores and its visits are not a halving schedule's)%s%s");
     if (c->pending != 0) return set_err(YY_E_STATE, "yy_mcts_advance with a select or a root expansion pending%s%s");
     if (!c->remap) {
         const size_t n = (size_t)c->cfg.G * c->dev.node_cap * sizeof(int32_t);
@@ -1765,6 +1861,8 @@ extern "C" int yy_mcts_advance(yy_mcts *c, const int32_t *actions, int32_t *kept
 
 static int launch_mcts(yy_mcts *c, int backup, int sel, const float *policy, const float *value, const double *noise,
                        double eps, float *planes, uint8_t *needs_eval, yy_stream_t s) {
+    // Gumbel root search: a root expansion reads the Gumbel rows
+    if (backup && c->dev.gumbel && !c->dev.g_rows) return set_err(YY_E_STATE, "YY_FLAG_GUMBEL_ROOT: no Gumbel rows set (yy_mcts_set_gumbel)%s%s");
     // shared evaluation table: every tree-step launch gets a stamp of its own; without the table nothing is launched here
     if (c->dev.sh.meta) {
         hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, (hipStream_t)s, c->dev.sh_stamp);

@@ -16,6 +16,8 @@
 //               pi[a] * mask[a] (ascending a, float64) exceeds u * total (uniform over the legal moves if the total is 0);
 //               temperature 0: the floor(u * n)-th of the n actions tied at max(pi).
 //   purpose 3 = playout cap (not in the reference): ONE uniform u in [0, 1) per (game, ply); u < p_full = a full search.
+//   purpose 4 = Gumbel root search (not in the reference): g(a) = f32(-log(-log(u))) per (game, ply, action a), u a 53-bit
+//               uniform strictly inside (0, 1) (yy_draws.h, gumbel_draw).
 // One game per wavefront; the inverse CDF runs on lane 0 (A <= 192) so that its float64 sums have one fixed order, which the
 // host restatement in tests/ reproduces bit for bit.
 #include <hip/hip_runtime.h>
@@ -80,7 +82,26 @@ __global__ void __launch_bounds__(256) k_draw_budgets(uint64_t seed, const int64
     is_full[g] = full;
 }
 
+// Gumbel root search: rows[g, a] = the Gumbel variable of action a at the root of (game_id[g], ply[g]), for every a < A
+__global__ void __launch_bounds__(64) k_root_gumbel(uint64_t seed, const int64_t *__restrict__ game_id,
+                                                    const int32_t *__restrict__ ply, int A, float *__restrict__ rows) {
+    const int g = blockIdx.x;
+    const int64_t gid = game_id[g];
+    const int p = ply[g];
+    for (int a = threadIdx.x; a < A; a += 64) rows[(size_t)g * A + a] = gumbel_draw(seed, gid, p, a);
+}
+
 }   // namespace sp
+
+extern "C" int yy_selfplay_root_gumbel(uint64_t seed, const int64_t *game_id, const int32_t *ply, int G, int A, float *rows,
+                                       yy_stream_t s) {
+    if (G == 0) return YY_OK;
+    if (!game_id || !ply || !rows || G < 0 || A < 1 || A > 192)
+        return yy_tower_set_err(YY_E_INVALID, "yy_selfplay_root_gumbel: bad argument");
+    sp::k_root_gumbel<<<dim3(G), dim3(64), 0, (hipStream_t)s>>>(seed, game_id, ply, A, rows);
+    if (hipGetLastError() != hipSuccess) return yy_tower_set_err(YY_E_HIP, "yy_selfplay_root_gumbel: launch failed");
+    return YY_OK;
+}
 
 extern "C" int yy_selfplay_root_noise(uint64_t seed, const int64_t *game_id, const int32_t *ply, const uint8_t *draw,
                                       const uint8_t *mask, int G, int A, double alpha, double *noise, yy_stream_t s) {

@@ -46,6 +46,7 @@ struct SpDev {
     int8_t *h_player;                    // [G][T]
     int32_t *h_ply;                      // [G][T]
     double *noise;                       // [G][A] the row k_mcts mixes into a root expansion (all zero: none)
+    float *gumbel;                       // [G][A] Gumbel root search: the row a root expansion takes its base scores from; else nullptr
     unsigned long long *ctr;             // [C_COUNT]
     int64_t *prm;                        // [2] first game index, stride
     // finished examples
@@ -170,6 +171,9 @@ __device__ __forceinline__ void settle(const MctsDev &d, const SpDev &r, const i
         for (int j = 0; j < 3; j++) legal[j] = j < NW && j * 64 + lane < A && ((mask.w[j < NW ? j : 0] >> lane) & 1);
         sp::dirichlet_row(r.seed, gid, ply, ply == 0, legal, A, r.alpha, r.noise + (size_t)g * A);
     }
+    if (r.gumbel) {                                                             // Gumbel root search: k_root_gumbel's row, at every ply
+        for (int a = lane; a < A; a += 64) r.gumbel[(size_t)g * A + a] = sp::gumbel_draw(r.seed, gid, ply, a);
+    }
 }
 
 template <int NW>
@@ -211,9 +215,13 @@ __global__ void __launch_bounds__(64) k_selfplay_move(MctsDev d, SpDev r, float 
         const bool pre = bb_pre2x2(black, white, gb);
         const BB<NW> mask = (player == 1) ? bb_legal(black, white, pre, d.geo, gb) : bb_legal(white, black, pre, d.geo, gb);
         int action = -1;
-        if (lane == 0)
-            action = sp::pick_action(r.seed, gid, ply, r.thr, pi, [&mask](int a) { return bb_test(mask, a); }, A);
-        action = rfl(action);
+        if (d.gumbel) {                                                         // wave-uniform: the Gumbel winner, at every ply
+            action = gumbel_winner<NW>(d, g);
+        } else {
+            if (lane == 0)
+                action = sp::pick_action(r.seed, gid, ply, r.thr, pi, [&mask](int a) { return bb_test(mask, a); }, A);
+            action = rfl(action);
+        }
         bb_play<NW>(d.geo, gb, black, white, player, action);
         player = -player;                                                       // yin_yang_game.py:58, regardless
         ply += 1;
@@ -326,8 +334,10 @@ extern "C" int yy_selfplay_run_create(yy_mcts *c, const yy_selfplay_config *cfg,
         {(void **)&s.ex_z, cap * sizeof(float)},
         {(void **)&s.ex_gid, cap * sizeof(int64_t)},
         {(void **)&s.ex_ply, cap * sizeof(int64_t)},
+        {(void **)&s.gumbel, c->dev.gumbel ? G * A * sizeof(float) : 0},
     };
     for (auto &a : allocs) {
+        if (a.n == 0) continue;
         const hipError_t me = hipMalloc(a.p, a.n);
         if (me != hipSuccess) {
             (void)hipGetLastError();
@@ -343,6 +353,7 @@ extern "C" int yy_selfplay_run_create(yy_mcts *c, const yy_selfplay_config *cfg,
         }
     }
     HIP_TRY(hipDeviceSynchronize());
+    if (s.gumbel) c->dev.g_rows = s.gumbel;   // Gumbel root search: the context's root expansions read the run's rows (yy_mcts_set_gumbel)
     *out = r;
     return YY_OK;
 }

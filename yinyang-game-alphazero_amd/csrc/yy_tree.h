@@ -320,6 +320,13 @@ struct MctsDev {
     // MCTS solver (YY_FLAG_SOLVER): proven statuses are propagated after a descent that ended on an exact value, and a proven
     // node below the root ends a descent; 0: off, no node ever carries a proven flag and every kernel does what it did without it
     uint32_t solver;
+    // Gumbel root search (YY_FLAG_GUMBEL_ROOT): m of yy_mcts_config.gumbel_root; 0: off, every kernel does what it did without
+    // it.  K = 1 and copied boards only (yy_mcts_create).  g_rows: the caller's Gumbel variables f32 [G][A] by action
+    // (yy_mcts_set_gumbel); g_s0: f32 [G][A], the base score g + log P of game g's root edge j at g*A + j (root expansion)
+    uint32_t gumbel;
+    float g_cvisit, g_cscale;
+    const float *g_rows;
+    float *g_s0;
 };
 
 // ---- shared evaluation table, replacing mode: the claim word and the sweep state (yy_engine.hip, yy_shared_table.hip)
@@ -535,14 +542,137 @@ __device__ __forceinline__ void prune_forced(const MctsDev &d, const uint4 *edge
     }
 }
 
+// ------------------------------------------------------------------------------------ Gumbel root search (YY_FLAG_GUMBEL_ROOT)
+// seq(m', n)[S] (include/yy_engine.h): the visit count the root child that descent S of a search of n simulations goes to must
+// have.  Inside a phase the c considered children all hold v visits at its start, so the table is never built: round r of a
+// phase is c entries of v + r.  Wave-uniform scalar work: at most ceil(log2 m') halvings, then phases of n / (2L) rounds.
+__device__ __forceinline__ int gumbel_seq_at(const int mp, const int n, const int S) {
+    if (mp <= 1) return S;
+    const int L = 32 - __clz(mp - 1);   // ceil(log2 m'), m' >= 2
+    int c = mp, v = 0, pos = 0;
+    for (;;) {
+        const int extra = max(1, n / (L * c));
+        if (S < pos + extra * c) return v + (S - pos) / c;
+        pos += extra * c;
+        v += extra;
+        c = max(2, c / 2);
+    }
+}
+// Order-preserving key of f32(s0 + sigma) of a root child with N visits and value sum W, maxN the largest child visit count:
+// sigma = f32(f32(f32(c_visit + maxN) * c_scale) * q), q = f32(W / N) or 0.  + 0.0f as in child_key_at; a NaN score gets key 0
+__device__ __forceinline__ uint32_t gumbel_key(const MctsDev &d, const float s0, const int maxN, const int N, const float W) {
+    const float q = (N > 0) ? __fdiv_rn(W, (float)N) : 0.0f;
+    const float sg = __fmul_rn(__fmul_rn(__fadd_rn(d.g_cvisit, (float)maxN), d.g_cscale), q);
+    const float sc = __fadd_rn(__fadd_rn(s0, sg), 0.0f);
+    return (sc != sc) ? 0u : f32_key(sc);
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t t = (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// The Gumbel winner of game g's root: among the children with the largest visit count the largest f32(s0 + sigma), the lowest
+// edge on ties; its action, or -1 for an inactive game and for a root without children.  Every lane of the wavefront calls it.
+template <int NW> __device__ __forceinline__ int gumbel_winner(const MctsDev &d, const int g) {
+    const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
+    const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
+    if (rfl((int)d.state[g].active) == 0 || k == 0) return -1;
+    const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
+    const float *s0 = d.g_s0 + (size_t)g * d.geo.A;
+    uint4 e[NW];
+    int mx = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int j = i * 64 + lane_id();
+        e[i] = (j < k) ? edges[first + j] : make_uint4(0u, 0u, 0u, 0u);
+        mx = max(mx, (int)e[i].y);
+    }
+    mx = wave_max_i32(mx);
+    uint64_t best = 0;                                                          // key << 32 | ~edge: the largest key, then the lowest edge
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int j = i * 64 + lane_id();
+        if (j < k && (int)e[i].y == mx) {
+            const uint64_t c = ((uint64_t)gumbel_key(d, s0[j], mx, mx, __uint_as_float(e[i].z)) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)j);
+            best = c > best ? c : best;
+        }
+    }
+    best = wave_max_u64(best);
+    const int j = (int)(0xFFFFFFFFu - (uint32_t)best);
+    return (int)(rfl(edges[first + j].w) >> 24);
+}
+
+// The policy target of the Gumbel root search into pi[0 .. A): pi' = softmax(log P + sigma64(cq)) over the k > 0 root edges
+// of an active game, in float64 (include/yy_engine.h); an unvisited child is completed with the visited children's SW / SN,
+// SW summed in units of 2^-32 like first-play urgency's, so that it does not depend on which lane holds which child.
+template <int NW>
+__device__ __forceinline__ void gumbel_distribution(const MctsDev &d, const uint4 *edges, const int first, const int k, double *pi) {
+    const int A = d.geo.A;
+    uint4 e[NW];
+    int mx = 0, sn = 0;
+    long long sw = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int j = i * 64 + lane_id();
+        e[i] = (j < k) ? edges[first + j] : make_uint4(0u, 0u, 0u, 0u);
+        const int n = (int)e[i].y;
+        mx = max(mx, n);
+        if (n > 0) {
+            sn += n;
+            sw += (long long)__dmul_rn((double)__uint_as_float(e[i].z), 4294967296.0);
+        }
+    }
+    mx = wave_max_i32(mx);
+    sn = wave_sum(sn);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sw += __shfl_xor(sw, o, 64);
+    const double cq0 = sn ? __ddiv_rn(__dmul_rn((double)sw, 0x1p-32), (double)sn) : 0.0;
+    const double scale = __dmul_rn(__dadd_rn((double)d.g_cvisit, (double)mx), (double)d.g_cscale);
+    double l[NW], lm = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int n = (int)e[i].y;
+        const double cq = (n > 0) ? __ddiv_rn((double)__uint_as_float(e[i].z), (double)n) : cq0;
+        l[i] = (i * 64 + lane_id() < k) ? __dadd_rn(log((double)__uint_as_float(e[i].x)), __dmul_rn(scale, cq)) : -INFINITY;
+        lm = fmax(lm, l[i]);
+    }
+    lm = sp::wave_max_f64(lm);
+    double x[NW], part = 0.0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        // every prior 0: the uniform row over the root's edges
+        x[i] = (i * 64 + lane_id() < k) ? ((lm > -INFINITY) ? exp(l[i] - lm) : 1.0) : 0.0;
+        part += x[i];
+    }
+    const double tot = sp::wave_sum_f64(part);
+    for (int a = lane_id(); a < A; a += 64) pi[a] = 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NW; i++)
+        if (i * 64 + lane_id() < k) pi[(int)(e[i].w >> 24)] = x[i] / tot;
+}
+
 // Node.get_children_distribution (mcts.py:183-215) of game g's root for T == 1 and T == 0 into pi[0 .. A) (float64; global
-// memory or LDS), with forced playouts on the pruned counts.  Every thread of the one-wavefront block calls it.
+// memory or LDS), with forced playouts on the pruned counts; with the Gumbel root search its policy target for both.  Every
+// thread of the one-wavefront block calls it.
 template <int NW> __device__ __forceinline__ void root_distribution(const MctsDev &d, const int g, const int tzero, double *pi) {
     const int A = d.geo.A;
     const uint4 hdr = d.nodes[(size_t)g * d.node_cap];
     const int k = node_k(rfl(hdr.y)), first = rfl((int)hdr.x);
     const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
     const bool act = rfl((int)d.state[g].active) != 0;
+    if (d.gumbel && act && k > 0) {                                             // wave-uniform
+        gumbel_distribution<NW>(d, edges, first, k, pi);
+        return;
+    }
     int cn[NW];                                                                 // k <= A <= 64 * NW: edge i*64 + lane
     int sum = 0, mx = 0;
 #pragma unroll

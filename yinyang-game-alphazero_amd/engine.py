@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, SHARED_EVALUATIONS_HIGH_WATER, forced_k, fpu_r, shared_slots
-from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_SOLVER, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, SHARED_EVALUATIONS_HIGH_WATER, forced_k, fpu_r, gumbel_m, shared_slots
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_GUMBEL_ROOT, FLAG_SOLVER, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -387,6 +387,22 @@ def root_noise(seed, game_id, ply, draw, mask, alpha):
     return out
 
 
+def gumbel_rows(seed, game_ids, plies, A, out=None):
+    """Gumbel root search: the Gumbel(0, 1) variable of every action at the root of (game_ids[g], plies[g]), keyed by (seed,
+    game id, ply, action) (include/yy_engine.h, yy_selfplay_root_gumbel): float32 [G,A], what BatchedMCTS.set_gumbel takes.
+    out: a float32 [G,A] tensor to draw into (the context keeps the pointer of the rows it was given)."""
+    G = game_ids.shape[0]
+    _need(game_ids, torch.int64, (G,), "game_ids")
+    _need(plies, torch.int32, (G,), "plies")
+    if out is None:
+        out = torch.empty((G, int(A)), dtype=torch.float32, device=game_ids.device)
+    _need(out, torch.float32, (G, int(A)), "out")
+    with torch.cuda.device(game_ids.device):
+        check(lib().yy_selfplay_root_gumbel(ct.c_uint64(int(seed) & (2 ** 64 - 1)), _p(game_ids), _p(plies), G, int(A), _p(out),
+                                            _stream()))
+    return out
+
+
 def sample_actions(seed, game_id, ply, searching, pi, mask, temperature_threshold):
     """The move choice of play_game (self_play.py:143-160), keyed by (seed, game_id, ply): int32 [G], -1 where not searching."""
     G, A = mask.shape
@@ -673,8 +689,16 @@ class BatchedMCTS:
     def __init__(self, G, R, C, max_sims, cpuct=1.0, aliased=False, rowcol=False, device=None,
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
                  keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
-                 fpu_reduction=None, fpu_reduction_root=None, solver=False):
-        """solver=True (copied boards and leaves_per_step == 1 only; default off: every launch is what it is without the
+                 fpu_reduction=None, fpu_reduction_root=None, solver=False, gumbel_root=None, gumbel_c_visit=None,
+                 gumbel_c_scale=None):
+        """gumbel_root=m in 2 .. 64 (copied boards and leaves_per_step == 1 only, not with forced_playouts or solver; None / 0 =
+        off: every launch is what it is without the option; the paper: 16) with gumbel_c_visit (None: 50) and gumbel_c_scale
+        (None: 1.0): the Gumbel root search (YY_FLAG_GUMBEL_ROOT, include/yy_engine.h).  The root spends the search's budget by
+        sequential halving over the m children of largest g + log P, g the Gumbel rows of set_gumbel() (gumbel_rows() draws
+        them; needed before the first search), root_policy() is the completed-Q target softmax(log P + sigma(q)) at both
+        temperatures, root_gumbel_action() the move; root_counts() stays raw.  The budget is the search's num_sims (or the
+        game's own); advance() is refused.  Fixed at creation.
+        solver=True (copied boards and leaves_per_step == 1 only; default off: every launch is what it is without the
         option): the MCTS-Solver (YY_FLAG_SOLVER, include/yy_engine.h).  Terminal results are propagated up the tree as proven
         WIN / LOSS / DRAW statuses, a descent that reaches a proven node below the root stops there without an evaluator row,
         and the root keeps being searched; root_proven() and solver_counters() read the proofs.  Fixed at creation.
@@ -713,6 +737,8 @@ class BatchedMCTS:
         self.forced_playouts = forced_k(forced_playouts)
         self.fpu_reduction, self.fpu_reduction_root = fpu_r(fpu_reduction, fpu_reduction_root)
         self.solver = bool(solver)
+        self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
+        self._gumbel = None                    # device float32 [G,A] the root expansions read (set_gumbel)
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
                          _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
                          | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
@@ -720,9 +746,11 @@ class BatchedMCTS:
                          | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0)
                          | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0)
                          | (FLAG_FPU_REDUCTION if self.fpu_reduction else 0)
-                         | (FLAG_SOLVER if self.solver else 0),
+                         | (FLAG_SOLVER if self.solver else 0)
+                         | (FLAG_GUMBEL_ROOT if self.gumbel_root else 0),
                          int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
-                         self.forced_playouts, self.fpu_reduction, self.fpu_reduction_root)
+                         self.forced_playouts, self.fpu_reduction, self.fpu_reduction_root,
+                         self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale)
         h = ct.c_void_p()
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_create(ct.byref(cfg), ct.byref(h)))
@@ -884,6 +912,30 @@ class BatchedMCTS:
         finished search (YYError with a select pending)."""
         return self._read(lib().yy_mcts_solver_counters, self.SOLVER_COUNTERS)
 
+    def set_gumbel(self, rows):
+        """Gumbel root search: the Gumbel variables the root expansions read, device float32 [G,A] by action (gumbel_rows()).
+        The context keeps the tensor and its pointer: set it before steps are captured and rewrite it in place
+        (gumbel_rows(..., out=rows)) before every search."""
+        _need(rows, torch.float32, (self.G, self.A), "rows")
+        check(lib().yy_mcts_set_gumbel(self._h, _p(rows)))
+        self._gumbel = rows
+
+    def root_gumbel(self):
+        """Gumbel root search: float32 [G,A], the base score f32(g + log P) of every root child by action; NaN for an action
+        without a root edge and for an inactive game."""
+        out = torch.empty((self.G, self.A), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_root_gumbel(self._h, _p(out), _stream()))
+        return out
+
+    def root_gumbel_action(self):
+        """Gumbel root search: int32 [G], the move -- among the most visited root children the largest g + log P + sigma(q),
+        the lowest action on ties; -1 for an inactive game and for a root without children."""
+        out = torch.empty(self.G, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_root_gumbel_action(self._h, _p(out), _stream()))
+        return out
+
     def root_stats(self):
         visits = torch.empty(self.G, dtype=torch.int32, device=self.device)
         wsum = torch.empty(self.G, dtype=torch.float64, device=self.device)
@@ -997,8 +1049,9 @@ class BatchedMCTS:
         budget exceeds (nothing is read back; values are clamped to 0 .. max_sims on the device)."""
         num_sims, budgets = self._sim_budgets(num_sims, num_sims_bound)
         self.set_sim_budgets(budgets)
-        if self.K > 1 or getattr(self, "_advanced", False):
-            # K > 1: the last step's descents follow from it on the device; K = 1: the budget of a kept root (tree reuse)
+        if self.K > 1 or getattr(self, "_advanced", False) or getattr(self, "gumbel_root", 0):
+            # K > 1: the last step's descents follow from it on the device; K = 1: the budget of a kept root (tree reuse), and
+            # the budget that the Gumbel root search plans its halving for
             self.set_num_sims(num_sims)
         self.begin(boards, root_players, active)
         policy, _ = evaluate(True)

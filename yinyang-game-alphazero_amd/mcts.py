@@ -137,8 +137,15 @@ class MCTS:
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False, solver=False):
-        """solver=True (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; default off): the
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_seed=0):
+        """gumbel_root=m in 2 .. 64 with gumbel_c_visit (None: 50) / gumbel_c_scale (None: 1.0) (not in the reference; needs
+        board_semantics="copied" and leaves_per_step == 1, not with forced_playouts, tree_reuse or solver; None / 0 = off): the
+        Gumbel root search (engine.BatchedMCTS, options.SearchOptions).  Every search draws its own Gumbel rows from the
+        device's counter streams, keyed by (gumbel_seed, the game's index in the batch, the number of searches made so far);
+        the distribution search() returns is the completed-Q policy target at temperature 0 and 1 (any other temperature
+        raises ValueError), and gumbel_action() / gumbel_actions() give the move of the last search: the Gumbel winner.
+        dirichlet_noise=False is recommended with it.
+        solver=True (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; default off): the
         MCTS-Solver (engine.BatchedMCTS, options.SearchOptions) -- proven wins, losses and draws are propagated in the tree, a
         descent stops at a proven node below the root without asking the network, and the root keeps being searched.  The
         distribution search() returns is computed from the visit counts as without it; the proofs are read with the
@@ -196,6 +203,12 @@ class MCTS:
         # the resolver's refusals: aliased boards, leaves_per_step > 1
         self.solver = bool(solver) and options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics,
                                                        solver=solver).solver
+        self.gumbel = options.gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
+        if self.gumbel[0]:                                      # the resolver's refusals
+            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts,
+                            tree_reuse=tree_reuse, solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit,
+                            gumbel_c_scale=gumbel_c_scale)
+        self.gumbel_seed, self.gumbel_searches, self._gumbel_ctx = int(gumbel_seed), 0, None
         self._shared_owner = None              # the network whose rows the tables hold
         self.game, self.neural_net = game, neural_net
         self.num_simulations, self.cpuct, self.temperature = num_simulations, cpuct, temperature
@@ -224,7 +237,11 @@ class MCTS:
                                      reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
                                      evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
                                      forced_playouts=self.forced_playouts, fpu_reduction=self.fpu_reduction,
-                                     fpu_reduction_root=self.fpu_reduction_root, solver=self.solver)
+                                     fpu_reduction_root=self.fpu_reduction_root, solver=self.solver,
+                                     **(dict(zip(("gumbel_root", "gumbel_c_visit", "gumbel_c_scale"), self.gumbel))
+                                        if self.gumbel[0] else {}))
+            if self.gumbel[0]:                                   # the rows every search redraws in place
+                ctx.set_gumbel(torch.zeros((G, self.A), dtype=torch.float32, device=ctx.device))
             if self.shared_evaluations:
                 ctx.set_shared_evaluations(engine.SharedEvaluations(self.R, self.C, self.shared_evaluations, ctx.device,
                                                                     *self.symmetry, replace=self.shared_evaluations_replace))
@@ -264,6 +281,14 @@ class MCTS:
         if not isinstance(sims, (int, np.integer)):
             sims = np.asarray(sims.cpu() if isinstance(sims, torch.Tensor) else sims)
         most = int(sims.max()) if isinstance(sims, np.ndarray) and sims.size else int(sims)
+        if self.gumbel[0]:
+            # this search's Gumbel rows: game = index in the batch, "ply" = the search counter (24 bits of the counter word)
+            G = boards.shape[0]
+            engine.gumbel_rows(self.gumbel_seed, torch.arange(G, dtype=torch.int64, device=ctx.device),
+                               torch.full((G,), self.gumbel_searches & 0xFFFFFF, dtype=torch.int32, device=ctx.device), self.A,
+                               out=ctx._gumbel)
+            self.gumbel_searches += 1
+            self._gumbel_ctx = ctx
         if self.use_graph and self._capturable(ev) and most > 8:
             # device-resident evaluator: replay [forward + yy_mcts_step] from a hipGraph (one host call per simulation
             # instead of one per kernel); same launches, same results as the eager loop
@@ -278,12 +303,25 @@ class MCTS:
         if self.temperature in (0, 1.0):
             pi = ctx.root_policy(temperature_zero=(self.temperature == 0))
         else:
+            if self.gumbel[0]:
+                raise ValueError(f"gumbel_root={self.gumbel[0]}: the completed-Q policy target exists for temperature 0 and 1 "
+                                 f"(root_policy), not for temperature={self.temperature}")
             if self.forced_playouts:
                 raise ValueError(f"forced_playouts={self.forced_playouts}: the pruned distribution exists for temperature 0 and 1 "
                                  f"(root_policy), not for temperature={self.temperature}")
             c = ctx.root_counts().cpu().numpy()
             pi = torch.from_numpy(np.stack([children_distribution(r, self.temperature) for r in c])).to(boards.device)
         return pi, ctx
+
+    def gumbel_actions(self):
+        """gumbel_root: the Gumbel winner of every game of the last search_batch / search (device int32 [G]; -1: no move)."""
+        if self._gumbel_ctx is None:
+            raise ValueError("gumbel_actions needs MCTS(gumbel_root=m) and a finished search")
+        return self._gumbel_ctx.root_gumbel_action()
+
+    def gumbel_action(self):
+        """gumbel_root: the Gumbel winner of the last search() (an int; -1: no move)."""
+        return int(self.gumbel_actions()[0])
 
     # ---- reference API (mcts.py:275-343)
     def search(self, board, player, add_exploration_noise=False, num_simulations=None):

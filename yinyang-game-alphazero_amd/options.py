@@ -124,7 +124,18 @@ class SearchOptions:
     is proven lost for the opponent when there is one.  It goes with the playout cap, tree reuse (statuses travel with the
     kept nodes), free-running, evaluation reuse, the book, the shared table, evaluation symmetry, forced playouts and
     fpu_reduction.  Proofs under virtual visits and on a board that changes under a node are follow-ups, and the reference has
-    no such option: refused with leaves_per_step > 1, board_semantics="aliased", reference_quirks and rng="numpy"."""
+    no such option: refused with leaves_per_step > 1, board_semantics="aliased", reference_quirks and rng="numpy".
+
+    gumbel_root m in 2 .. 64 (the paper: 16) with gumbel_c_visit (None: 50) and gumbel_c_scale (None: 1.0): the Gumbel root search
+    (Danihelka et al., ICLR 2022; include/yy_engine.h YY_FLAG_GUMBEL_ROOT).  Every root draws a Gumbel
+    variable per action from the game's own counter stream, spends the search's budget -- num_simulations, or the playout-cap
+    draw -- by sequential halving over the m actions of largest g + log P, records softmax(log P + sigma(completed q)) as pi
+    and plays the most visited child of largest g + log P + sigma(q) at every ply: the temperature rule and the move draw are
+    not consulted.  Below the root the search is unchanged.  dirichlet_epsilon = 0 is recommended with it.  It goes with the
+    playout cap, free-running, evaluation symmetry, evaluation reuse, the book, both shared tables and fpu_reduction (below the
+    root only).  It changes which moves a search picks.  Sequential halving plans the visits of a fresh root in the one-descent
+    selection, and the reference has no such option: refused with leaves_per_step > 1, board_semantics="aliased",
+    reference_quirks, rng="numpy", forced_playouts, tree_reuse and solver (each a follow-up)."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -138,6 +149,9 @@ class SearchOptions:
     shared_evaluations: int = 0             # slots of the shared evaluation table (a power of two); 0: off
     shared_evaluations_replace: bool = False  # the table deduplicates inserts and evicts (needs shared_evaluations)
     solver: bool = False                    # proven wins, losses and draws in the tree
+    gumbel_root: int = 0                    # m of the Gumbel root search; 0: off
+    gumbel_c_visit: float = 0.0             # resolved: 50 where it was not given; 0.0 when the option is off
+    gumbel_c_scale: float = 0.0             # resolved: 1.0 where it was not given; 0.0 when the option is off
 
     @property
     def playout_cap(self):
@@ -160,6 +174,8 @@ class SearchOptions:
             on.update(shared_evaluations_replace=True)
         if self.solver:
             on.update(solver=True)
+        if self.gumbel_root:
+            on.update(gumbel_root=self.gumbel_root, gumbel_c_visit=self.gumbel_c_visit, gumbel_c_scale=self.gumbel_c_scale)
         return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
 
 
@@ -175,6 +191,42 @@ def forced_k(forced_playouts):
     if not 0.0 <= k < float("inf"):
         raise OptionConflict(f"forced_playouts={forced_playouts!r}: a finite number >= 0 (0 / None: off; KataGo uses 2)", "forced_playouts")
     return k
+
+
+GUMBEL_C_VISIT, GUMBEL_C_SCALE = 50.0, 1.0   # the paper's board-game values
+
+
+def gumbel_m(gumbel_root, gumbel_c_visit=None, gumbel_c_scale=None):
+    """(m, c_visit, c_scale) as the device takes them: (0, 0.0, 0.0) for gumbel_root None / 0 (off), else the int m in 2 .. 64,
+    the finite c_visit >= 0 (None: 50) and the finite c_scale > 0 (None: 1.0).  OptionConflict naming gumbel_root for anything
+    else, a c value without the option included."""
+    def num(x):
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            return float("nan")
+
+    if gumbel_root is None or gumbel_root is False or (not isinstance(gumbel_root, bool) and gumbel_root == 0):
+        if gumbel_c_visit is not None or gumbel_c_scale is not None:
+            raise OptionConflict("gumbel_c_visit / gumbel_c_scale without gumbel_root: they belong to the option, and gumbel_root "
+                                 "0 / None switches it off", "gumbel_root")
+        return 0, 0.0, 0.0
+    try:
+        m = int(gumbel_root)
+        if m != gumbel_root or isinstance(gumbel_root, bool):
+            m = -1
+    except (TypeError, ValueError):
+        m = -1
+    if not 2 <= m <= 64:
+        raise OptionConflict(f"gumbel_root={gumbel_root!r}: the number of root actions sequential halving starts from, an int in "
+                             "2 .. 64 (0 / None: off; the paper uses 16)", "gumbel_root")
+    cv = GUMBEL_C_VISIT if gumbel_c_visit is None else num(gumbel_c_visit)
+    if not 0.0 <= cv < float("inf"):
+        raise OptionConflict(f"gumbel_c_visit={gumbel_c_visit!r}: a finite number >= 0 (None: 50)", "gumbel_root")
+    cs = GUMBEL_C_SCALE if gumbel_c_scale is None else num(gumbel_c_scale)
+    if not 0.0 < cs < float("inf"):
+        raise OptionConflict(f"gumbel_c_scale={gumbel_c_scale!r}: a finite number > 0 (None: 1.0)", "gumbel_root")
+    return m, cv, cs
 
 
 SHARED_EVALUATIONS_DEFAULT_SLOTS = 1 << 23   # 8x8: 280 bytes a slot = 2.3 GB, the 8-stone opening book's size
@@ -232,12 +284,12 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
             fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
-            solver=False):
+            solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
     counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- evaluation_symmetry, forced_playouts, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
+    -- evaluation_symmetry, forced_playouts, gumbel_root, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
     shared_evaluations, shared_evaluations_replace, solver -- so two broken rules name the same option everywhere.  forced_playouts,
     fpu_reduction: None and 0 = off; shared_evaluations: None and False = off; shared_evaluations_replace: None and False = off."""
     K = max(1, int(leaves_per_step))
@@ -261,6 +313,17 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             raise OptionConflict(f"forced_playouts={forced_playouts}: the forcing test is part of the one-descent selection on copied "
                                  f"boards, and the reference has no such option -- not with {', '.join(b[1] for b in bad)}",
                                  "forced_playouts", [b[0] for b in bad])
+    gm, gcv, gcs = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
+    if gm:
+        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
+               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
+               (bool(forced), "forced_playouts", f"forced_playouts={forced_playouts}"), (bool(tree_reuse), "tree_reuse", "tree_reuse=True"),
+               (bool(solver), "solver", "solver=True")]
+        bad = [b[1:] for b in bad if b[0]]
+        if bad:
+            raise OptionConflict(f"gumbel_root={gumbel_root}: sequential halving plans the visits of a fresh root in the one-descent "
+                                 "selection on copied boards, its draws are the device's counter streams, and the reference has no "
+                                 f"such option -- not with {', '.join(b[1] for b in bad)}", "gumbel_root", [b[0] for b in bad])
     if free_running:
         bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
                (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
@@ -333,4 +396,4 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
                          evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
-                         shared, replace, bool(solver))
+                         shared, replace, bool(solver), gm, gcv, gcs)

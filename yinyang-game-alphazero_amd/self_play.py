@@ -89,8 +89,13 @@ class _Engine:
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, solver=False):
-        """solver (default off): the MCTS-Solver in every search, fast and full alike (options.SearchOptions) -- descents stop
+                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
+        """gumbel_root m (default off) with gumbel_c_visit / gumbel_c_scale: the Gumbel root search in every search, fast and full
+        alike (options.SearchOptions) -- every root draws its Gumbel variables from the game's own counter stream (keyed by seed,
+        game index and ply), spends its budget by sequential halving, records the completed-Q policy target as pi and plays
+        the Gumbel winner at every ply: the temperature rule and the move draw are not consulted.  dirichlet_epsilon = 0 is
+        recommended with it (the Gumbel variables are the root's exploration).
+        solver (default off): the MCTS-Solver in every search, fast and full alike (options.SearchOptions) -- descents stop
         at proven nodes below the root and ask for no evaluator row; the move draw and the recorded pi are computed from the
         visit counts as without it and do not look at proofs.
         shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
@@ -125,13 +130,15 @@ class _Engine:
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
                                forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
-                               solver)
+                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
         if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
             raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
                              "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
         self.K, self.tree_reuse, self.forced_playouts = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts
         self.fpu_reduction, self.fpu_reduction_root = opts.fpu_reduction, opts.fpu_reduction_root
         self.solver = opts.solver
+        self.gumbel = dict(gumbel_root=opts.gumbel_root, gumbel_c_visit=opts.gumbel_c_visit,
+                           gumbel_c_scale=opts.gumbel_c_scale) if opts.gumbel_root else {}
         self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
@@ -156,7 +163,7 @@ class _Engine:
                                       leaves_per_step=self.K, evaluation_symmetry=self.symmetry[0],
                                       symmetry_seed=self.symmetry[1], forced_playouts=self.forced_playouts,
                                       fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root,
-                                      solver=self.solver)
+                                      solver=self.solver, **self.gumbel)
         self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
@@ -241,6 +248,11 @@ class LockstepEngine(_Engine):
         # playout cap: the examples of a game are its fully searched moves only, so an example's index is not its ply
         self.hist_ply = torch.zeros((G, T), dtype=torch.int64, device=dev) if self.fast_sims is not None else None
         self._ar = torch.arange(G, device=dev)
+        # Gumbel root search: the rows the root expansions read, redrawn in place before every search (captured steps hold
+        # the pointer); the free-running run has rows of its own (engine.SelfPlayRun)
+        self.gumbel_rows = torch.zeros((G, self.A), dtype=torch.float32, device=dev) if self.gumbel else None
+        if self.gumbel:
+            self.ctx.set_gumbel(self.gumbel_rows)
         self._ones = torch.ones(G, dtype=torch.int8, device=dev)
         # draining batch: once no new game will start, live games are packed to the front and only the leaf rows of the first
         # `rows` GAMES are evaluated (rows = the smallest tier that holds them; one captured step per tier).  rows and the tiers
@@ -251,7 +263,8 @@ class LockstepEngine(_Engine):
                                    if row_tiers is None else {int(t) for t in row_tiers if 0 < int(t) < G}))
 
     def _pack_live_games(self):
-        """Once per tier change: stable permutation of every per-slot tensor, live games first."""
+        """Once per tier change: stable permutation of every per-slot tensor, live games first (the Gumbel rows are redrawn
+        per move from (game id, ply) and stay in place)."""
         perm = torch.argsort((~self.alive).to(torch.int8), stable=True)
         for name in ("boards", "players", "ply", "n_ex", "alive", "game_id", "hist_state", "hist_pi", "hist_player") + (
                 ("hist_ply",) if self.hist_ply is not None else ()):
@@ -423,6 +436,8 @@ class LockstepEngine(_Engine):
         elif self.eps > 0:                                                     # add_noise = (step == 0), :131
             first = (searching & (self.ply == 0)).to(torch.uint8)
             noise = engine.root_noise(self.seed, self.game_id, self.ply, first, mask_u8, self.alpha)
+        if self.gumbel:                                                        # every root, every ply: the game's own stream
+            engine.gumbel_rows(self.seed, self.game_id, self.ply, self.A, out=self.gumbel_rows)
         record = searching                                                     # the games whose move becomes an example
         if self.fast_sims is None:
             self.search.run(self.boards, rp, self.sims, noise=noise, eps=self.eps, active=s_u8, rows=self.rows)
@@ -441,7 +456,9 @@ class LockstepEngine(_Engine):
             self.hist_ply[ar, slot] = torch.where(record, self.ply.to(torch.int64), self.hist_ply[ar, slot])
         self.n_ex += record.to(torch.int64)
         # ---- choose the action (:143-160) from the game's own stream
-        if self.rng == "numpy":
+        if self.gumbel:                                                        # the Gumbel winner, at every ply (no draw)
+            action = torch.where(searching, self.ctx.root_gumbel_action(), torch.full((G,), -1, dtype=torch.int32, device=dev))
+        elif self.rng == "numpy":
             action = self._numpy_actions(searching, pi, mask_u8)
         else:
             action = engine.sample_actions(self.seed, self.game_id, self.ply, s_u8, pi, mask_u8, self.thr)
@@ -651,8 +668,9 @@ class SelfPlayLanes:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, solver=False, **engine_kwargs):
-        """solver: the MCTS-Solver in every lane (options.SearchOptions).
+                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, **engine_kwargs):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale: the Gumbel root search in every lane (options.SearchOptions).
+        solver: the MCTS-Solver in every lane (options.SearchOptions).
         shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
         size asked for; memory_bytes() reports their sum.  shared_evaluations_replace: every lane's table is a replacing one,
         swept by its lane on the lane's stream.
@@ -664,7 +682,7 @@ class SelfPlayLanes:
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
                                forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
-                               solver)
+                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -868,8 +886,11 @@ class SelfPlayWorker:
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False, solver=False):
-        """solver: MCTS's (needs board_semantics="copied" and reference_quirks=False, which are not this class's defaults).
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale: MCTS's (needs board_semantics="copied" and reference_quirks=False, which
+        are not this class's defaults); every search draws its Gumbel rows in MCTS and the move played is the Gumbel winner at
+        every ply (MCTS.gumbel_action), so numpy's stream is not asked for the move.
+        solver: MCTS's (needs board_semantics="copied" and reference_quirks=False, which are not this class's defaults).
         shared_evaluations: MCTS's (a table shared by the one game's searches; needs board_semantics="copied",
         reference_quirks=False and a network whose evaluator is row-independent).  shared_evaluations_replace: MCTS's too.
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0; this
@@ -887,7 +908,8 @@ class SelfPlayWorker:
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
                                forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
                                fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
-                               shared_evaluations_replace=shared_evaluations_replace, solver=solver)
+                               shared_evaluations_replace=shared_evaluations_replace, solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+        self.gumbel_root = opts.gumbel_root
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
         self.num_simulations, self.num_games = num_simulations, num_games
@@ -909,7 +931,9 @@ class SelfPlayWorker:
                          evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
                          forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
                          fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None,
-                         shared_evaluations_replace=opts.shared_evaluations_replace, solver=opts.solver)
+                         shared_evaluations_replace=opts.shared_evaluations_replace, solver=opts.solver,
+                         **(dict(gumbel_root=opts.gumbel_root, gumbel_c_visit=opts.gumbel_c_visit,
+                                 gumbel_c_scale=opts.gumbel_c_scale) if opts.gumbel_root else {}))
 
     def play_game(self):
         game, examples = self.game, []
@@ -951,7 +975,9 @@ class SelfPlayWorker:
             else:
                 pi, root = self.mcts.search(board, root_player, add_exploration_noise=(step == 0))
                 examples.append((board, pi, player))
-            if temperature == 0:
+            if self.gumbel_root:
+                action = self.mcts.gumbel_action()
+            elif temperature == 0:
                 action = np.random.choice(np.where(pi == np.max(pi))[0])
             else:
                 probs = pi * valid_moves
@@ -993,8 +1019,9 @@ class SelfPlayManager:
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
                  fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
-                 solver=False):
-        """solver (its three counters go into `stats` as solver_*, in lockstep runs: a free-running context stays armed, and
+                 solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale: the Gumbel root search (options.SearchOptions),
+        solver (its three counters go into `stats` as solver_*, in lockstep runs: a free-running context stays armed, and
         the counters are read after a finished search),
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
         (None: the engine's seed, 1000 + seed, on every rank), forced_playouts, fpu_reduction / fpu_reduction_root,
@@ -1006,7 +1033,7 @@ class SelfPlayManager:
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
                                        tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
-                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace, solver)
+                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace, solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -1076,7 +1103,7 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
     the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root, shared_evaluations,
-    shared_evaluations_replace and solver among them) are SelfPlayManager's too."""
+    shared_evaluations_replace, solver and gumbel_root / gumbel_c_visit / gumbel_c_scale among them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
