@@ -145,6 +145,11 @@ HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root", "solver")]}
 
 
+def _handed(args, names):
+    """The flags' values under the option names `names`."""
+    return {n: getattr(args, "simulations" if n == "num_simulations" else n) for n in names}
+
+
 def _flag(args, name):
     """An option's name as its flag, with the value it was given."""
     attr = "simulations" if name == "num_simulations" else name
@@ -158,7 +163,7 @@ def refused(args):
     from yinyang_game_alphazero_amd import options       # imports neither torch nor numpy
     for names in HANDED[args.mode]:
         try:
-            options.resolve(**{n: getattr(args, "simulations" if n == "num_simulations" else n) for n in names})
+            options.resolve(**_handed(args, names))
         except options.OptionConflict as e:
             others = ", ".join(_flag(args, n) for n in e.conflicts)
             return f"train_alphazero.py: {_flag(args, e.option)}: {'not with ' + others if others else 'out of range'} ({e})"
@@ -199,17 +204,10 @@ def main(argv=None):
             dist.barrier()
     if args.mode == "train":                     # train_alphazero.py:84-101
         az = pkg.AlphaZero(game, args.model_dir, args.data_dir, num_iterations=args.iterations, num_episodes=args.episodes,
-                           num_simulations=args.simulations, num_epochs=args.epochs, num_workers=args.workers,
+                           num_epochs=args.epochs, num_workers=args.workers,
                            mcts_threads=args.mcts_threads, nn_mode=args.nn, concurrent_games=args.concurrent_games,
                            arena_games=args.arena_games, num_channels=args.channels, num_res_blocks=args.blocks,
-                           lr=args.lr, batch_size=args.batch_size, leaves_per_step=args.leaves_per_step,
-                           fast_simulations=args.fast_simulations, full_search_probability=args.full_search_probability,
-                           tree_reuse=args.tree_reuse, free_running=args.free_running,
-                           evaluation_symmetry=args.evaluation_symmetry, symmetry_seed=args.symmetry_seed,
-                           forced_playouts=args.forced_playouts, fpu_reduction=args.fpu_reduction,
-                           fpu_reduction_root=args.fpu_reduction_root, shared_evaluations=args.shared_evaluations,
-                           shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver,
-                           gumbel_root=args.gumbel_root, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
+                           lr=args.lr, batch_size=args.batch_size, **_handed(args, _SEARCH + ("symmetry_seed",)))
         hist = az.run()
         if rank == 0:
             print(json.dumps({"iterations": hist}))
@@ -221,32 +219,19 @@ def main(argv=None):
         if not os.path.exists(model_path):
             sys.exit(f"Model file not found: {model_path}")
         res = pkg.evaluate_vs_random(game, model_path, num_games=10, num_simulations=args.simulations, nn_mode=args.nn,
-                                     num_channels=args.channels, num_res_blocks=args.blocks,
-                                     leaves_per_step=args.leaves_per_step, tree_reuse=args.tree_reuse,
-                                     fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
-                                     solver=args.solver)
+                                     num_channels=args.channels, num_res_blocks=args.blocks, **_handed(args, HANDED["evaluate"][0]))
         print(json.dumps(res))
         return
     if not os.path.exists(model_path):           # same contract as the reference (train_alphazero.py:107-109)
         sys.exit(f"Model file not found: {model_path}")
-    path = pkg.generate_self_play_data(game, model_path, args.data_dir, num_games=args.episodes,
-                                       num_workers=args.workers, num_simulations=args.simulations,
-                                       concurrent_games=args.concurrent_games, board_semantics=args.board_semantics,
-                                       reference_quirks=args.reference_quirks, nn_mode=args.nn, seed=args.seed,
+    path = pkg.generate_self_play_data(game, model_path, args.data_dir, num_games=args.episodes, num_workers=args.workers,
+                                       concurrent_games=args.concurrent_games, nn_mode=args.nn, seed=args.seed,
                                        num_channels=args.channels, num_res_blocks=args.blocks,
                                        reference_format=args.reference_format,
                                        evaluation_reuse=None if args.evaluation_reuse == "auto" else False,
                                        opening_book_stones=0 if args.leaves_per_step > 1 else args.opening_book_stones,
-                                       lanes=args.lanes or None, leaves_per_step=args.leaves_per_step,
-                                       fast_simulations=args.fast_simulations,
-                                       full_search_probability=args.full_search_probability, tree_reuse=args.tree_reuse,
-                                       free_running=args.free_running, evaluation_symmetry=args.evaluation_symmetry,
-                                       symmetry_seed=args.symmetry_seed, forced_playouts=args.forced_playouts,
-                                       fpu_reduction=args.fpu_reduction, fpu_reduction_root=args.fpu_reduction_root,
-                                       shared_evaluations=args.shared_evaluations,
-                                       shared_evaluations_replace=args.shared_evaluations_replace, solver=args.solver,
-                                       gumbel_root=args.gumbel_root, gumbel_c_visit=args.gumbel_c_visit,
-                                       gumbel_c_scale=args.gumbel_c_scale)
+                                       lanes=args.lanes or None,
+                                       **_handed(args, HANDED["self-play"][0] + ("symmetry_seed",)))
     if rank == 0:
         st = pkg.generate_self_play_data.last_stats
         st = dict(st, positions_per_s=st["positions"] / st["seconds"], expansions_per_s=st["evals"] / st["seconds"])

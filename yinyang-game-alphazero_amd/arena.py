@@ -107,6 +107,10 @@ def proven_winning_move(ctx):
     return torch.where(wins.any(1), pick, torch.full_like(pick, -1))
 
 
+# what of SearchOptions.keywords() a match takes
+ARENA_OPTIONS = ("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root", "solver")
+
+
 class Arena:
     """num_games games between two players on one GPU.  A player is a batched evaluator
     (planes -> policy, value) searched with `num_simulations`, or the string "random" (uniformly random
@@ -142,10 +146,9 @@ class Arena:
         self.game = game
         opts = options.resolve(num_simulations, leaves_per_step, "aliased" if literal else "copied", tree_reuse=tree_reuse,
                                fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root, solver=solver)
-        self.tree_reuse, self.K = opts.tree_reuse, opts.leaves_per_step
-        self.fpu = dict(fpu_reduction=opts.fpu_reduction, fpu_reduction_root=opts.fpu_reduction_root) if opts.fpu_reduction else {}
-        self.solver = opts.solver
-        self.ctx_keywords = dict(self.fpu, **(dict(solver=True) if self.solver else {}))   # of every tree context of the match
+        self.tree_reuse, self.K, self.solver = opts.tree_reuse, opts.leaves_per_step, opts.solver
+        self.ctx_keywords = opts.tree_keywords()                     # of every tree context of the match
+        self.fpu = {k: v for k, v in self.ctx_keywords.items() if k.startswith("fpu_")}
         self.literal = bool(literal)
         self.evaluation_reuse = bool(evaluation_reuse)
         self.reference_scoring = bool(reference_scoring) or self.literal
@@ -177,7 +180,7 @@ class Arena:
                  and self.K == 1)
         ctx = engine.BatchedMCTS(G, self.R, self.C, max(1, self.sims), cpuct=self.cpuct, rowcol=self.rowcol, device=dev,
                                  aliased=self.literal, reuse_pass_value=reuse, reuse_transpositions=reuse,
-                                 leaves_per_step=self.K, **self.ctx_keywords)
+                                 **self.ctx_keywords)
         own = []           # tree_reuse: (the player moves as A, its evaluator's search on its own context)
         try:
             search = LockstepSearch(ctx, dual, use_graph=dense)     # routed mode: the row sets change every move
@@ -438,9 +441,7 @@ class AlphaZero:
         cur = _load_evaluator(self.game, current_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         best = _load_evaluator(self.game, best_model_path, self.device, self.nn_mode, self.num_channels, self.num_res_blocks)
         res = (Arena(self.game, cur, best, self.num_simulations, device=self.device, seed=len(self.history) * 131 + rank,
-                     leaves_per_step=self.options.leaves_per_step, tree_reuse=self.options.tree_reuse,
-                     fpu_reduction=self.options.fpu_reduction, fpu_reduction_root=self.options.fpu_reduction_root,
-                     solver=self.options.solver).play(mine)
+                     **{k: v for k, v in self.options.keywords().items() if k in ARENA_OPTIONS}).play(mine)
                if mine > 0 else dict(a_wins=0, b_wins=0, draws=0, games=0))
         if multi:
             t = torch.tensor([res["a_wins"], res["b_wins"], res["draws"], res["games"]], dtype=torch.int64, device=self.device)

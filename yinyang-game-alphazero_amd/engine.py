@@ -739,15 +739,13 @@ class BatchedMCTS:
         self.solver = bool(solver)
         self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
         self._gumbel = None                    # device float32 [G,A] the root expansions read (set_gumbel)
-        cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct,
-                         _flags(rowcol, aliased) | (FLAG_REUSE_PASS_VALUE if reuse_pass_value else 0)
-                         | (FLAG_REUSE_TRANSPOSITIONS if reuse_transpositions else 0)
-                         | (FLAG_KEEP_EVALUATIONS if keep_evaluations else 0)
-                         | (FLAG_EVAL_SYMMETRY if self.symmetry[0] == "random" else 0)
-                         | (FLAG_FORCED_PLAYOUTS if self.forced_playouts else 0)
-                         | (FLAG_FPU_REDUCTION if self.fpu_reduction else 0)
-                         | (FLAG_SOLVER if self.solver else 0)
-                         | (FLAG_GUMBEL_ROOT if self.gumbel_root else 0),
+        flags = _flags(rowcol, aliased)
+        for flag, on in ((FLAG_REUSE_PASS_VALUE, reuse_pass_value), (FLAG_REUSE_TRANSPOSITIONS, reuse_transpositions),
+                         (FLAG_KEEP_EVALUATIONS, keep_evaluations), (FLAG_EVAL_SYMMETRY, self.symmetry[0] == "random"),
+                         (FLAG_FORCED_PLAYOUTS, self.forced_playouts), (FLAG_FPU_REDUCTION, self.fpu_reduction),
+                         (FLAG_SOLVER, self.solver), (FLAG_GUMBEL_ROOT, self.gumbel_root)):
+            flags |= flag if on else 0
+        cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct, flags,
                          int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
                          self.forced_playouts, self.fpu_reduction, self.fpu_reduction_root,
                          self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale)

@@ -138,76 +138,43 @@ class MCTS:
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
                  shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_seed=0):
-        """gumbel_root=m in 2 .. 64 with gumbel_c_visit (None: 50) / gumbel_c_scale (None: 1.0) (not in the reference; needs
-        board_semantics="copied" and leaves_per_step == 1, not with forced_playouts, tree_reuse or solver; None / 0 = off): the
-        Gumbel root search (engine.BatchedMCTS, options.SearchOptions).  Every search draws its own Gumbel rows from the
-        device's counter streams, keyed by (gumbel_seed, the game's index in the batch, the number of searches made so far);
-        the distribution search() returns is the completed-Q policy target at temperature 0 and 1 (any other temperature
-        raises ValueError), and gumbel_action() / gumbel_actions() give the move of the last search: the Gumbel winner.
-        dirichlet_noise=False is recommended with it.
-        solver=True (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; default off): the
-        MCTS-Solver (engine.BatchedMCTS, options.SearchOptions) -- proven wins, losses and draws are propagated in the tree, a
-        descent stops at a proven node below the root without asking the network, and the root keeps being searched.  The
-        distribution search() returns is computed from the visit counts as without it; the proofs are read with the
-        context's root_proven().
-        shared_evaluations_replace (needs shared_evaluations): the table in its replacing form (engine.SharedEvaluations
-        replace=True, options.SearchOptions): one slot per position, and a sweep after every search -- with tree_reuse after
-        the advance that follows it -- evicts what was not used once the table is nearly full.  The same results.
-        shared_evaluations (not in the reference; None / False = off, True = the default size, an int = slots): the searches
-        of a context share their evaluations through an engine.SharedEvaluations table -- a position evaluated in an earlier
-        step of any game of the batch, or in an earlier search, needs no evaluator row again; same results.  Needs
-        board_semantics="copied", leaves_per_step == 1 and an evaluator that declares `row_independent` (network.BatchedEvaluator
-        in its float32-accurate modes; a search with any other evaluator raises ValueError); the table is emptied when the
-        network object changes.
-        fpu_reduction=r > 0 with fpu_reduction_root (None: r) (not in the reference; None / 0 = off): first-play urgency
-        reduction -- an unvisited child is scored with the mean value of its visited siblings less r * sqrt(their share of the
-        prior) instead of q = 0 (engine.BatchedMCTS); both board semantics, every leaves_per_step.
-        forced_playouts=k > 0 (not in the reference; needs board_semantics="copied" and leaves_per_step == 1; None / 0 = off):
-        forced playouts with policy target pruning at the root (engine.BatchedMCTS); the distribution search() returns is the
-        pruned one.  The device prunes for temperature 0 and 1 only: a search with any other temperature raises ValueError.
-        evaluation_symmetry="random" (not in the reference; needs board_semantics="copied"): every position is shown to the
-        network under a board symmetry drawn from (symmetry_seed, position) and the policy mapped back (engine.BatchedMCTS).
-        board_semantics: "aliased" = literal reference (the search mutates the caller's board);
+        """board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
+        num_threads is accepted for signature compatibility; simulations of one search are always
+        sequential (the reference's thread pool is an unsynchronised race, SURVEY.md section 0).
         evaluation_reuse (not in the reference; default off = its evaluator call sequence): a position is evaluated once per
         search (pass values with copied boards + the evaluation cache, include/yy_engine.h YY_FLAG_REUSE_*); same results, fewer
         evaluator rows; needs a deterministic network whose row results do not depend on the rest of the batch.
-        num_threads is accepted for signature compatibility; simulations of one search are always
-        sequential (the reference's thread pool is an unsynchronised race, SURVEY.md section 0).
-        leaves_per_step K (not in the reference; default 1 = its search): leaf parallelism with virtual visits -- every step
-        runs K descents per game and evaluates their leaves in one batch, so a search takes ceil(num_simulations / K)
-        evaluator calls (include/yy_engine.h).  Needs board_semantics="copied" and no evaluation_reuse.  It changes which
-        moves a search picks.
-        tree_reuse (default False = the reference, whose reuse_tree result never reaches search): reuse_tree() also re-roots
-        the tree on the device at the move taken (engine.BatchedMCTS.advance) and the next search(board, player) of that
-        position continues from the kept subtree, topping its root up to num_simulations; search_batch likewise after
-        advance_batch(actions).  Needs board_semantics="copied" and leaves_per_step == 1 (ValueError otherwise)."""
+        leaves_per_step, tree_reuse, evaluation_symmetry / symmetry_seed (None: 0), forced_playouts, fpu_reduction /
+        fpu_reduction_root, shared_evaluations / shared_evaluations_replace, solver and gumbel_root / gumbel_c_visit /
+        gumbel_c_scale are not in the reference and default to its search: options.SearchOptions says what each does and
+        options.resolve, asked once with all of them, which combine (OptionConflict, a ValueError, otherwise); the record is
+        `self.options`.  What is this class's own:
+        tree_reuse: reuse_tree() also re-roots the tree on the device at the move taken (engine.BatchedMCTS.advance) and the
+        next search(board, player) of that position continues from the kept subtree, topping its root up to num_simulations;
+        search_batch likewise after advance_batch(actions).
+        forced_playouts, gumbel_root: the distribution search() returns is the pruned one / the completed-Q policy target, which
+        the device computes for temperature 0 and 1 only: a search with any other temperature raises ValueError.
+        gumbel_root: every search draws its own Gumbel rows from the device's counter streams, keyed by (gumbel_seed, the game's
+        index in the batch, the number of searches made so far); gumbel_action() / gumbel_actions() give the move of the last
+        search: the Gumbel winner.  dirichlet_noise=False is recommended with it.
+        solver: the distribution search() returns is computed from the visit counts as without it; the proofs are read with the
+        context's root_proven().
+        shared_evaluations: the table (engine.SharedEvaluations) serves every search of a context, is emptied when the network
+        object changes, and needs an evaluator that declares `row_independent` (a search with any other raises ValueError); in
+        its replacing form it is swept after every search -- with tree_reuse after the advance that follows it."""
         assert board_semantics in ("aliased", "copied")
-        if tree_reuse and (board_semantics == "aliased" or max(1, int(leaves_per_step)) > 1):
-            raise ValueError('tree_reuse=True needs board_semantics="copied" and leaves_per_step == 1')
-        self.tree_reuse = bool(tree_reuse)
-        if evaluation_symmetry != "off" and board_semantics == "aliased":
-            raise ValueError('evaluation_symmetry="random" needs board_semantics="copied"')
-        self.symmetry = engine.symmetry_key(evaluation_symmetry, symmetry_seed)
-        self.forced_playouts = options.forced_k(forced_playouts)
-        if self.forced_playouts:                                # the resolver's refusals: aliased boards, leaves_per_step > 1
-            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts)
-        self.fpu_reduction, self.fpu_reduction_root = options.fpu_r(fpu_reduction, fpu_reduction_root)
-        # the resolver's refusals: aliased boards, leaves_per_step > 1
-        self.shared_evaluations = options.shared_slots(shared_evaluations)
-        if self.shared_evaluations:
-            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, shared_evaluations=shared_evaluations)
-        # refused without shared_evaluations
-        self.shared_evaluations_replace = options.resolve(shared_evaluations=shared_evaluations,
-                                                          shared_evaluations_replace=shared_evaluations_replace).shared_evaluations_replace
-        # the resolver's refusals: aliased boards, leaves_per_step > 1
-        self.solver = bool(solver) and options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics,
-                                                       solver=solver).solver
-        self.gumbel = options.gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
-        if self.gumbel[0]:                                      # the resolver's refusals
-            options.resolve(leaves_per_step=leaves_per_step, board_semantics=board_semantics, forced_playouts=forced_playouts,
-                            tree_reuse=tree_reuse, solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit,
-                            gumbel_c_scale=gumbel_c_scale)
+        self.options = opts = options.resolve(
+            None, leaves_per_step, board_semantics, evaluation_reuse=(evaluation_reuse,), tree_reuse=tree_reuse,
+            evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed, forced_playouts=forced_playouts,
+            fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
+            shared_evaluations_replace=shared_evaluations_replace, solver=solver, gumbel_root=gumbel_root,
+            gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+        for name in ("leaves_per_step", "tree_reuse", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
+                     "shared_evaluations_replace", "solver"):
+            setattr(self, name, getattr(opts, name))
+        self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, opts.symmetry_seed)
+        self.gumbel = (opts.gumbel_root, opts.gumbel_c_visit, opts.gumbel_c_scale)
         self.gumbel_seed, self.gumbel_searches, self._gumbel_ctx = int(gumbel_seed), 0, None
         self._shared_owner = None              # the network whose rows the tables hold
         self.game, self.neural_net = game, neural_net
@@ -216,7 +183,6 @@ class MCTS:
         self.use_dirichlet, self.dirichlet_alpha, self.dirichlet_epsilon = dirichlet_noise, dirichlet_alpha, dirichlet_epsilon
         self.board_semantics = board_semantics
         self.evaluation_reuse = bool(evaluation_reuse)
-        self.leaves_per_step = max(1, int(leaves_per_step))
         self.R, self.C = game.getBoardSize()
         self.A = game.getActionSize()
         self.rowcol = bool(getattr(game, "rowcol_rule", False))
@@ -234,12 +200,7 @@ class MCTS:
                                      aliased=(self.board_semantics == "aliased"), rowcol=self.rowcol,
                                      device=self.device,
                                      reuse_pass_value=self.evaluation_reuse and self.board_semantics == "copied",
-                                     reuse_transpositions=self.evaluation_reuse, leaves_per_step=self.leaves_per_step,
-                                     evaluation_symmetry=self.symmetry[0], symmetry_seed=self.symmetry[1],
-                                     forced_playouts=self.forced_playouts, fpu_reduction=self.fpu_reduction,
-                                     fpu_reduction_root=self.fpu_reduction_root, solver=self.solver,
-                                     **(dict(zip(("gumbel_root", "gumbel_c_visit", "gumbel_c_scale"), self.gumbel))
-                                        if self.gumbel[0] else {}))
+                                     reuse_transpositions=self.evaluation_reuse, **self.options.tree_keywords())
             if self.gumbel[0]:                                   # the rows every search redraws in place
                 ctx.set_gumbel(torch.zeros((G, self.A), dtype=torch.float32, device=ctx.device))
             if self.shared_evaluations:

@@ -1,6 +1,8 @@
 """The search options of the self-play layer and the ONE place that says which of them combine.  Imports neither torch nor
 numpy: train_alphazero.py asks for the verdict before it pays for either.  Every entry point calls `resolve` once with the
-inputs it has and hands `SearchOptions.keywords()` on.  A new option is one field, one rule in `resolve`, one forwarded keyword."""
+inputs it has, keeps the record and hands one of its two views on: `keywords()` to the next entry point, `tree_keywords()` to
+a tree context.  The combinations are one ordered table, RULES; what is handed on is another, HANDED_ON.  A new option is one
+field, one row in each table, its value check in `resolve`, and one keyword in each signature that takes it."""
 from dataclasses import dataclass
 
 
@@ -159,24 +161,36 @@ class SearchOptions:
         return {} if self.fast_simulations is None else dict(fast_simulations=self.fast_simulations,
                                                               full_search_probability=self.full_search_probability)
 
+    def _handed(self, tree_only=False):
+        return dict(leaves_per_step=self.leaves_per_step,
+                    **{f: getattr(self, f) for switch, fields, tree in HANDED_ON for f in fields
+                       if getattr(self, switch) != getattr(SearchOptions, switch) and (tree or not tree_only)})
+
     def keywords(self):
-        """The keywords to hand to the next layer: leaves_per_step always, the others only when they are on."""
-        on = {k: True for k in ("tree_reuse", "free_running") if getattr(self, k)}
-        if self.evaluation_symmetry != "off":
-            on.update(evaluation_symmetry=self.evaluation_symmetry, symmetry_seed=self.symmetry_seed)
-        if self.forced_playouts:
-            on.update(forced_playouts=self.forced_playouts)
-        if self.fpu_reduction:
-            on.update(fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root)
-        if self.shared_evaluations:
-            on.update(shared_evaluations=self.shared_evaluations)
-        if self.shared_evaluations_replace:
-            on.update(shared_evaluations_replace=True)
-        if self.solver:
-            on.update(solver=True)
-        if self.gumbel_root:
-            on.update(gumbel_root=self.gumbel_root, gumbel_c_visit=self.gumbel_c_visit, gumbel_c_scale=self.gumbel_c_scale)
-        return dict(leaves_per_step=self.leaves_per_step, **self.playout_cap, **on)
+        """The keywords to hand to the next layer: leaves_per_step always, the groups of HANDED_ON that are on."""
+        return self._handed()
+
+    def tree_keywords(self, seed=None):
+        """The keywords of keywords() that a tree context (engine.BatchedMCTS) takes; `seed` stands in for a symmetry_seed of
+        None."""
+        kw = self._handed(tree_only=True)
+        if "symmetry_seed" in kw and kw["symmetry_seed"] is None:
+            kw["symmetry_seed"] = seed
+        return kw
+
+
+# What a record hands on beside leaves_per_step, as groups: (the field that switches the group on -- it is on when the field
+# is not at its default --, the fields handed on then, whether a tree context takes them).  Both views read this table.
+HANDED_ON = (("fast_simulations", ("fast_simulations", "full_search_probability"), False),
+             ("tree_reuse", ("tree_reuse",), False),
+             ("free_running", ("free_running",), False),
+             ("evaluation_symmetry", ("evaluation_symmetry", "symmetry_seed"), True),
+             ("forced_playouts", ("forced_playouts",), True),
+             ("fpu_reduction", ("fpu_reduction", "fpu_reduction_root"), True),
+             ("shared_evaluations", ("shared_evaluations",), False),
+             ("shared_evaluations_replace", ("shared_evaluations_replace",), False),
+             ("solver", ("solver",), True),
+             ("gumbel_root", ("gumbel_root", "gumbel_c_visit", "gumbel_c_scale"), True))
 
 
 def forced_k(forced_playouts):
@@ -280,6 +294,44 @@ def fpu_r(fpu_reduction, fpu_reduction_root=None):
     return r, root
 
 
+# The conflict rules, in the ONE order they are asked in: (the option that refuses, the inputs it does not go with -- named in
+# this order --, why).  Two broken rules name the earlier one everywhere.  Every option's value check comes right before its
+# first rule, the playout cap's range checks between tree_reuse and leaves_per_step (resolve).
+_NO_SUCH_OPTION = "the reference has no such option, so it does not go with what exists for transcript parity with it -- not with"
+RULES = (
+    ("evaluation_symmetry", ("board_semantics", "reference_quirks", "rng"), _NO_SUCH_OPTION),
+    ("forced_playouts", ("leaves_per_step", "board_semantics", "reference_quirks", "rng"),
+     "the forcing test is part of the one-descent selection on copied boards, and the reference has no such option -- not with"),
+    ("gumbel_root", ("leaves_per_step", "board_semantics", "reference_quirks", "rng", "forced_playouts", "tree_reuse", "solver"),
+     "sequential halving plans the visits of a fresh root in the one-descent selection on copied boards, its draws are the "
+     "device's counter streams, and the reference has no such option -- not with"),
+    ("free_running", ("leaves_per_step", "board_semantics", "reference_quirks", "rng", "tree_reuse"),
+     "the in-step move plays copied boards with one descent per step, the device's counter streams and a fresh root per move "
+     "-- not with"),
+    ("tree_reuse", ("leaves_per_step",), "the tree is re-rooted for one descent per step only -- not with"),
+    ("tree_reuse", ("board_semantics",), "a kept subtree needs every node's own board -- not with"),
+    ("leaves_per_step", ("board_semantics", "reference_quirks", "evaluation_reuse", "opening_book"),
+     "a leaf-parallel search runs on copied boards, evaluates every leaf and has no book -- not with"),
+    ("fpu_reduction", ("reference_quirks", "rng"), _NO_SUCH_OPTION),
+    ("shared_evaluations", ("board_semantics", "leaves_per_step", "reference_quirks"),
+     "a shared evaluation table serves a position's stored row to every game, which needs copied boards, one descent per step "
+     "and a search that is not the reference's literal one -- not with"),
+    ("shared_evaluations_replace", ("shared_evaluations",),
+     "it is the replacing form of the shared evaluation table -- not without"),
+    ("solver", ("leaves_per_step", "board_semantics", "reference_quirks", "rng"),
+     "a proof belongs to a node whose position does not change and to one descent per step, and the reference has no such "
+     "option -- not with"))
+
+
+def _ask(option, rendered, given):
+    """The rules of `option`, which is on and renders as `rendered`: OptionConflict for the first of them that `given` -- input
+    -> (it is in the way, as a message renders it) -- breaks."""
+    for _, others, why in (r for r in RULES if r[0] == option):
+        bad = [n for n in others if given[n][0]]
+        if bad:
+            raise OptionConflict(f"{rendered}: {why} {', '.join(given[n][1] for n in bad)}", option, bad)
+
+
 def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", reference_quirks=False, rng="philox",
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
@@ -288,57 +340,34 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
-    counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are checked in one fixed order
-    -- evaluation_symmetry, forced_playouts, gumbel_root, free_running, tree_reuse, the playout cap, leaves_per_step, fpu_reduction,
-    shared_evaluations, shared_evaluations_replace, solver -- so two broken rules name the same option everywhere.  forced_playouts,
-    fpu_reduction: None and 0 = off; shared_evaluations: None and False = off; shared_evaluations_replace: None and False = off."""
+    counts <= 0: no book); num_simulations None: no upper bound for fast_simulations.  The rules are asked in the one fixed
+    order of RULES, so two broken rules name the same option everywhere.  forced_playouts, fpu_reduction: None and 0 = off;
+    shared_evaluations: None and False = off; shared_evaluations_replace: None and False = off."""
     K = max(1, int(leaves_per_step))
-    aliased = board_semantics == "aliased"
+    given = dict(leaves_per_step=(K > 1, f"leaves_per_step={leaves_per_step}"),
+                 board_semantics=(board_semantics == "aliased", 'board_semantics="aliased"'),
+                 reference_quirks=(reference_quirks, "reference_quirks=True"), rng=(rng != "philox", f'rng="{rng}"'),
+                 tree_reuse=(tree_reuse, "tree_reuse=True"), solver=(solver, "solver=True"),
+                 evaluation_reuse=(any(x is not None and bool(x) for x in evaluation_reuse),
+                                   "evaluation reuse (reuse_pass_value / reuse_transpositions / keep_evaluations / evaluation_reuse)"),
+                 opening_book=(opening_book is not None and not (isinstance(opening_book, int) and opening_book <= 0),
+                               "an opening book"))
     if evaluation_symmetry not in ("off", "random"):
         raise OptionConflict(f'evaluation_symmetry={evaluation_symmetry!r}: "off" or "random"', "evaluation_symmetry")
-    if evaluation_symmetry != "off":
-        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (reference_quirks, "reference_quirks", "reference_quirks=True"),
-               (rng != "philox", "rng", f'rng="{rng}"')]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f'evaluation_symmetry="{evaluation_symmetry}": the reference has no such option, so it does not go with '
-                                 f"what exists for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
-                                 "evaluation_symmetry", [b[0] for b in bad])
+    sym = evaluation_symmetry != "off"
+    if sym:
+        _ask("evaluation_symmetry", f'evaluation_symmetry="{evaluation_symmetry}"', given)
     forced = forced_k(forced_playouts)
+    given["forced_playouts"] = (forced, f"forced_playouts={forced_playouts}")
     if forced:
-        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
-               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f"forced_playouts={forced_playouts}: the forcing test is part of the one-descent selection on copied "
-                                 f"boards, and the reference has no such option -- not with {', '.join(b[1] for b in bad)}",
-                                 "forced_playouts", [b[0] for b in bad])
+        _ask("forced_playouts", given["forced_playouts"][1], given)
     gm, gcv, gcs = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
     if gm:
-        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
-               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
-               (bool(forced), "forced_playouts", f"forced_playouts={forced_playouts}"), (bool(tree_reuse), "tree_reuse", "tree_reuse=True"),
-               (bool(solver), "solver", "solver=True")]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f"gumbel_root={gumbel_root}: sequential halving plans the visits of a fresh root in the one-descent "
-                                 "selection on copied boards, its draws are the device's counter streams, and the reference has no "
-                                 f"such option -- not with {', '.join(b[1] for b in bad)}", "gumbel_root", [b[0] for b in bad])
+        _ask("gumbel_root", f"gumbel_root={gumbel_root}", given)
     if free_running:
-        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
-               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"'),
-               (tree_reuse, "tree_reuse", "tree_reuse=True")]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict("free_running=True: the in-step move plays copied boards with one descent per step, the device's "
-                                 f"counter streams and a fresh root per move -- not with {', '.join(b[1] for b in bad)}",
-                                 "free_running", [b[0] for b in bad])
-    if tree_reuse and K > 1:
-        raise OptionConflict(f"tree_reuse=True: the tree is re-rooted for one descent per step only -- not with leaves_per_step={leaves_per_step}",
-                             "tree_reuse", ["leaves_per_step"])
-    if tree_reuse and aliased:
-        raise OptionConflict('tree_reuse=True: a kept subtree needs every node\'s own board -- not with board_semantics="aliased"',
-                             "tree_reuse", ["board_semantics"])
+        _ask("free_running", "free_running=True", given)
+    if tree_reuse:
+        _ask("tree_reuse", "tree_reuse=True", given)
     P = float(full_search_probability)
     if not 0.0 < P <= 1.0:
         raise OptionConflict(f"full_search_probability={full_search_probability}: the share of full searches lies in (0, 1]",
@@ -350,50 +379,23 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
         raise OptionConflict(f"fast_simulations={fast_simulations}: a fast search runs no more than num_simulations={num_simulations}",
                              "fast_simulations", ["num_simulations"])
     if K > 1:
-        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (reference_quirks, "reference_quirks", "reference_quirks=True"),
-               (any(x is not None and bool(x) for x in evaluation_reuse), "evaluation_reuse",
-                "evaluation reuse (reuse_pass_value / reuse_transpositions / keep_evaluations / evaluation_reuse)"),
-               (opening_book is not None and not (isinstance(opening_book, int) and opening_book <= 0), "opening_book", "an opening book")]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f"leaves_per_step={K}: a leaf-parallel search runs on copied boards, evaluates every leaf and has no "
-                                 f"book -- not with {', '.join(b[1] for b in bad)}", "leaves_per_step", [b[0] for b in bad])
+        _ask("leaves_per_step", f"leaves_per_step={K}", given)
     fpu, fpu_root = fpu_r(fpu_reduction, fpu_reduction_root)
     if fpu:
-        bad = [(reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f"fpu_reduction={fpu_reduction}: the reference has no such option, so it does not go with what exists "
-                                 f"for transcript parity with it -- not with {', '.join(b[1] for b in bad)}",
-                                 "fpu_reduction", [b[0] for b in bad])
+        _ask("fpu_reduction", f"fpu_reduction={fpu_reduction}", given)
     shared = shared_slots(shared_evaluations)
+    given["shared_evaluations"] = (not shared, "shared_evaluations")       # in the way of its replacing form when it is off
     if shared:
-        bad = [(aliased, "board_semantics", 'board_semantics="aliased"'), (K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"),
-               (reference_quirks, "reference_quirks", "reference_quirks=True")]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict(f"shared_evaluations={shared_evaluations}: a shared evaluation table serves a position's stored row "
-                                 "to every game, which needs copied boards, one descent per step and a search that is not the "
-                                 f"reference's literal one -- not with {', '.join(b[1] for b in bad)}",
-                                 "shared_evaluations", [b[0] for b in bad])
+        _ask("shared_evaluations", f"shared_evaluations={shared_evaluations}", given)
     if shared_evaluations_replace not in (None, False, True):
         raise OptionConflict(f"shared_evaluations_replace={shared_evaluations_replace!r}: True or False", "shared_evaluations_replace")
-    replace = bool(shared_evaluations_replace)
-    if replace and not shared:
-        raise OptionConflict("shared_evaluations_replace=True: it is the replacing form of the shared evaluation table -- not "
-                             "without shared_evaluations", "shared_evaluations_replace", ["shared_evaluations"])
+    if shared_evaluations_replace:
+        _ask("shared_evaluations_replace", "shared_evaluations_replace=True", given)
     if solver not in (None, False, True):
         raise OptionConflict(f"solver={solver!r}: True or False", "solver")
     if solver:
-        bad = [(K > 1, "leaves_per_step", f"leaves_per_step={leaves_per_step}"), (aliased, "board_semantics", 'board_semantics="aliased"'),
-               (reference_quirks, "reference_quirks", "reference_quirks=True"), (rng != "philox", "rng", f'rng="{rng}"')]
-        bad = [b[1:] for b in bad if b[0]]
-        if bad:
-            raise OptionConflict("solver=True: a proof belongs to a node whose position does not change and to one descent per step, "
-                                 f"and the reference has no such option -- not with {', '.join(b[1] for b in bad)}",
-                                 "solver", [b[0] for b in bad])
+        _ask("solver", "solver=True", given)
     cap = fast is not None and P < 1.0
-    sym = evaluation_symmetry != "off"
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
                          evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
-                         shared, replace, bool(solver), gm, gcv, gcs)
+                         shared, bool(shared_evaluations_replace), bool(solver), gm, gcv, gcs)

@@ -134,11 +134,8 @@ class _Engine:
         if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
             raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
                              "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
-        self.K, self.tree_reuse, self.forced_playouts = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts
-        self.fpu_reduction, self.fpu_reduction_root = opts.fpu_reduction, opts.fpu_reduction_root
-        self.solver = opts.solver
-        self.gumbel = dict(gumbel_root=opts.gumbel_root, gumbel_c_visit=opts.gumbel_c_visit,
-                           gumbel_c_scale=opts.gumbel_c_scale) if opts.gumbel_root else {}
+        self.options = opts
+        self.K, self.tree_reuse, self.forced_playouts, self.solver = opts.leaves_per_step, opts.tree_reuse, opts.forced_playouts, opts.solver
         self.symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         self.fast_sims, self.p_full = opts.fast_simulations, opts.full_search_probability
         self.game = game
@@ -160,10 +157,7 @@ class _Engine:
         self.ctx = engine.BatchedMCTS(self.G, self.R, self.C, self.sims, cpuct=cpuct, aliased=self.aliased,
                                       rowcol=self.rowcol, device=self.device, reuse_pass_value=self.reuse_pass_value,
                                       reuse_transpositions=self.reuse_transpositions, keep_evaluations=self.keep_evaluations,
-                                      leaves_per_step=self.K, evaluation_symmetry=self.symmetry[0],
-                                      symmetry_seed=self.symmetry[1], forced_playouts=self.forced_playouts,
-                                      fpu_reduction=self.fpu_reduction, fpu_reduction_root=self.fpu_reduction_root,
-                                      solver=self.solver, **self.gumbel)
+                                      **opts.tree_keywords(seed))
         self.book = _opening_book(opening_book, game, evaluator, self.device, self.symmetry)
         if self.book is not None:
             self.ctx.set_book(self.book)
@@ -250,8 +244,8 @@ class LockstepEngine(_Engine):
         self._ar = torch.arange(G, device=dev)
         # Gumbel root search: the rows the root expansions read, redrawn in place before every search (captured steps hold
         # the pointer); the free-running run has rows of its own (engine.SelfPlayRun)
-        self.gumbel_rows = torch.zeros((G, self.A), dtype=torch.float32, device=dev) if self.gumbel else None
-        if self.gumbel:
+        self.gumbel_rows = torch.zeros((G, self.A), dtype=torch.float32, device=dev) if self.options.gumbel_root else None
+        if self.options.gumbel_root:
             self.ctx.set_gumbel(self.gumbel_rows)
         self._ones = torch.ones(G, dtype=torch.int8, device=dev)
         # draining batch: once no new game will start, live games are packed to the front and only the leaf rows of the first
@@ -436,7 +430,7 @@ class LockstepEngine(_Engine):
         elif self.eps > 0:                                                     # add_noise = (step == 0), :131
             first = (searching & (self.ply == 0)).to(torch.uint8)
             noise = engine.root_noise(self.seed, self.game_id, self.ply, first, mask_u8, self.alpha)
-        if self.gumbel:                                                        # every root, every ply: the game's own stream
+        if self.options.gumbel_root:                                                        # every root, every ply: the game's own stream
             engine.gumbel_rows(self.seed, self.game_id, self.ply, self.A, out=self.gumbel_rows)
         record = searching                                                     # the games whose move becomes an example
         if self.fast_sims is None:
@@ -456,7 +450,7 @@ class LockstepEngine(_Engine):
             self.hist_ply[ar, slot] = torch.where(record, self.ply.to(torch.int64), self.hist_ply[ar, slot])
         self.n_ex += record.to(torch.int64)
         # ---- choose the action (:143-160) from the game's own stream
-        if self.gumbel:                                                        # the Gumbel winner, at every ply (no draw)
+        if self.options.gumbel_root:                                                        # the Gumbel winner, at every ply (no draw)
             action = torch.where(searching, self.ctx.root_gumbel_action(), torch.full((G,), -1, dtype=torch.int32, device=dev))
         elif self.rng == "numpy":
             action = self._numpy_actions(searching, pi, mask_u8)
@@ -927,13 +921,7 @@ class SelfPlayWorker:
         self.mcts = MCTS(game, neural_net, num_simulations=num_simulations, cpuct=cpuct,
                          dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                          num_threads=num_parallel, board_semantics=board_semantics, device=device,
-                         leaves_per_step=self.leaves_per_step, tree_reuse=self.tree_reuse,
-                         evaluation_symmetry=opts.evaluation_symmetry, symmetry_seed=opts.symmetry_seed,
-                         forced_playouts=opts.forced_playouts, fpu_reduction=opts.fpu_reduction,
-                         fpu_reduction_root=opts.fpu_reduction_root, shared_evaluations=opts.shared_evaluations or None,
-                         shared_evaluations_replace=opts.shared_evaluations_replace, solver=opts.solver,
-                         **(dict(gumbel_root=opts.gumbel_root, gumbel_c_visit=opts.gumbel_c_visit,
-                                 gumbel_c_scale=opts.gumbel_c_scale) if opts.gumbel_root else {}))
+                         **{k: v for k, v in opts.keywords().items() if k not in opts.playout_cap})   # the cap is drawn in play_game
 
     def play_game(self):
         game, examples = self.game, []
