@@ -1,8 +1,8 @@
 """Plain-numpy restatement of forced playouts with policy target pruning (include/yy_engine.h YY_FLAG_FORCED_PLAYOUTS, DESIGN.md
 section 3).
 
-TEST INFRASTRUCTURE.  One game, copied boards, K = 1, on the Node / Edge / _expand / _select of leaf_parallel_model.py, the Tree
-and advance() of tree_reuse_model.py and the exact hash evaluator of hash_eval.py.
+TEST INFRASTRUCTURE.  One game, copied boards, K = 1: the search of tests/tree_model.py with forced=k, which asks is_forced()
+below at the root, and the exact hash evaluator of hash_eval.py.
 
   search(root_or_board, player, budget, k)   tree_reuse_model.search with one change: at depth 0 of every descent, with S the sum
                                              of the root's child visits, an edge with N >= 1 and f64(N)*f64(N) < (k*f64(P))*f64(S)
@@ -25,9 +25,8 @@ import math
 
 import numpy as np
 
-from hash_eval import hash_eval_batch
-from leaf_parallel_model import EXPAND, REEXPAND, ROOTPASS, TERMINAL, Node, Result, _expand, _select
-from tree_reuse_model import Tree, advance  # noqa: F401  (advance: re-exported for the callers of this model)
+import tree_model
+from tree_model import Tree, advance  # noqa: F401  (advance: re-exported for the callers of this model)
 
 f32 = np.float32
 
@@ -103,102 +102,18 @@ PSCALE = 32.0   # the hash evaluator's priors lie in (0, 1/64]: k * P * S then s
                 # evaluator returns them times 32 (a power of two: still exact in float32), priors in (0, 1/2]
 
 
-def search(root_or_board, player, budget, k, pbits=10, vbits=11, noise=None, eps=0.25, cpuct=1.0, flags=0, mutant=None,
-           pscale=PSCALE):
-    """-> Result: tree_reuse_model.search's fields (counts, child_w, child_p, root_visits, root_w, evals, kept, tree) plus forced,
-    pruned, pi, pi0 (module docstring)."""
+def search(root_or_board, player, budget, k, pbits=10, vbits=11, cpuct=1.0, mutant=None, pscale=PSCALE, **options):
+    """tree_model.search at K = 1 with forced=k -> Result, with pruned, pi, pi0 (module docstring)."""
     assert mutant is None or mutant in MUTANTS
-    def evaluator(b):
-        pol, val = hash_eval_batch(b, pbits, vbits)
-        return pol * f32(pscale), val
-
-    cpuct = f32(cpuct)
-    raw = {}
-    if isinstance(root_or_board, Tree):
-        tree = root_or_board
-        root = tree.root
-        assert root.player == int(player)
-        raw = {id(e): e.P for e in root.edges}
-        if noise is not None and any(float(noise[e.action]) != 0.0 for e in root.edges):
-            keep = f32(1.0 - eps)
-            for e in root.edges:
-                e.P = f32(float(f32(keep * e.P)) + eps * float(noise[e.action]))
-    else:
-        board = np.array(root_or_board, np.int8)
-        root = Node(board, int(player))
-        pol = evaluator(board[None])[0][0]
-        _expand(root, pol, flags, noise, eps)                      # root call, value discarded (mcts.py:295)
-        raw = {id(e): f32(pol[e.action]) for e in root.edges}
-        tree = Tree(root)
-    A = root.board.size
-    kept = tree.kept
-    evals = forced = 0
-
-    def child_sum():
-        return tree.n if mutant == "s_root_n" else sum(e.N for e in root.edges)
-
-    while tree.n < budget:
-        node, path, parent = root, [], None
-        while True:
-            if node.terminal:
-                kind = TERMINAL
-                break
-            if not node.edges:
-                kind = ROOTPASS if node is root else REEXPAND
-                break
-            e = None
-            if k and node is root:
-                S = child_sum()
-                owed = [x for x in node.edges
-                        if is_forced(k, raw[id(x)] if mutant == "prior_raw" else x.P, x.N, S, mutant)]
-                if owed:
-                    e = owed[-1] if mutant == "forced_high" else owed[0]   # edges are in ascending action
-                    forced += 1
-            if e is None:
-                e = _select(node, {}, cpuct)
-            path.append(e)
-            parent = node
-            if e.child is None:
-                kind = EXPAND
-                break
-            node = e.child
-        if kind == TERMINAL:
-            v, v_is_py = node.tv, True
-        else:
-            if kind == EXPAND:
-                b = parent.board.copy()
-                b.flat[path[-1].action] = parent.player
-                child = Node(b, -parent.player)
-                path[-1].child = child
-                node = child
-            P, V = evaluator(node.board[None])
-            evals += 1
-            _expand(node, P[0], flags)
-            v, v_is_py = f32(V[0]), False
-        depth = len(path)
-        v32 = f32(v)
-        for i, e in enumerate(path):
-            sv = -v32 if (depth - (i + 1)) & 1 else v32
-            e.N += 1
-            e.W = f32(e.W + sv)
-        tree.n += 1
-        if tree.is_py and v_is_py and depth == 0:
-            tree.w_py += v
-        else:
-            sv = -v32 if depth & 1 else v32
-            base = f32(tree.w_py) if tree.is_py else tree.wf
-            tree.wf = f32(base + sv)
-            tree.is_py = False
-    r = Result()
-    r.counts = np.zeros(A, np.int32)
-    r.pruned = np.zeros(A, np.int32)
-    r.child_w = np.zeros(A, np.float32)
-    r.child_p = np.zeros(A, np.float32)
-    S = child_sum() if (mutant == "s_root_n" and root.edges) else None
-    for e, npr in zip(root.edges, prune(root.edges, k, cpuct, mutant, raw, S)):
-        r.counts[e.action], r.child_w[e.action], r.child_p[e.action], r.pruned[e.action] = e.N, e.W, e.P, npr
+    s = tree_model.Search(root_or_board, player, budget, 1, pbits, vbits, cpuct=cpuct, forced=k, pscale=pscale,
+                          mutant=mutant and "forced_playouts." + mutant, **options).run()
+    r = s.result()
+    edges = s.root.edges
+    r.pruned = np.zeros(s.A, np.int32)
+    S = s.tree.n if (mutant == "s_root_n" and edges) else None
+    for e, npr in zip(edges, prune(edges, k, cpuct, mutant, s.raw, S)):
+        r.pruned[e.action] = npr
     r.pi, r.pi0 = distribution(r.pruned, False), distribution(r.pruned, True)
-    r.root_visits, r.root_w, r.evals, r.kept, r.tree, r.forced = tree.n, tree.w, evals, kept, tree, forced
     return r
 
 

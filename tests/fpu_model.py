@@ -1,8 +1,8 @@
 """Plain-numpy restatement of the first-play urgency reduction (include/yy_engine.h YY_FLAG_FPU_REDUCTION).
 
-TEST INFRASTRUCTURE.  One game, on the Node / Edge / _expand / _select of leaf_parallel_model.py, the Tree and advance() of
-tree_reuse_model.py, the forcing test of forced_playouts_model.py and the exact hash evaluator of hash_eval.py (its priors
-times PSCALE, as in forced_playouts_model: sqrt(SP) is then not negligible next to the values).
+TEST INFRASTRUCTURE.  One game: the search of tests/tree_model.py with r / r_root, which asks select() below wherever r > 0,
+and the exact hash evaluator of hash_eval.py (its priors times PSCALE, as in forced_playouts_model: sqrt(SP) is then not
+negligible next to the values).
 
   search(root_or_board, player, budget, r, r_root, K, forced, aliased)
         the search of leaf_parallel_model (K descents per step with virtual visits; K = 1: the reference's search) from a
@@ -22,10 +22,9 @@ import math
 import numpy as np
 
 import oracle_lib as O
-from forced_playouts_model import PSCALE, is_forced
-from hash_eval import hash_eval_batch
-from leaf_parallel_model import EXPAND, REEXPAND, ROOTPASS, TERMINAL, Node, Result, _expand, _select
-from tree_reuse_model import Tree, advance
+import tree_model
+from forced_playouts_model import PSCALE
+from tree_model import advance, dirichlet_noise, random_root  # noqa: F401  (re-exported for the callers of this model)
 
 f32 = np.float32
 
@@ -94,150 +93,11 @@ def select(node, vc, cpuct, r, mutant=None, raw=None):
     return best
 
 
-def search(root_or_board, player, budget, r=0.0, r_root=None, K=1, forced=0.0, aliased=False, pbits=10, vbits=11, noise=None,
-           eps=0.25, cpuct=1.0, flags=0, mutant=None, pscale=PSCALE):
-    """-> Result with counts int32 [A], child_w f32 [A], child_p f32 [A], root_visits, root_w, evals, tree (the Tree after
-    the search, for advance()), final_board (aliased: the one board after the search) and failed (a descent found no
-    selectable child: the game stopped there, as on the device)."""
+def search(root_or_board, player, budget, r=0.0, r_root=None, K=1, pbits=10, vbits=11, mutant=None, pscale=PSCALE, **options):
+    """tree_model.search with the reduction r (the root: r_root; None: r) -> Result; forced, aliased: its keywords."""
     assert mutant is None or mutant in MUTANTS
-    assert K == 1 or not (forced or aliased or isinstance(root_or_board, Tree))
-    assert not (aliased and (forced or isinstance(root_or_board, Tree)))
-    r = float(r)
-    r_root = r if r_root is None else float(r_root)
-    if mutant == "r_everywhere":
-        r_root = r
-
-    def evaluator(b):
-        pol, val = hash_eval_batch(b, pbits, vbits)
-        return pol * f32(pscale), val
-
-    cpuct = f32(cpuct)
-    raw = {}
-    if isinstance(root_or_board, Tree):
-        tree = root_or_board
-        root = tree.root
-        assert root.player == int(player)
-        if noise is not None and any(float(noise[e.action]) != 0.0 for e in root.edges):
-            raw = {id(e): e.P for e in root.edges}
-            keep = f32(1.0 - eps)
-            for e in root.edges:
-                e.P = f32(float(f32(keep * e.P)) + eps * float(noise[e.action]))
-    else:
-        board = np.array(root_or_board, np.int8)
-        root = Node(board, int(player))
-        pol = evaluator(board[None])[0][0]
-        _expand(root, pol, flags, noise, eps)                      # root call, value discarded (mcts.py:295)
-        if noise is not None and any(float(noise[e.action]) != 0.0 for e in root.edges):
-            raw = {id(e): f32(pol[e.action]) for e in root.edges}
-        tree = Tree(root)
-    shared = root.board.copy()                                     # aliased: the one board of the search
-    A = root.board.size
-    evals = 0
-    failed = False
-
-    def choose(node, vc):
-        if forced and node is root:
-            S = sum(e.N for e in root.edges)
-            owed = [x for x in root.edges if is_forced(forced, x.P, x.N, S)]
-            if owed:
-                return owed[0]
-        if not r:
-            return _select(node, vc, cpuct)
-        return select(node, vc, cpuct, r_root if node is root else r, mutant, raw if node is root else None)
-
-    while tree.n < budget and not failed:
-        keff = min(K, budget - tree.n)
-        vc, desc, first_of = {}, [], {}
-        for j in range(keff):                                      # selection phase: the tree does not change
-            node, path, parent = root, [], None
-            while True:
-                if node.terminal:
-                    kind = TERMINAL
-                    break
-                if not node.edges:
-                    kind = ROOTPASS if node is root else REEXPAND
-                    break
-                e = choose(node, vc)
-                if e is None:
-                    failed = True
-                    break
-                path.append(e)
-                parent = node
-                if e.child is None:
-                    kind = EXPAND
-                    break
-                node = e.child
-            if failed:
-                break
-            for e in path:
-                vc[id(e)] = vc.get(id(e), 0) + 1
-            key = id(path[-1]) if kind == EXPAND else id(node)
-            dup = first_of.setdefault(key, j) if kind != TERMINAL else j
-            desc.append(dict(kind=kind, path=path, node=node, parent=parent, dup=dup if dup != j else -1))
-        if failed:
-            break
-        for d in desc:
-            d["need"] = d["kind"] != TERMINAL and d["dup"] < 0
-            if not d["need"]:
-                continue
-            if aliased:                                            # the shared board: place the move iff it is legal on it now
-                if d["kind"] != ROOTPASS:
-                    par, e = d["parent"], d["path"][-1]
-                    if O.valid_mask(shared[None], [par.player], flags)[0][e.action]:
-                        shared.flat[e.action] = par.player
-                    d["player"] = -par.player
-                else:
-                    d["player"] = root.player
-                d["board"] = shared.copy()
-            elif d["kind"] == EXPAND:
-                par, e = d["parent"], d["path"][-1]
-                b = par.board.copy()
-                b.flat[e.action] = par.player                    # a legal move of the parent always places (copied boards)
-                d["board"], d["player"] = b, -par.player
-            else:
-                d["board"], d["player"] = d["node"].board, d["node"].player
-        rows = [d for d in desc if d["need"]]
-        if rows:
-            P, V = evaluator(np.stack([d["board"] for d in rows]))
-            for i, d in enumerate(rows):
-                d["policy"], d["value"] = P[i], f32(V[i])
-        evals += len(rows)
-        for d in desc:                                             # expansion + backup phase, in descent order
-            if d["kind"] == TERMINAL:
-                v, v_is_py = d["node"].tv, True
-            elif d["dup"] >= 0:
-                v, v_is_py = desc[d["dup"]]["value"], False
-            else:
-                v, v_is_py = d["value"], False
-                if d["kind"] == EXPAND:
-                    child = Node(d["board"], d["player"])
-                    d["path"][-1].child = child
-                    _expand(child, d["policy"], flags)
-                else:
-                    d["node"].board = d["board"]                   # aliased: the node is expanded on the board as it is now
-                    _expand(d["node"], d["policy"], flags)
-            depth = len(d["path"])
-            v32 = f32(v)
-            for i, e in enumerate(d["path"]):
-                sv = -v32 if (depth - (i + 1)) & 1 else v32
-                e.N += 1
-                e.W = f32(e.W + sv)
-            tree.n += 1
-            if tree.is_py and v_is_py and depth == 0:
-                tree.w_py += v
-            else:
-                sv = -v32 if depth & 1 else v32
-                base = f32(tree.w_py) if tree.is_py else tree.wf
-                tree.wf = f32(base + sv)
-                tree.is_py = False
-    res = Result()
-    res.counts = np.zeros(A, np.int32)
-    res.child_w = np.zeros(A, np.float32)
-    res.child_p = np.zeros(A, np.float32)
-    for e in root.edges:
-        res.counts[e.action], res.child_w[e.action], res.child_p[e.action] = e.N, e.W, e.P
-    res.root_visits, res.root_w, res.evals, res.tree, res.final_board, res.failed = tree.n, tree.w, evals, tree, shared, failed
-    return res
+    return tree_model.search(root_or_board, player, budget, K, pbits, vbits, r=r, r_root=r_root, pscale=pscale,
+                             mutant=mutant and "fpu." + mutant, **options)
 
 
 # ------------------------------------------------------------------------------------------------ the fixtures of the GPU tests
@@ -270,26 +130,6 @@ CASES = {
     "5x7-aliased":    (5, 7, 48, dict(r=R, aliased=True), 0.25, 1),
     "9x12-aliased":   (9, 12, 16, dict(r=R, aliased=True), 0.0, 1),
 }
-
-
-def random_root(rows, cols, plies, seed):
-    """A position after `plies` random legal moves from the empty board (fewer when the game ends first), side to move."""
-    rng = np.random.default_rng(seed)
-    board, player = np.zeros((1, rows, cols), np.int8), np.ones(1, np.int8)
-    for _ in range(plies):
-        m = O.valid_mask(board, player)[0]
-        if not m.any() or O.game_ended(board, player)[0] != 0:
-            break
-        board, player, _ = O.next_state(board, player, np.array([rng.choice(np.flatnonzero(m))], np.int32))
-    return board[0], int(player[0])
-
-
-def dirichlet_noise(board, player, seed, alpha=0.3):
-    legal = np.flatnonzero(O.valid_mask(board[None], [player])[0])
-    nz = np.zeros(board.size)
-    if len(legal):
-        nz[legal] = np.random.default_rng(seed).dirichlet([alpha] * len(legal))
-    return nz
 
 
 class Move:

@@ -1,7 +1,7 @@
 """Plain-numpy restatement of the Gumbel root search (include/yy_engine.h YY_FLAG_GUMBEL_ROOT).
 
-TEST INFRASTRUCTURE.  One game, copied boards, K = 1, on the Node / Edge / _expand / _select of leaf_parallel_model.py and the
-exact hash evaluator of hash_eval.py.  Below the root the search is leaf_parallel_model's PUCT; the root differs:
+TEST INFRASTRUCTURE.  One game, copied boards, K = 1: the search of tests/tree_model.py with m > 0, which asks select_root()
+below at the root, and the exact hash evaluator of hash_eval.py.  Below the root the search is plain PUCT; the root differs:
 
   seq(m, n)                 the considered-visit sequence, mctx's table; seq_at(m, n, S) the device's closed form of seq(m, n)[S]
   gumbel(seed, gid, ply, a) the draw: f32(-log(-log(u))) over tests/philox_ref.py, purpose 4
@@ -17,8 +17,7 @@ import math
 import numpy as np
 
 import philox_ref as P
-from hash_eval import hash_eval_batch
-from leaf_parallel_model import EXPAND, REEXPAND, ROOTPASS, TERMINAL, Node, _expand, _select
+import tree_model
 
 f32 = np.float32
 PURPOSE = 4
@@ -86,20 +85,19 @@ def best_of(edges, idx, s0, maxN, c_visit, c_scale):
     return best
 
 
-class Search:
-    def __init__(self, board, player, n, m, c_visit=50.0, c_scale=1.0, pbits=10, vbits=11, noise=None, eps=0.25, cpuct=1.0,
-                 pscale=1.0, zero_prior=None):
-        """zero_prior: an action whose root prior is set to exactly 0 (s0 = -inf)"""
-        self.n, self.m, self.cv, self.cs, self.cpuct = int(n), int(m), f32(c_visit), f32(c_scale), f32(cpuct)
-        self.eval = lambda b: (lambda pv: (pv[0] * f32(pscale), pv[1]))(hash_eval_batch(b, pbits, vbits))
-        self.root = Node(np.array(board, np.int8), int(player))
-        pol = self.eval(self.root.board[None])[0][0].copy()
-        if zero_prior is not None:
-            pol[zero_prior] = 0.0
-        _expand(self.root, pol, 0, noise, eps)
-        self.A = self.root.board.size
-        self.sims = 0
-        self.s0 = None
+def select_root(edges, s0, n, m, c_visit, c_scale):
+    """-> the edge a descent takes at the root; n: the budget, s0: the base scores in edge order"""
+    S = sum(e.N for e in edges)
+    v = seq(min(m, len(edges)), n)[S]
+    maxN = max(e.N for e in edges)
+    cand = [i for i, e in enumerate(edges) if e.N == v] or list(range(len(edges)))
+    return edges[best_of(edges, cand, s0, maxN, c_visit, c_scale)]
+
+
+class Search(tree_model.Search):
+    def __init__(self, board, player, n, m, c_visit=50.0, c_scale=1.0, **options):
+        """tree_model.Search at K = 1 with the root rule; zero_prior: an action whose root prior is set to exactly 0 (s0 = -inf)"""
+        super().__init__(board, player, n, 1, m=m, c_visit=c_visit, c_scale=c_scale, **options)
 
     def host_s0(self, g_row):
         with np.errstate(divide="ignore"):
@@ -109,74 +107,15 @@ class Search:
         """by_action: array [A] or dict of the root children's base scores"""
         self.s0 = [f32(by_action[e.action]) for e in self.root.edges]
 
-    def select_root(self):
-        edges = self.root.edges
-        S = sum(e.N for e in edges)
-        v = seq(min(self.m, len(edges)), self.n)[S]
-        maxN = max(e.N for e in edges)
-        cand = [i for i, e in enumerate(edges) if e.N == v] or list(range(len(edges)))
-        return edges[best_of(edges, cand, self.s0, maxN, self.cv, self.cs)]
-
-    def step(self):
-        """one simulation; False once the budget is spent"""
-        if self.sims >= self.n:
-            return False
-        root = self.root
-        node, path, parent = root, [], None
-        while True:
-            if node.terminal:
-                kind = TERMINAL
-                break
-            if not node.edges:
-                kind = ROOTPASS if node is root else REEXPAND
-                break
-            e = self.select_root() if node is root else _select(node, {}, self.cpuct)
-            path.append(e)
-            parent = node
-            if e.child is None:
-                kind = EXPAND
-                break
-            node = e.child
-        if kind == TERMINAL:
-            v = node.tv
-        else:
-            if kind == EXPAND:
-                b = parent.board.copy()
-                b.flat[path[-1].action] = parent.player
-                node = path[-1].child = Node(b, -parent.player)
-            Pn, V = self.eval(node.board[None])
-            _expand(node, Pn[0], 0)
-            v = f32(V[0])
-        v32, depth = f32(v), len(path)
-        for i, e in enumerate(path):
-            e.N += 1
-            e.W = f32(e.W + (-v32 if (depth - (i + 1)) & 1 else v32))
-        self.sims += 1
-        return True
-
-    def run(self):
-        while self.step():
-            pass
-        return self
-
     # ---- read-outs, by action
     def counts(self):
-        out = np.zeros(self.A, np.int32)
-        for e in self.root.edges:
-            out[e.action] = e.N
-        return out
+        return self.result().counts
 
     def child_w(self):
-        out = np.zeros(self.A, np.float32)
-        for e in self.root.edges:
-            out[e.action] = e.W
-        return out
+        return self.result().child_w
 
     def child_p(self):
-        out = np.zeros(self.A, np.float32)
-        for e in self.root.edges:
-            out[e.action] = e.P
-        return out
+        return self.result().child_p
 
     def winner(self):
         edges = self.root.edges

@@ -1,8 +1,7 @@
 """Plain-numpy restatement of the MCTS solver (include/yy_engine.h YY_FLAG_SOLVER).
 
-TEST INFRASTRUCTURE.  One game, copied boards, one descent per step, on fpu_model.py: its select() (first-play urgency), the
-forcing test, the Tree and advance() of tree_reuse_model.py, the Node / Edge / _expand / _select of leaf_parallel_model.py and
-the exact hash evaluator with its priors times PSCALE.
+TEST INFRASTRUCTURE.  One game, copied boards, one descent per step: the search of tests/tree_model.py with solver=True, which
+asks status() and propagate() below, and the exact hash evaluator with its priors times PSCALE.
 
   search(root_or_board, player, budget, solver, r, r_root, forced)
         fpu_model.search at K = 1 on copied boards, from a board or a kept Tree, with the proofs.  solver=False: that search,
@@ -27,14 +26,11 @@ import numpy as np
 
 import fpu_model as F
 import oracle_lib as O
-from forced_playouts_model import PSCALE, distribution, is_forced, prune
-from hash_eval import hash_eval_batch
-from leaf_parallel_model import EXPAND, REEXPAND, ROOTPASS, TERMINAL, Node, Result, _expand, _select
-from tree_reuse_model import Tree, advance
+import tree_model
+from forced_playouts_model import PSCALE, distribution, prune
+from tree_model import PROVEN, advance  # noqa: F401  (PROVEN: the kind of a descent that ended on a proven node)
 
-f32 = np.float32
 NONE, WIN, LOSS, DRAW = 0, 1, 2, 3
-PROVEN = 8                                                         # the kind of a descent that ended on a proven node
 VALUE = {WIN: 1, LOSS: -1, DRAW: 0.0001}                           # python numbers, as Node.tv
 
 MUTANTS = {
@@ -92,124 +88,11 @@ def propagate(tree, nodes, mutant=None):
     return proven, root
 
 
-def search(root_or_board, player, budget, solver=True, r=0.0, r_root=None, forced=0.0, pbits=10, vbits=11, noise=None, eps=0.25,
-           cpuct=1.0, flags=0, mutant=None, pscale=PSCALE):
-    """-> Result with fpu_model.search's fields and root_proven (int), child_proven int8 [A] (by action; 0 where the child does
-    not exist), proven_nodes, proven_descents, proven_roots (of this call) and ended (the kind of every descent)."""
+def search(root_or_board, player, budget, solver=True, pbits=10, vbits=11, mutant=None, pscale=PSCALE, **options):
+    """tree_model.search at K = 1 with the proofs -> Result; r, r_root, forced: its keywords."""
     assert mutant is None or mutant in MUTANTS
-    r = float(r)
-    r_root = r if r_root is None else float(r_root)
-
-    def evaluator(b):
-        pol, val = hash_eval_batch(b, pbits, vbits)
-        return pol * f32(pscale), val
-
-    cpuct = f32(cpuct)
-    if isinstance(root_or_board, Tree):
-        tree = root_or_board
-        root = tree.root
-        assert root.player == int(player)
-        if noise is not None and any(float(noise[e.action]) != 0.0 for e in root.edges):
-            keep = f32(1.0 - eps)
-            for e in root.edges:
-                e.P = f32(float(f32(keep * e.P)) + eps * float(noise[e.action]))
-    else:
-        board = np.array(root_or_board, np.int8)
-        root = Node(board, int(player))
-        _expand(root, evaluator(board[None])[0][0], flags, noise, eps)      # root call, value discarded (mcts.py:295)
-        tree = Tree(root)
-    if not hasattr(tree, "proven"):
-        tree.proven = {}
-    tree.log = getattr(tree, "log", [])                            # (node, status, children) of every node proven by propagation
-    A = root.board.size
-    evals = n_proven = n_descents = n_roots = 0
-    failed = False
-    ended = []
-
-    def choose(node):
-        if forced and node is root:
-            S = sum(e.N for e in root.edges)
-            owed = [x for x in root.edges if is_forced(forced, x.P, x.N, S)]
-            if owed:
-                return owed[0]
-        if not r:
-            return _select(node, {}, cpuct)
-        return F.select(node, {}, cpuct, r_root if node is root else r)
-
-    while tree.n < budget and not failed:
-        node, path, nodes = root, [], []
-        while True:
-            if node.terminal:
-                kind = TERMINAL
-                break
-            if solver and status(tree, node) != NONE and (node is not root or mutant == "root_terminal"):
-                kind = PROVEN
-                break
-            if not node.edges:
-                kind = ROOTPASS if node is root else REEXPAND
-                break
-            e = choose(node)
-            if e is None:
-                failed = True
-                break
-            path.append(e)
-            nodes.append(node)
-            if e.child is None:
-                kind = EXPAND
-                break
-            node = e.child
-        if failed:
-            break
-        ended.append(kind)
-        exact = kind in (TERMINAL, PROVEN)
-        if kind == TERMINAL:
-            v, v_is_py = node.tv, True
-        elif kind == PROVEN:
-            v, v_is_py = VALUE[status(tree, node)], True
-            n_descents += 1
-        else:
-            if kind == EXPAND:
-                par, e = nodes[-1], path[-1]
-                b = par.board.copy()
-                b.flat[e.action] = par.player                        # a legal move of the parent always places (copied boards)
-                node = Node(b, -par.player)
-                e.child = node
-            P, V = evaluator(node.board[None])
-            evals += 1
-            _expand(node, P[0], flags)
-            v, v_is_py = f32(V[0]), False
-            exact = kind == EXPAND and node.terminal
-        depth = len(path)
-        v32 = f32(v)
-        for i, e in enumerate(path):
-            sv = -v32 if (depth - (i + 1)) & 1 else v32
-            e.N += 1
-            e.W = f32(e.W + sv)
-        tree.n += 1
-        if tree.is_py and v_is_py and depth == 0:
-            tree.w_py += v
-        else:
-            sv = -v32 if depth & 1 else v32
-            base = f32(tree.w_py) if tree.is_py else tree.wf
-            tree.wf = f32(base + sv)
-            tree.is_py = False
-        if solver and exact:
-            a, b = propagate(tree, nodes, mutant)
-            n_proven += a
-            n_roots += b
-    res = Result()
-    res.counts = np.zeros(A, np.int32)
-    res.child_w = np.zeros(A, np.float32)
-    res.child_p = np.zeros(A, np.float32)
-    res.child_proven = np.zeros(A, np.int8)
-    for e in root.edges:
-        res.counts[e.action], res.child_w[e.action], res.child_p[e.action] = e.N, e.W, e.P
-        if solver and e.child is not None:
-            res.child_proven[e.action] = status(tree, e.child)
-    res.root_proven = status(tree, root) if solver else NONE
-    res.root_visits, res.root_w, res.evals, res.tree, res.failed = tree.n, tree.w, evals, tree, failed
-    res.proven_nodes, res.proven_descents, res.proven_roots, res.ended = n_proven, n_descents, n_roots, ended
-    return res
+    return tree_model.search(root_or_board, player, budget, 1, pbits, vbits, solver=solver, pscale=pscale,
+                             mutant=mutant and "solver." + mutant, **options)
 
 
 def root_policy(res, forced=0.0, tzero=False):

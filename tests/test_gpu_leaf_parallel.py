@@ -4,9 +4,9 @@ rows limit, inactive games), the sticky error, the refused combinations, and the
 import numpy as np
 import pytest
 
-import leaf_parallel_model as M
+import tree_model as M
 from hash_eval import hash_eval_batch, hash_eval_torch, planes_to_boards
-from test_leaf_parallel_model import dirichlet_noise, random_root
+from tree_model import dirichlet_noise, random_root
 
 pytestmark = pytest.mark.gpu
 PB, VB = 10, 11

@@ -15,7 +15,8 @@ import pytest
 import leaf_parallel_model as M
 import oracle_lib as O
 from hash_eval import hash_eval_batch, hash_eval_torch, planes_to_boards
-from test_leaf_parallel_model import dirichlet_noise, one_move_root, pass_root, random_root, terminal_root
+from test_leaf_parallel_model import one_move_root, pass_root, terminal_root
+from tree_model import dirichlet_noise, random_root
 
 pytestmark = pytest.mark.gpu
 PB, VB = 10, 11

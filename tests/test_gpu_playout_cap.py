@@ -5,9 +5,9 @@ the fully searched plies with the pi of a full search of that position alone."""
 import numpy as np
 import pytest
 
-import leaf_parallel_model as M
 import oracle_lib as O
 import philox_ref as P
+import tree_model as M
 from hash_eval import hash_eval_torch
 
 pytestmark = pytest.mark.gpu

@@ -14,8 +14,8 @@ import sys
 import numpy as np
 import pytest
 
-import leaf_parallel_model as M
 import oracle_lib as O
+import tree_model as M
 from hash_eval import hash_eval_torch
 
 pytestmark = pytest.mark.gpu

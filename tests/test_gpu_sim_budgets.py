@@ -12,12 +12,12 @@ import functools
 import numpy as np
 import pytest
 
-import leaf_parallel_model as M
 import oracle_lib as O
 import philox_ref as P
+import tree_model as M
 from hash_eval import hash_eval_torch
 from test_gpu_leaf_parallel_trace import COUNTERS, PB, VB, Tracer, differences, observables, root_observables
-from test_leaf_parallel_model import dirichlet_noise, random_root
+from tree_model import dirichlet_noise, random_root
 
 pytestmark = pytest.mark.gpu
 ROOT_KEYS = ("counts", "child_w", "child_p", "visits", "root_w")

@@ -19,10 +19,10 @@ import numpy as np
 import pytest
 
 import forced_playouts_model as FM
-import leaf_parallel_model as LM
 import solver_model as SM
+import tree_model as LM
 from hash_eval import hash_eval_torch
-from test_leaf_parallel_model import random_root
+from tree_model import random_root
 
 pytestmark = pytest.mark.gpu
 READERS = ("forced_descents", "solver_counters", "shared_counters", "shared_counters_ex")    # every reader but status()

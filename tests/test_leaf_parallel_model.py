@@ -5,26 +5,8 @@ import pytest
 
 import oracle_lib as O
 import leaf_parallel_model as M
-
-
-def random_root(R, C, plies, seed, flags=0):
-    """A position after `plies` random legal moves from the empty board (fewer when the game ends first), side to move."""
-    rng = np.random.default_rng(seed)
-    board, player = np.zeros((1, R, C), np.int8), np.ones(1, np.int8)
-    for _ in range(plies):
-        m = O.valid_mask(board, player, flags)[0]
-        if not m.any() or O.game_ended(board, player, flags)[0] != 0:
-            break
-        board, player, _ = O.next_state(board, player, np.array([rng.choice(np.flatnonzero(m))], np.int32), flags)
-    return board[0], int(player[0])
-
-
-def dirichlet_noise(board, player, seed, alpha=0.3, flags=0):
-    legal = np.flatnonzero(O.valid_mask(board[None], [player], flags)[0])
-    nz = np.zeros(board.size)
-    if len(legal):
-        nz[legal] = np.random.default_rng(seed).dirichlet([alpha] * len(legal))
-    return nz
+import tree_model
+from tree_model import dirichlet_noise, random_root
 
 
 CASES = [(3, 3, 0, 30), (3, 3, 2, 40), (6, 6, 4, 120), (8, 8, 6, 160), (16, 12, 10, 48)]
@@ -51,7 +33,7 @@ def uniform_policy(monkeypatch, value=0.0):
         b = np.asarray(boards)
         G, A = b.shape[0], b[0].size
         return np.full((G, A), 1.0 / 64, np.float32), np.full(G, value, np.float32)
-    monkeypatch.setattr(M, "hash_eval_batch", ev)
+    monkeypatch.setattr(tree_model, "hash_eval_batch", ev)
 
 
 def test_fresh_root_k_children_visited_once_in_order(monkeypatch):

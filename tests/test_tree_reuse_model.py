@@ -12,7 +12,7 @@ import leaf_parallel_model as L
 import oracle_lib as O
 import tree_reuse_cases as Cs
 import tree_reuse_model as T
-from test_leaf_parallel_model import dirichlet_noise, random_root
+from tree_model import dirichlet_noise, random_root
 
 
 @pytest.mark.parametrize("R,C,plies,sims", [(3, 3, 2, 40), (1, 6, 1, 30), (5, 7, 6, 80), (9, 12, 10, 40)])

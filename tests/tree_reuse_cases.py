@@ -18,7 +18,7 @@ import numpy as np
 
 import oracle_lib as O
 import tree_reuse_model as T
-from test_leaf_parallel_model import dirichlet_noise, random_root
+from tree_model import dirichlet_noise, random_root
 
 KINDS8 = ("best", "best", "best", "once", "unvisited", "none", "oob", "terminal")
 
