@@ -175,11 +175,58 @@ extern "C" {
                               float64, sigma64(x) = (f64(c_visit) + f64(maxN)) * f64(c_scale) * x, cq = f64(W) / f64(N) of a
                               visited child, and for an unvisited one SW / SN over the visited children, SW = f64(sum of
                               (int64)(f64(W) * 2^32)) * 2^-32 (each term truncated toward zero: no order dependence), 0 when
-                              none is visited.  The paper's v_mix needs the root's own network value, which the tree does not
-                              keep: a follow-up.  A root without children keeps the uniform row.  yy_mcts_root_counts stays raw.
+                              none is visited (YY_FLAG_GUMBEL_INTERIOR completes with the paper's v_mix instead).  A root
+                              without children keeps the uniform row.  yy_mcts_root_counts stays raw.
                               The move: yy_mcts_root_gumbel_action -- among the children with the largest visit count the
                               largest f32(s0 + sigma), the lowest edge on ties -- which yy_mcts_step_selfplay plays at every ply
                               (no temperature rule, no move draw).  Flag clear: every kernel does what it did without it. */
+
+#define YY_FLAG_GUMBEL_INTERIOR 1024u /* the rest of Gumbel AlphaZero (Danihelka et al. 2022, section 5 and appendix D): v_mix
+                              and completed-Q selection below the root.  Only with YY_FLAG_GUMBEL_ROOT, and not with
+                              YY_FLAG_FPU_REDUCTION (no PUCT score is left for it to act on): create returns YY_E_UNSUPPORTED.  It goes
+                              with and is refused with whatever YY_FLAG_GUMBEL_ROOT is.  Flag clear: every kernel does what it
+                              did without it, the plain Gumbel root search included.  With it:
+                              (1) The root record keeps the evaluator's value of the root position, as every other expanded
+                              node's does; nothing is backed up.  The root expansion is yy_mcts_expand_root_value
+                              (yy_mcts_expand_root returns YY_E_UNSUPPORTED); yy_mcts_step_selfplay reads the value of the root's
+                              row.  A NaN value fails the game like any other expansion's.
+                              (2) The improved policy of a node with k > 0 edges, from its own evaluator value vhat (f32) and
+                              per edge the stored prior P (f32), visits N and value sum W (f32).  All products, sums and
+                              quotients below are the correctly rounded float64 ones, one rounding each, never contracted:
+                                p(a)  = (uint64)(max(f64(P) * 2^40, 0))             (truncated; the prior in units of 2^-40)
+                                q(a)  = f64(W) / f64(N)                             (N > 0)
+                                S     = sum of N,  maxN = largest N                 (integers)
+                                SPv   = sum over N > 0 of p(a)                      (integer)
+                                SPQ   = sum over N > 0 of (int64)(f64(p(a)) * q(a)) (integer, each term truncated toward zero;
+                                                                                      a NaN or infinite product adds 0)
+                                v_mix = f64(vhat)                                             if S == 0
+                                v_mix = (f64(vhat) + f64(S) * wq) / f64(1 + S),  wq = f64(SPQ) / f64(SPv), 0 when SPv == 0
+                                cq(a) = q(a) if N > 0, else v_mix
+                                x(a)  = ((f64(c_visit) + f64(maxN)) * f64(c_scale)) * cq(a)   (sigma of the root's target; no
+                                                                                               min-max rescaling of q)
+                                xm    = the largest x(a) over the edges with p(a) > 0 (NaNs passed over)
+                                t(a)  = (uint64)((f64(p(a)) * E(x(a) + (-xm))) * 2^12)         (truncated; 0 where p(a) == 0)
+                                Z     = sum of t(a)                                            (integer, below 2^53)
+                                pi'(a) = f64(t(a)) / f64(Z)
+                              so no sum depends on the order of the children, no log is taken, and with finite value sums the
+                              edge that sets xm has E = 1, hence Z > 0.  Every p(a) == 0: t(a) = 1 for every edge (the uniform
+                              row).  An edge whose x(a) - xm is a NaN (a NaN or infinite value sum) carries no term, its pi'
+                              and score are NaN; when that leaves Z == 0, every pi' and every score is the NaN 0 / 0.
+                              vhat is taken with the sign it is stored with -- the evaluator's value for the node's side to
+                              move -- while W / N of an edge is in the tree's inherited convention (the backed-up value as the
+                              CHILD's side to move sees it, mcts.py:406-412): v_mix mixes the two as they stand.
+                              E(x), x <= 0, is the project's own exponential: 0 below -708; else n = rint(x * log2e) (half to even),
+                              r = (x + (-(n * ln2_hi))) + (-(n * ln2_lo)), log2e = 0x1.71547652b82fep+0, ln2_hi = 0x1.62e42feep-1,
+                              ln2_lo = 0x1.a39ef35793c76p-33; p = 1/13!, then p = p * r + 1/i! for i = 12 .. 0 (the constants
+                              are the float64 quotients 1.0 / i!; multiply and add rounded separately); E = p * 2^n, exact.
+                              Within 1e-14 relative of exp (the Taylor remainder on |r| <= 0.3466 is below 2^-53).
+                              (3) Policy target: yy_mcts_root_policy and the example record of yy_mcts_step_selfplay return pi'
+                              of the root in place of the softmax above.
+                              (4) Selection at depth > 0 of a descent: the child of the largest
+                                f64(pi'(a)) + (-(f64(N(a)) / f64(1 + S)))
+                              compared as float64, the lowest edge on ties; a NaN score is never the largest, and the game fails
+                              when every score is NaN.  PUCT is not consulted below the root.  Depth 0 (sequential halving), the
+                              path, the counters, expansion and backup are unchanged; so is yy_mcts_root_gumbel_action. */
 
 typedef void *yy_stream_t;
 
@@ -325,6 +372,10 @@ int yy_mcts_begin(yy_mcts *ctx, const int8_t *boards, const int8_t *root_players
  * A game whose noise row is all zero keeps its raw priors (add_exploration_noise=False). */
 int yy_mcts_expand_root(yy_mcts *ctx, const float *policy, const double *noise, double eps,
                         yy_stream_t stream);
+/* The same root expansion with the evaluator's value of call #0, float32 [G] (row g*K with K leaves per step): a context with
+ * YY_FLAG_GUMBEL_INTERIOR keeps it in the root record (and needs this form); any other context discards it as above. */
+int yy_mcts_expand_root_value(yy_mcts *ctx, const float *policy, const float *value, const double *noise, double eps,
+                              yy_stream_t stream);
 
 /* Selection + leaf state (mcts.py:356-399 up to the predict call): PUCT descent in float32
  * (mcts.py:97-145), place-if-legal, terminal test and legal mask of the new position, and the 5
@@ -356,6 +407,12 @@ int yy_mcts_root_stats(yy_mcts *ctx, int32_t *visits, double *value_sum, yy_stre
 /* The board each game's root refers to after the search, int8 [G,R,C]: unchanged in copied mode,
  * the mutated caller board in aliased mode. */
 int yy_mcts_get_boards(yy_mcts *ctx, int8_t *boards, yy_stream_t stream);
+
+/* Test and tool support only, no part of a search: the trees as they stand.  caps (HOST int64 [2], or NULL) = {node records, edge records} per game;
+ * nodes uint32 [G, caps[0], 4] = per node {first edge, k | flags << 16 | player << 24, terminal or proven value (f32 bits), the
+ * evaluator's value (f32 bits)}; edges uint32 [G, caps[1], 4] = per edge {prior (f32 bits), N, W (f32 bits), child | action <<
+ * 24; child 0xFFFFFF = none}; sizes int32 [G, 2] = {nodes, edges} in use.  Device pointers, each may be NULL; async copies. */
+int yy_mcts_tree(yy_mcts *ctx, uint32_t *nodes, uint32_t *edges, int32_t *sizes, int64_t *caps, yy_stream_t stream);
 
 /* sync. Host outputs: number of games that failed in ANY search since the previous status call -- arena overflow,
  * NaN priors or a NaN value from the evaluator; such a game stops searching, and the flag is sticky: yy_mcts_begin

@@ -131,6 +131,11 @@ def parse_args(argv=None):
                    help="c_visit of --gumbel-root's sigma (default 50)")
     p.add_argument("--gumbel-c-scale", type=float, default=None, metavar="Y",
                    help="c_scale of --gumbel-root's sigma (default 1.0)")
+    p.add_argument("--gumbel-interior", action="store_true",
+                   help="self-play and train, with --gumbel-root: the rest of Gumbel AlphaZero -- the root keeps its network value, "
+                        "unvisited children are completed with v_mix in the policy target, and a descent below the root takes the "
+                        "child of largest improved-policy share less visit share instead of the PUCT choice (default off; changes "
+                        "which moves are picked; not with --fpu-reduction)")
     return p.parse_args(argv)
 
 
@@ -139,7 +144,8 @@ def parse_args(argv=None):
 # flags there; --leaves-per-step > 1 has always refused them in train mode too and still does: the second call.
 _SEARCH = ("num_simulations", "leaves_per_step", "fast_simulations", "full_search_probability", "tree_reuse", "free_running",
            "evaluation_symmetry", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
-           "shared_evaluations_replace", "solver", "gumbel_root", "gumbel_c_visit", "gumbel_c_scale")
+           "shared_evaluations_replace", "solver", "gumbel_root", "gumbel_c_visit", "gumbel_c_scale",
+           "gumbel_interior")
 HANDED = {"self-play": [_SEARCH + ("board_semantics", "reference_quirks")],
           "train": [_SEARCH, ("leaves_per_step", "board_semantics", "reference_quirks")],
           "evaluate": [("leaves_per_step", "tree_reuse", "fpu_reduction", "fpu_reduction_root", "solver")]}

@@ -21,6 +21,7 @@ FLAG_FORCED_PLAYOUTS = 64
 FLAG_FPU_REDUCTION = 128
 FLAG_SOLVER = 256
 FLAG_GUMBEL_ROOT = 512
+FLAG_GUMBEL_INTERIOR = 1024
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -90,6 +91,7 @@ _SIGS = {
     "yy_mcts_advance": [_vp, _vp, _vp, _vp],
     "yy_mcts_begin": [_vp, _vp, _vp, _vp, _vp, _vp],
     "yy_mcts_expand_root": [_vp, _vp, _vp, C.c_double, _vp],
+    "yy_mcts_expand_root_value": [_vp, _vp, _vp, _vp, C.c_double, _vp],
     "yy_mcts_select": [_vp, _vp, _vp, _vp],
     "yy_mcts_expand_backup": [_vp, _vp, _vp, _vp],
     "yy_mcts_step": [_vp, _vp, _vp, _vp, _vp, _vp],
@@ -97,6 +99,7 @@ _SIGS = {
     "yy_mcts_root_policy": [_vp, C.c_int, _vp, _vp],
     "yy_mcts_root_stats": [_vp, _vp, _vp, _vp],
     "yy_mcts_get_boards": [_vp, _vp, _vp],
+    "yy_mcts_tree": [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp],
     "yy_mcts_status": [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)],
     "yy_mcts_reset_counters": [_vp, _vp],
     "yy_mcts_forced_descents": [_vp, C.POINTER(C.c_uint64)],

@@ -362,8 +362,8 @@ class AlphaZero:
                  concurrent_games=4096, device=None, lr=0.001, batch_size=64, leaves_per_step=1, fast_simulations=None,
                  full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
-        """gumbel_root / gumbel_c_visit / gumbel_c_scale: the Gumbel root search (options.SearchOptions) in the loop's self-play;
+                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale / gumbel_interior: the Gumbel root search (options.SearchOptions) in the loop's self-play;
         the arena does not take it.
         solver: the MCTS-Solver (options.SearchOptions) in the loop's self-play and, as a playing-strength parameter, its arena.
         shared_evaluations_replace: the loop's self-play uses the replacing table (options.SearchOptions).
@@ -382,7 +382,7 @@ class AlphaZero:
                                        fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root,
                                        shared_evaluations=shared_evaluations, shared_evaluations_replace=shared_evaluations_replace,
                                        solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit,
-                                       gumbel_c_scale=gumbel_c_scale)
+                                       gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         self.game, self.model_dir, self.data_dir = game, model_dir, data_dir
         self.num_iterations, self.num_episodes, self.num_simulations = num_iterations, num_episodes, num_simulations
         self.num_epochs, self.temperature_threshold, self.update_threshold = num_epochs, temperature_threshold, update_threshold

@@ -968,6 +968,32 @@ __device__ __forceinline__ void do_select(const MctsDev &d, const int g, float *
             if (best == BEST_NONE) { kind = K_NONE; if (lane == 0) fail_game(st); break; }  // every score NaN
             w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
             s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
+        } else if (d.g_interior) {
+            // Gumbel search below the root (YY_FLAG_GUMBEL_INTERIOR, include/yy_engine.h): the child of the largest
+            // pi'(a) - N(a) / (1 + S), the lowest edge on ties; PUCT and first-play urgency are not consulted.  Wave-uniform
+            // branch on the flag word, like the two above; the node's edges are held in registers for the two passes
+            uint4 e[NW];
+#pragma unroll
+            for (int i = 0; i < NW; i++) e[i] = (i * 64 + lane < k) ? edges[first + i * 64 + lane] : make_uint4(0u, 0u, 0u, 0u);
+            uint64_t t[NW];
+            const GumbelNode gn = gumbel_improved<NW>(d, e, k, rflf(__uint_as_float(hdr.w)), t);
+            const double zf = (double)gn.Z, s1 = (double)(1 + gn.S);
+            uint64_t bk = 0;
+            uint32_t bw = 0, bn = 0;
+            int bi = BEST_NONE;
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                if (i * 64 + lane < k && t[i] != GI_NAN) {
+                    const uint64_t key = f64_key(__dadd_rn(__ddiv_rn((double)t[i], zf), -__ddiv_rn((double)(int)e[i].y, s1)));
+                    if (key > bk) { bk = key; bi = i * 64 + lane; bw = e[i].w; bn = e[i].y; }   // strict >: lowest edge of a lane
+                }
+            }
+            const uint64_t mxk = wave_max_u64(bk);
+            const uint32_t mi = wave_umin((bk == mxk && bi != BEST_NONE) ? (uint32_t)bi : 0xFFFFFFFFu);
+            if (mxk == 0ull || mi == 0xFFFFFFFFu) { kind = K_NONE; if (lane == 0) fail_game(st); break; }   // every score NaN
+            best = (int)mi;
+            w = (uint32_t)__builtin_amdgcn_readlane((int)bw, best & 63);
+            s_carry = (int)__builtin_amdgcn_readlane((int)bn, best & 63) - 1;
         } else {
             const float sq = d.sqrt_tab[min(S, d.sqrt_n - 1)];   // f32(math.sqrt(sum_visits))
             // first-play urgency: one more pass over the node's edges for the sums behind the q of its unvisited children
@@ -1151,7 +1177,8 @@ __device__ __forceinline__ void do_expand_backup(const MctsDev &d, const int g, 
         // the root call of mcts.py:288 looks nothing up, and its value is discarded: yy_mcts_expand_root is not given it
         const bool root = kind == K_ROOTINIT;
         const int src = (root || !(d.ec.meta || d.bk.meta || d.sh.meta)) ? SRC_NONE : rfl(st->leaf_src);
-        const LeafEval ev = leaf_eval<NW>(d, g, src, policy, root ? nullptr : value);
+        // YY_FLAG_GUMBEL_INTERIOR: the root keeps the evaluator's value of its position in its record, like every other expansion
+        const LeafEval ev = leaf_eval<NW>(d, g, src, policy, (root && !d.g_interior) ? nullptr : value);
         v = ev.v;
         const bool hold = d.reuse && !root;   // a pass node keeps its value; a pass root that of its first simulation
         if (!expand_leaf<NW>(d, st, g, &st->leaf, path, ev.prow, v, hold, d.aliased != 0u, root ? noise : nullptr, eps)) {
@@ -1677,6 +1704,10 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
         if (!(cfg->gumbel_c_scale > 0.0f && cfg->gumbel_c_scale < INFINITY))
             return set_err(YY_E_INVALID, "YY_FLAG_GUMBEL_ROOT: gumbel_c_scale must be positive and finite%s%s");
     }
+    if ((cfg->flags & YY_FLAG_GUMBEL_INTERIOR) && !(cfg->flags & YY_FLAG_GUMBEL_ROOT))
+        return set_err(YY_E_UNSUPPORTED, "YY_FLAG_GUMBEL_INTERIOR needs YY_FLAG_GUMBEL_ROOT (it completes the Gumbel root search below the root)%s%s");
+    if ((cfg->flags & YY_FLAG_GUMBEL_INTERIOR) && (cfg->flags & YY_FLAG_FPU_REDUCTION))
+        return set_err(YY_E_UNSUPPORTED, "YY_FLAG_GUMBEL_INTERIOR does not go with YY_FLAG_FPU_REDUCTION (no PUCT score is left below the root, and the root never had one)%s%s");
     if (cfg->leaves_per_step < 0) return set_err(YY_E_INVALID, "leaves_per_step < 0%s%s");
     if (cfg->leaves_per_step > 64) return set_err(YY_E_UNSUPPORTED, "leaves_per_step > 64%s%s");
     if (cfg->leaves_per_step > 1) {
@@ -1706,6 +1737,7 @@ extern "C" int yy_mcts_create(const yy_mcts_config *cfg, yy_mcts **out) {
     d.gumbel = (cfg->flags & YY_FLAG_GUMBEL_ROOT) ? (uint32_t)cfg->gumbel_root : 0u;
     d.g_cvisit = d.gumbel ? cfg->gumbel_c_visit : 0.0f;
     d.g_cscale = d.gumbel ? cfg->gumbel_c_scale : 0.0f;
+    d.g_interior = (cfg->flags & YY_FLAG_GUMBEL_INTERIOR) ? 1u : 0u;
     m.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     // virtual visits: a sum of child counts reaches max_sims - 1 + K - 1 within a step
     d.sqrt_n = cfg->max_sims + 2 + (m.K > 1 ? m.K : 0);
@@ -1881,8 +1913,20 @@ static int launch_mcts(yy_mcts *c, int backup, int sel, const float *policy, con
 
 extern "C" int yy_mcts_expand_root(yy_mcts *c, const float *policy, const double *noise, double eps, yy_stream_t s) {
     if (!c || !policy) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (c->dev.g_interior)
+        return set_err(YY_E_UNSUPPORTED, "yy_mcts_expand_root: YY_FLAG_GUMBEL_INTERIOR keeps the root's value (yy_mcts_expand_root_value)%s%s");
     if (c->pending != 2) return set_err(YY_E_STATE, "yy_mcts_expand_root without yy_mcts_begin%s%s");
     int e = launch_mcts(c, 1, 0, policy, nullptr, noise, eps, nullptr, nullptr, s);
+    if (e == YY_OK) c->pending = 0;
+    return e;
+}
+
+extern "C" int yy_mcts_expand_root_value(yy_mcts *c, const float *policy, const float *value, const double *noise, double eps,
+                                         yy_stream_t s) {
+    if (!c || !policy || !value) return set_err(YY_E_INVALID, "null pointer%s%s");
+    if (c->pending != 2) return set_err(YY_E_STATE, "yy_mcts_expand_root_value without yy_mcts_begin%s%s");
+    // without the flag the kernel discards the value, as yy_mcts_expand_root does
+    int e = launch_mcts(c, 1, 0, policy, value, noise, eps, nullptr, nullptr, s);
     if (e == YY_OK) c->pending = 0;
     return e;
 }
@@ -1936,6 +1980,27 @@ extern "C" int yy_mcts_root_stats(yy_mcts *c, int32_t *visits, double *wsum, yy_
     if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
     hipLaunchKernelGGL(k_root_stats, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, c->dev, visits, wsum);
     HIP_TRY(hipGetLastError());
+    return YY_OK;
+}
+
+__global__ void k_tree_sizes(MctsDev d, int32_t *sizes) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G) return;
+    sizes[2 * g] = d.state[g].n_nodes;
+    sizes[2 * g + 1] = d.state[g].n_edges;
+}
+
+extern "C" int yy_mcts_tree(yy_mcts *c, uint32_t *nodes, uint32_t *edges, int32_t *sizes, int64_t *caps, yy_stream_t s) {
+    if (!c) return set_err(YY_E_INVALID, "null pointer%s%s");
+    const MctsDev &d = c->dev;
+    if (caps) { caps[0] = d.node_cap; caps[1] = d.edge_cap; }
+    const size_t G = (size_t)c->cfg.G;
+    if (nodes) HIP_TRY(hipMemcpyAsync(nodes, d.nodes, G * d.node_cap * sizeof(uint4), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    if (edges) HIP_TRY(hipMemcpyAsync(edges, d.edges, G * d.edge_cap * sizeof(uint4), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    if (sizes) {
+        hipLaunchKernelGGL(k_tree_sizes, dim3((c->cfg.G + 255) / 256), dim3(256), 0, (hipStream_t)s, d, sizes);
+        HIP_TRY(hipGetLastError());
+    }
     return YY_OK;
 }
 

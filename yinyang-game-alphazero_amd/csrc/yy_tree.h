@@ -327,6 +327,10 @@ struct MctsDev {
     float g_cvisit, g_cscale;
     const float *g_rows;
     float *g_s0;
+    // Gumbel search below the root (YY_FLAG_GUMBEL_INTERIOR, only with YY_FLAG_GUMBEL_ROOT): the root record keeps the evaluator's
+    // value, unvisited children are completed with v_mix and a descent below the root takes the child of the largest
+    // pi'(a) - N(a) / (1 + S); 0: off, every kernel does what it did without it
+    uint32_t g_interior;
 };
 
 // ---- shared evaluation table, replacing mode: the claim word and the sweep state (yy_engine.hip, yy_shared_table.hip)
@@ -610,11 +614,118 @@ template <int NW> __device__ __forceinline__ int gumbel_winner(const MctsDev &d,
     return (int)(rfl(edges[first + j].w) >> 24);
 }
 
+// ---- Gumbel search below the root (YY_FLAG_GUMBEL_INTERIOR): v_mix, completed Q and the improved policy pi', in arithmetic that a
+// numpy restatement reproduces bit for bit (include/yy_engine.h): no log, the project's own exponential, integer sums.
+// E(x) = exp(x) for x <= 0: correctly rounded float64 products and sums only (no contraction), an exact scaling by 2^n.
+__device__ __forceinline__ double gumbel_exp(const double x) {
+    if (x < -708.0) return 0.0;
+    const double n = __builtin_rint(__dmul_rn(x, 0x1.71547652b82fep+0));        // log2(e)
+    const double r = __dadd_rn(__dadd_rn(x, -__dmul_rn(n, 0x1.62e42feep-1)), -__dmul_rn(n, 0x1.a39ef35793c76p-33));   // ln2 hi, lo
+    double p = 1.0 / 6227020800.0;                                              // Taylor, degree 13, Horner
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 479001600.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 39916800.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 3628800.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 362880.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 40320.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 5040.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 720.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 120.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 24.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0 / 6.0);
+    p = __dadd_rn(__dmul_rn(p, r), 0.5);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0);
+    p = __dadd_rn(__dmul_rn(p, r), 1.0);
+    // n in -1022 .. 0: 2^n is a normal number and the product is exact
+    return __dmul_rn(p, __longlong_as_double((long long)((int)n + 1023) << 52));
+}
+// float64 -> unsigned key with the same order; a NaN gets key 0, every other value a key > 0
+__device__ __forceinline__ uint64_t f64_key(const double f) {
+    const uint64_t u = (uint64_t)__double_as_longlong(f);
+    return (f != f) ? 0ull : (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+#define GI_NAN 0xFFFFFFFFFFFFFFFFull   // the term of an edge whose completed q is a NaN
+// What the improved policy of a node needs, from its k > 0 edges e[] (edge i*64 + lane in e[i], zero past the k-th) and its own
+// evaluator value vhat: S = the children's visits, v_mix, sigma's scale and maximum, the terms t[] (gumbel_term) and their sum
+// Z: pi'(a) = f64(t(a)) / f64(Z).  The sums are integers (P and P * q in units of 2^-40, the terms in units of 2^-52), so that
+// they do not depend on which lane holds which child.  Only the edges and the terms are kept per edge; priors and sigmas are
+// recomputed where they are read.  One copy: the descent below the root (do_select) and the root's policy target read it.
+struct GumbelNode { int S; bool anyp; double vmix, scale, xm; uint64_t Z; };
+// the prior of an edge in units of 2^-40 (truncated), and sigma of its completed q
+// (a negative prior counts as 0, as a NaN would: expansion refuses NaN priors)
+__device__ __forceinline__ uint64_t gumbel_prior(const uint4 e) {
+    return (uint64_t)fmax(__dmul_rn((double)__uint_as_float(e.x), 1099511627776.0), 0.0);
+}
+__device__ __forceinline__ double gumbel_sigma(const GumbelNode &n, const uint4 e) {
+    return __dmul_rn(n.scale, ((int)e.y > 0) ? __ddiv_rn((double)__uint_as_float(e.z), (double)(int)e.y) : n.vmix);
+}
+// t(a) in units of 2^-52: GI_NAN for an edge whose sigma is a NaN against the maximum, 1 for every edge when every prior is 0
+__device__ __forceinline__ uint64_t gumbel_term(const GumbelNode &n, const uint4 e) {
+    if (!n.anyp) return 1ull;
+    const uint64_t p = gumbel_prior(e);
+    if (!p) return 0ull;
+    const double a = __dadd_rn(gumbel_sigma(n, e), -n.xm);                      // <= 0 wherever a term is taken
+    return (a != a) ? GI_NAN : (uint64_t)__dmul_rn(__dmul_rn((double)p, gumbel_exp(a)), 4096.0);
+}
+template <int NW>
+__device__ __forceinline__ GumbelNode gumbel_improved(const MctsDev &d, const uint4 (&e)[NW], const int k, const float vhat,
+                                                      uint64_t (&t)[NW]) {
+    int mx = 0, S = 0;
+    uint64_t spv = 0;
+    long long spq = 0;
+    bool anyp = false;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        const int n = (int)e[i].y;
+        const uint64_t p = gumbel_prior(e[i]);
+        anyp |= p != 0ull;
+        mx = max(mx, n);
+        if (n > 0) {
+            S += n;
+            spv += p;
+            const double pq = __dmul_rn((double)p, __ddiv_rn((double)__uint_as_float(e[i].z), (double)n));
+            spq += (fabs(pq) < 0x1p62) ? (long long)pq : 0ll;                   // a NaN or infinite value sum adds nothing here
+        }
+    }
+    mx = wave_max_i32(mx);
+    S = wave_sum(S);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        spv += __shfl_xor((unsigned long long)spv, o, 64);
+        spq += __shfl_xor(spq, o, 64);
+    }
+    GumbelNode r;
+    r.S = S;
+    r.anyp = __ballot(anyp) != 0;                                               // false: every prior 0, the uniform row
+    r.vmix = (double)vhat;
+    if (S > 0) {
+        const double wq = spv ? __ddiv_rn((double)spq, (double)spv) : 0.0;       // the prior-weighted mean of the visited children
+        r.vmix = __ddiv_rn(__dadd_rn((double)vhat, __dmul_rn((double)S, wq)), (double)(1 + S));
+    }
+    r.scale = __dmul_rn(__dadd_rn((double)d.g_cvisit, (double)mx), (double)d.g_cscale);
+    double xm = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NW; i++)
+        if (gumbel_prior(e[i])) xm = fmax(xm, gumbel_sigma(r, e[i]));           // sigma_max: over the edges that can carry mass
+    r.xm = sp::wave_max_f64(xm);
+    uint64_t z = 0;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        t[i] = (i * 64 + lane_id() < k) ? gumbel_term(r, e[i]) : 0ull;
+        if (t[i] != GI_NAN) z += t[i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor((unsigned long long)z, o, 64);
+    r.Z = z;
+    return r;
+}
+
 // The policy target of the Gumbel root search into pi[0 .. A): pi' = softmax(log P + sigma64(cq)) over the k > 0 root edges
 // of an active game, in float64 (include/yy_engine.h); an unvisited child is completed with the visited children's SW / SN,
-// SW summed in units of 2^-32 like first-play urgency's, so that it does not depend on which lane holds which child.
+// SW summed in units of 2^-32 like first-play urgency's, so that it does not depend on which lane holds which child.  With
+// YY_FLAG_GUMBEL_INTERIOR (vhat: the root record's evaluator value) the target is gumbel_improved's pi', completed with v_mix.
 template <int NW>
-__device__ __forceinline__ void gumbel_distribution(const MctsDev &d, const uint4 *edges, const int first, const int k, double *pi) {
+__device__ __forceinline__ void gumbel_distribution(const MctsDev &d, const uint4 *edges, const int first, const int k,
+                                                    const float vhat, double *pi) {
     const int A = d.geo.A;
     uint4 e[NW];
     int mx = 0, sn = 0;
@@ -623,6 +734,20 @@ __device__ __forceinline__ void gumbel_distribution(const MctsDev &d, const uint
     for (int i = 0; i < NW; i++) {
         const int j = i * 64 + lane_id();
         e[i] = (j < k) ? edges[first + j] : make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (d.g_interior) {                                                         // wave-uniform: completed with v_mix, pi' = t / Z
+        uint64_t t[NW];
+        const GumbelNode gn = gumbel_improved<NW>(d, e, k, vhat, t);
+        for (int a = lane_id(); a < A; a += 64) pi[a] = 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NW; i++)
+            if (i * 64 + lane_id() < k)
+                pi[(int)(e[i].w >> 24)] = (t[i] == GI_NAN) ? __longlong_as_double(0x7FF8000000000000ll) : __ddiv_rn((double)t[i], (double)gn.Z);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
         const int n = (int)e[i].y;
         mx = max(mx, n);
         if (n > 0) {
@@ -670,7 +795,7 @@ template <int NW> __device__ __forceinline__ void root_distribution(const MctsDe
     const uint4 *edges = d.edges + (size_t)g * d.edge_cap;
     const bool act = rfl((int)d.state[g].active) != 0;
     if (d.gumbel && act && k > 0) {                                             // wave-uniform
-        gumbel_distribution<NW>(d, edges, first, k, pi);
+        gumbel_distribution<NW>(d, edges, first, k, rflf(__uint_as_float(hdr.w)), pi);
         return;
     }
     int cn[NW];                                                                 // k <= A <= 64 * NW: edge i*64 + lane

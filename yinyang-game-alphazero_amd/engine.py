@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .options import SHARED_EVALUATIONS_DEFAULT_SLOTS, SHARED_EVALUATIONS_HIGH_WATER, forced_k, fpu_r, gumbel_m, shared_slots
-from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_GUMBEL_ROOT, FLAG_SOLVER, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
+from ._lib import FLAG_ALIASED, FLAG_EVAL_SYMMETRY, FLAG_FORCED_PLAYOUTS, FLAG_FPU_REDUCTION, FLAG_GUMBEL_INTERIOR, FLAG_GUMBEL_ROOT, FLAG_SOLVER, FLAG_REUSE_PASS_VALUE, FLAG_KEEP_EVALUATIONS, FLAG_REUSE_TRANSPOSITIONS, FLAG_ROWCOL, MctsConfig, check, lib
 
 
 def _stream():
@@ -683,6 +683,8 @@ class BatchedMCTS:
     """G games searched in lockstep on one GPU; replaces Node + MCTS.search/_simulate
     (ai/mcts.py:28-225, 275-414).  One game per wavefront; see csrc/yy_engine.hip."""
 
+    gumbel_interior = False                # a context's own once created; run_search reads it
+
     COUNTERS = ("evals", "levels", "children_scanned", "children_created", "terminal_revisits", "nodes", "reused_values",
                 "transposition_hits")
 
@@ -690,8 +692,13 @@ class BatchedMCTS:
                  edges_per_game=0, nodes_per_game=0, reuse_pass_value=False, reuse_transpositions=False,
                  keep_evaluations=False, leaves_per_step=1, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
                  fpu_reduction=None, fpu_reduction_root=None, solver=False, gumbel_root=None, gumbel_c_visit=None,
-                 gumbel_c_scale=None):
-        """gumbel_root=m in 2 .. 64 (copied boards and leaves_per_step == 1 only, not with forced_playouts or solver; None / 0 =
+                 gumbel_c_scale=None, gumbel_interior=False):
+        """gumbel_interior=True (only with gumbel_root, not with fpu_reduction; default off: every launch is what it is without
+        the option, the plain Gumbel root search included): v_mix and completed-Q selection below the root
+        (YY_FLAG_GUMBEL_INTERIOR, include/yy_engine.h).  The root keeps the evaluator's value of its position -- expand_root()
+        then needs value=, which run_search passes --, root_policy() completes unvisited children with v_mix, and a descent
+        below the root takes the child of largest pi'(a) - N(a) / (1 + sum N) instead of the PUCT choice.  Fixed at creation.
+        gumbel_root=m in 2 .. 64 (copied boards and leaves_per_step == 1 only, not with forced_playouts or solver; None / 0 =
         off: every launch is what it is without the option; the paper: 16) with gumbel_c_visit (None: 50) and gumbel_c_scale
         (None: 1.0): the Gumbel root search (YY_FLAG_GUMBEL_ROOT, include/yy_engine.h).  The root spends the search's budget by
         sequential halving over the m children of largest g + log P, g the Gumbel rows of set_gumbel() (gumbel_rows() draws
@@ -737,13 +744,16 @@ class BatchedMCTS:
         self.forced_playouts = forced_k(forced_playouts)
         self.fpu_reduction, self.fpu_reduction_root = fpu_r(fpu_reduction, fpu_reduction_root)
         self.solver = bool(solver)
-        self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
+        self.gumbel_root, self.gumbel_c_visit, self.gumbel_c_scale = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale,
+                                                                              gumbel_interior)
+        self.gumbel_interior = bool(gumbel_interior)
         self._gumbel = None                    # device float32 [G,A] the root expansions read (set_gumbel)
         flags = _flags(rowcol, aliased)
         for flag, on in ((FLAG_REUSE_PASS_VALUE, reuse_pass_value), (FLAG_REUSE_TRANSPOSITIONS, reuse_transpositions),
                          (FLAG_KEEP_EVALUATIONS, keep_evaluations), (FLAG_EVAL_SYMMETRY, self.symmetry[0] == "random"),
                          (FLAG_FORCED_PLAYOUTS, self.forced_playouts), (FLAG_FPU_REDUCTION, self.fpu_reduction),
-                         (FLAG_SOLVER, self.solver), (FLAG_GUMBEL_ROOT, self.gumbel_root)):
+                         (FLAG_SOLVER, self.solver), (FLAG_GUMBEL_ROOT, self.gumbel_root),
+                         (FLAG_GUMBEL_INTERIOR, self.gumbel_interior)):
             flags |= flag if on else 0
         cfg = MctsConfig(self.G, self.R, self.C, self.max_sims, self.cpuct, flags,
                          int(edges_per_game), int(nodes_per_game), int(leaves_per_step), self.symmetry[1] or 0,
@@ -843,12 +853,18 @@ class BatchedMCTS:
         self._advanced = True
         return kept
 
-    def expand_root(self, policy, noise=None, eps=0.25):
+    def expand_root(self, policy, noise=None, eps=0.25, value=None):
+        """value: the evaluator's value of the root call, float32 [rows]; a context with gumbel_interior keeps it in the root
+        record and needs it, every other context discards it (mcts.py:295)."""
         _need(policy, torch.float32, (self.rows, self.A), "policy")
         if noise is not None:
             _need(noise, torch.float64, (self.G, self.A), "noise")
         with torch.cuda.device(self.device):
-            check(lib().yy_mcts_expand_root(self._h, _p(policy), _p(noise), float(eps), _stream()))
+            if value is None:
+                check(lib().yy_mcts_expand_root(self._h, _p(policy), _p(noise), float(eps), _stream()))
+            else:
+                _need(value, torch.float32, (self.rows,), "value")
+                check(lib().yy_mcts_expand_root_value(self._h, _p(policy), _p(value), _p(noise), float(eps), _stream()))
 
     def select(self):
         with torch.cuda.device(self.device):
@@ -946,6 +962,19 @@ class BatchedMCTS:
         with torch.cuda.device(self.device):
             check(lib().yy_mcts_get_boards(self._h, _p(out), _stream()))
         return out
+
+    def tree(self):
+        """The trees as they stand (yy_mcts_tree, for tests and tools): (nodes [G,node_cap,4], edges [G,edge_cap,4] -- the 32-bit words
+        of the records as int32, named in include/yy_engine.h -- and sizes int32 [G,2] = nodes and edges in use)."""
+        caps = (ct.c_int64 * 2)()
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_tree(self._h, None, None, None, caps, None))
+        nodes = torch.empty((self.G, caps[0], 4), dtype=torch.int32, device=self.device)
+        edges = torch.empty((self.G, caps[1], 4), dtype=torch.int32, device=self.device)
+        sizes = torch.empty((self.G, 2), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().yy_mcts_tree(self._h, _p(nodes), _p(edges), _p(sizes), caps, _stream()))
+        return nodes, edges, sizes
 
     def status(self):
         """sync; raises YYError(YY_E_ARENA) when a game's arena overflowed; returns the counters."""
@@ -1052,8 +1081,9 @@ class BatchedMCTS:
             # the budget that the Gumbel root search plans its halving for
             self.set_num_sims(num_sims)
         self.begin(boards, root_players, active)
-        policy, _ = evaluate(True)
-        self.expand_root(policy, noise, eps)
+        policy, value = evaluate(True)
+        # the value of the root call is discarded (mcts.py:295) unless the root keeps it (gumbel_interior: v_mix)
+        self.expand_root(policy, noise, eps, **(dict(value=value) if self.gumbel_interior else {}))
         self.select()
         n_steps = self.steps(num_sims)
         if n_steps == 0:

@@ -137,7 +137,7 @@ class MCTS:
                  dirichlet_noise=True, dirichlet_alpha=0.3, dirichlet_epsilon=0.25, verbose=1,
                  board_semantics="aliased", device=None, evaluation_reuse=False, leaves_per_step=1, tree_reuse=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_seed=0):
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False, gumbel_seed=0):
         """board_semantics: "aliased" = literal reference (the search mutates the caller's board);
         "copied" = every node owns its board (what the reference's own tests assume).
         num_threads is accepted for signature compatibility; simulations of one search are always
@@ -169,7 +169,7 @@ class MCTS:
             evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed, forced_playouts=forced_playouts,
             fpu_reduction=fpu_reduction, fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
             shared_evaluations_replace=shared_evaluations_replace, solver=solver, gumbel_root=gumbel_root,
-            gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+            gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         for name in ("leaves_per_step", "tree_reuse", "forced_playouts", "fpu_reduction", "fpu_reduction_root", "shared_evaluations",
                      "shared_evaluations_replace", "solver"):
             setattr(self, name, getattr(opts, name))

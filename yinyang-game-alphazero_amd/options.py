@@ -137,7 +137,16 @@ class SearchOptions:
     playout cap, free-running, evaluation symmetry, evaluation reuse, the book, both shared tables and fpu_reduction (below the
     root only).  It changes which moves a search picks.  Sequential halving plans the visits of a fresh root in the one-descent
     selection, and the reference has no such option: refused with leaves_per_step > 1, board_semantics="aliased",
-    reference_quirks, rng="numpy", forced_playouts, tree_reuse and solver (each a follow-up)."""
+    reference_quirks, rng="numpy", forced_playouts, tree_reuse and solver (each a follow-up).
+
+    gumbel_interior (needs gumbel_root; default False): the rest of Gumbel AlphaZero (the paper's section 5 and appendix D;
+    include/yy_engine.h YY_FLAG_GUMBEL_INTERIOR).  The root keeps its own network value, an unvisited child
+    is completed with v_mix -- that value mixed with the prior-weighted mean of the visited children's -- in the policy target,
+    and a descent below the root visits the child of largest pi'(a) - N(a) / (1 + sum N), pi' the same completed-Q improved
+    policy, instead of the PUCT choice: deterministic, no exploration constant, no first-play urgency.  The arithmetic is
+    reproducible bit for bit (no log, an exponential of the project's own, integer sums).  It goes with whatever gumbel_root
+    goes with and is refused wherever gumbel_root is; fpu_reduction has nothing left to act on and is refused with it.  It
+    changes which moves a search picks."""
     leaves_per_step: int = 1
     fast_simulations: int = None            # None: the playout cap is off; full_search_probability is then 1.0
     full_search_probability: float = 1.0
@@ -154,6 +163,7 @@ class SearchOptions:
     gumbel_root: int = 0                    # m of the Gumbel root search; 0: off
     gumbel_c_visit: float = 0.0             # resolved: 50 where it was not given; 0.0 when the option is off
     gumbel_c_scale: float = 0.0             # resolved: 1.0 where it was not given; 0.0 when the option is off
+    gumbel_interior: bool = False           # v_mix and completed-Q selection below the root (needs gumbel_root)
 
     @property
     def playout_cap(self):
@@ -190,7 +200,9 @@ HANDED_ON = (("fast_simulations", ("fast_simulations", "full_search_probability"
              ("shared_evaluations", ("shared_evaluations",), False),
              ("shared_evaluations_replace", ("shared_evaluations_replace",), False),
              ("solver", ("solver",), True),
-             ("gumbel_root", ("gumbel_root", "gumbel_c_visit", "gumbel_c_scale"), True))
+             ("gumbel_root", ("gumbel_root", "gumbel_c_visit", "gumbel_c_scale"), True),
+             # a sub-option of the Gumbel group, in a row of its own so that both views carry it only when it is on
+             ("gumbel_interior", ("gumbel_interior",), True))
 
 
 def forced_k(forced_playouts):
@@ -210,17 +222,22 @@ def forced_k(forced_playouts):
 GUMBEL_C_VISIT, GUMBEL_C_SCALE = 50.0, 1.0   # the paper's board-game values
 
 
-def gumbel_m(gumbel_root, gumbel_c_visit=None, gumbel_c_scale=None):
+def gumbel_m(gumbel_root, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
     """(m, c_visit, c_scale) as the device takes them: (0, 0.0, 0.0) for gumbel_root None / 0 (off), else the int m in 2 .. 64,
     the finite c_visit >= 0 (None: 50) and the finite c_scale > 0 (None: 1.0).  OptionConflict naming gumbel_root for anything
-    else, a c value without the option included."""
+    else, a c value or gumbel_interior (None / False / True) without the option included."""
     def num(x):
         try:
             return float(x)
         except (TypeError, ValueError):
             return float("nan")
 
+    if gumbel_interior not in (None, False, True):
+        raise OptionConflict(f"gumbel_interior={gumbel_interior!r}: True or False", "gumbel_root")
     if gumbel_root is None or gumbel_root is False or (not isinstance(gumbel_root, bool) and gumbel_root == 0):
+        if gumbel_interior:
+            raise OptionConflict("gumbel_interior=True without gumbel_root: it completes the Gumbel root search below the root, "
+                                 "and gumbel_root 0 / None switches that off", "gumbel_root")
         if gumbel_c_visit is not None or gumbel_c_scale is not None:
             raise OptionConflict("gumbel_c_visit / gumbel_c_scale without gumbel_root: they belong to the option, and gumbel_root "
                                  "0 / None switches it off", "gumbel_root")
@@ -305,6 +322,9 @@ RULES = (
     ("gumbel_root", ("leaves_per_step", "board_semantics", "reference_quirks", "rng", "forced_playouts", "tree_reuse", "solver"),
      "sequential halving plans the visits of a fresh root in the one-descent selection on copied boards, its draws are the "
      "device's counter streams, and the reference has no such option -- not with"),
+    ("gumbel_root", ("fpu_reduction",),
+     "gumbel_interior=True selects below the root by the improved policy, so no PUCT score is left for first-play urgency to act "
+     "on -- not with"),
     ("free_running", ("leaves_per_step", "board_semantics", "reference_quirks", "rng", "tree_reuse"),
      "the in-step move plays copied boards with one descent per step, the device's counter streams and a fresh root per move "
      "-- not with"),
@@ -336,7 +356,7 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
             evaluation_reuse=(), opening_book=None, fast_simulations=None, full_search_probability=1.0, tree_reuse=False,
             free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
             fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
-            solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
+            solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
     """The SearchOptions of one combination, or OptionConflict (a ValueError) -- on the host, before anything touches the
     device.  Every default means "off" / "not given", so a caller passes what it has.  evaluation_reuse: the reuse options as
     given (None = the default, which K > 1 resolves to off); opening_book: an engine.OpeningBook or a stone count (None and
@@ -361,7 +381,10 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     given["forced_playouts"] = (forced, f"forced_playouts={forced_playouts}")
     if forced:
         _ask("forced_playouts", given["forced_playouts"][1], given)
-    gm, gcv, gcs = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale)
+    gm, gcv, gcs = gumbel_m(gumbel_root, gumbel_c_visit, gumbel_c_scale, gumbel_interior)
+    # first-play urgency is in the way of the Gumbel group only when gumbel_interior is on (its value is checked below)
+    given["fpu_reduction"] = (bool(gumbel_interior) and fpu_reduction is not None and fpu_reduction != 0,
+                              f"fpu_reduction={fpu_reduction}")
     if gm:
         _ask("gumbel_root", f"gumbel_root={gumbel_root}", given)
     if free_running:
@@ -398,4 +421,4 @@ def resolve(num_simulations=None, leaves_per_step=1, board_semantics="copied", r
     cap = fast is not None and P < 1.0
     return SearchOptions(K, fast if cap else None, P if cap else 1.0, bool(tree_reuse), bool(free_running),
                          evaluation_symmetry, None if not sym or symmetry_seed is None else int(symmetry_seed), forced, fpu, fpu_root,
-                         shared, bool(shared_evaluations_replace), bool(solver), gm, gcv, gcs)
+                         shared, bool(shared_evaluations_replace), bool(solver), gm, gcv, gcs, bool(gumbel_interior))

@@ -89,7 +89,7 @@ class _Engine:
                  opening_book=None, stream=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
+                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
         """gumbel_root m (default off) with gumbel_c_visit / gumbel_c_scale: the Gumbel root search in every search, fast and full
         alike (options.SearchOptions) -- every root draws its Gumbel variables from the game's own counter stream (keyed by seed,
         game index and ply), spends its budget by sequential halving, records the completed-Q policy target as pi and plays
@@ -130,7 +130,7 @@ class _Engine:
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, self.free_running, evaluation_symmetry, symmetry_seed,
                                forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
-                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         if opts.shared_evaluations and not getattr(evaluator, "row_independent", False):
             raise ValueError("shared_evaluations: a stored row stands in for the evaluator's, so the evaluator must declare "
                              "`row_independent` (a row's result does not depend on the rest of the batch); this one does not")
@@ -662,8 +662,8 @@ class SelfPlayLanes:
                  reuse_pass_value=None, reuse_transpositions=None, keep_evaluations=None, rng="philox", leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False, evaluation_symmetry="off",
                  symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None,
-                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, **engine_kwargs):
-        """gumbel_root / gumbel_c_visit / gumbel_c_scale: the Gumbel root search in every lane (options.SearchOptions).
+                 shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False, **engine_kwargs):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale / gumbel_interior: the Gumbel root search in every lane (options.SearchOptions).
         solver: the MCTS-Solver in every lane (options.SearchOptions).
         shared_evaluations: every lane gets a shared evaluation table of its own (one per context and stream), each of the
         size asked for; memory_bytes() reports their sum.  shared_evaluations_replace: every lane's table is a replacing one,
@@ -676,7 +676,7 @@ class SelfPlayLanes:
                                (reuse_pass_value, reuse_transpositions, keep_evaluations), opening_book, fast_simulations,
                                full_search_probability, tree_reuse, free_running, evaluation_symmetry, symmetry_seed,
                                forced_playouts, fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace,
-                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+                               solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         self.free_running, self.leaves_per_step = opts.free_running, opts.leaves_per_step
         symmetry = engine.symmetry_key(opts.evaluation_symmetry, seed if opts.symmetry_seed is None else opts.symmetry_seed)
         engine_kwargs.update(board_semantics=board_semantics, reference_quirks=reference_quirks, rng=rng,
@@ -880,8 +880,8 @@ class SelfPlayWorker:
                  board_semantics="aliased", reference_quirks=True, neural_net=None, device=None, leaves_per_step=1,
                  fast_simulations=None, full_search_probability=1.0, tree_reuse=False, free_running=False,
                  evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None, fpu_reduction=None, fpu_reduction_root=None,
-                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
-        """gumbel_root / gumbel_c_visit / gumbel_c_scale: MCTS's (needs board_semantics="copied" and reference_quirks=False, which
+                 shared_evaluations=None, shared_evaluations_replace=False, solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale / gumbel_interior: MCTS's (needs board_semantics="copied" and reference_quirks=False, which
         are not this class's defaults); every search draws its Gumbel rows in MCTS and the move played is the Gumbel winner at
         every ply (MCTS.gumbel_action), so numpy's stream is not asked for the move.
         solver: MCTS's (needs board_semantics="copied" and reference_quirks=False, which are not this class's defaults).
@@ -902,7 +902,7 @@ class SelfPlayWorker:
                                evaluation_symmetry=evaluation_symmetry, symmetry_seed=symmetry_seed,
                                forced_playouts=forced_playouts, fpu_reduction=fpu_reduction,
                                fpu_reduction_root=fpu_reduction_root, shared_evaluations=shared_evaluations,
-                               shared_evaluations_replace=shared_evaluations_replace, solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+                               shared_evaluations_replace=shared_evaluations_replace, solver=solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         self.gumbel_root = opts.gumbel_root
         self.tree_reuse, self.leaves_per_step, self.playout_cap = opts.tree_reuse, opts.leaves_per_step, opts.playout_cap
         self.game, self.model_path = game, model_path
@@ -1007,8 +1007,8 @@ class SelfPlayManager:
                  opening_book_stones=None, lanes=None, leaves_per_step=1, fast_simulations=None, full_search_probability=1.0,
                  tree_reuse=False, free_running=False, evaluation_symmetry="off", symmetry_seed=None, forced_playouts=None,
                  fpu_reduction=None, fpu_reduction_root=None, shared_evaluations=None, shared_evaluations_replace=False,
-                 solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None):
-        """gumbel_root / gumbel_c_visit / gumbel_c_scale: the Gumbel root search (options.SearchOptions),
+                 solver=False, gumbel_root=None, gumbel_c_visit=None, gumbel_c_scale=None, gumbel_interior=False):
+        """gumbel_root / gumbel_c_visit / gumbel_c_scale / gumbel_interior: the Gumbel root search (options.SearchOptions),
         solver (its three counters go into `stats` as solver_*, in lockstep runs: a free-running context stays armed, and
         the counters are read after a finished search),
         leaves_per_step, fast_simulations / full_search_probability, tree_reuse, free_running, evaluation_symmetry / symmetry_seed
@@ -1021,7 +1021,7 @@ class SelfPlayManager:
         self.options = options.resolve(num_simulations, leaves_per_step, board_semantics, reference_quirks, "philox",
                                        (evaluation_reuse,), opening_book_stones, fast_simulations, full_search_probability,
                                        tree_reuse, free_running, evaluation_symmetry, symmetry_seed, forced_playouts,
-                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace, solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+                                       fpu_reduction, fpu_reduction_root, shared_evaluations, shared_evaluations_replace, solver, gumbel_root=gumbel_root, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale, gumbel_interior=gumbel_interior)
         self.evaluation_reuse = evaluation_reuse
         self.lanes = lanes                 # HIP streams the rank's games are cut over (SelfPlayLanes); None = 2 from 512 slots on
         # None = 8 stones when it pays: evaluation reuse on, a board of at most 64 cells (770 k positions at 8x8: ~1.5 s to build)
@@ -1091,7 +1091,7 @@ def generate_self_play_data(game, model_path, output_dir, num_games=100, num_wor
     layout as well (training.save_examples_reference_format) so that the reference's training pipeline can read the file.
     leaves_per_step, fast_simulations, full_search_probability: SelfPlayManager's, checked here before anything is written;
     the other keywords (tree_reuse, free_running, forced_playouts, fpu_reduction / fpu_reduction_root, shared_evaluations,
-    shared_evaluations_replace, solver and gumbel_root / gumbel_c_visit / gumbel_c_scale among them) are SelfPlayManager's too."""
+    shared_evaluations_replace, solver and gumbel_root / gumbel_c_visit / gumbel_c_scale / gumbel_interior among them) are SelfPlayManager's too."""
     opts = options.resolve(num_simulations, leaves_per_step, fast_simulations=fast_simulations,
                            full_search_probability=full_search_probability)
     os.makedirs(output_dir, exist_ok=True)
